@@ -18,9 +18,14 @@ rank processes its own 128-crop shard of the global minibatch (weak scaling), th
 640x480 depth frames through the CoM-refinement cascade (crop -> centre of mass -> ScaleNet -> crop, hipdp/cascade.py) and trains the
 256x256 ResNet on it -- one plan per step.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the kernel family with the largest share of the step time,
-timed live with HIP events on the launch stream; `cpu_baseline` times the oracle's PyTorch-CPU restatement of the same
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`,
+`ms_per_step`, `config`); everything else it can measure or check runs only with `--full`: `roofline` describes the kernel
+family with the largest share of the step time, timed live with HIP events on the launch stream; the forward-only,
+no-augmentation, config 3 / config 5 and trainer legs; `cpu_baseline` times the oracle's PyTorch-CPU restatement of the same
 train step on the host cores (reported only).
+
+`--dump-outputs DIR` writes what the last timed step computed as float32 .npy files (dump_outputs): with the same arguments
+the inputs are the same from run to run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -397,7 +402,7 @@ def _mfma_busy_from_profiles(kernel_family, B, S, args):
 
 def _sub_bench(extra_args, timeout=900):
     """One more configuration of this script in a process of its own (own device allocations, own DPP_BF16): its JSON line."""
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--headline-only', '--no-cpu-baseline', '--no-trainer'] + extra_args,
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--full', '--headline-only', '--no-cpu-baseline', '--no-trainer'] + extra_args,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
     if r.returncode != 0:
         return dict(error=r.stderr.decode(errors='replace')[-800:])
@@ -478,6 +483,38 @@ def config3_leg(rt, torch, iters=200):
     return out
 
 
+DUMP_CAP = 2 << 20        # float32 elements per dumped array: six arrays stay under 64 MB
+
+
+def dump_outputs(eng, out_dir):
+    """`--dump-outputs DIR`: what the last timed step computed, as float32 DIR/<name>.npy, read right after the timed region (before
+    anything else runs on the engine):
+      cost              the train step's cost, (1,)
+      output            the net's output of the step's forward pass, (batch, 30)
+      params            every trained parameter after the step's ADAM update, in the reference's layout, concatenated in the net's order
+      bn_running_stats  the BatchNorm running statistics the step updated, concatenated the same way
+      minibatch_crops / minibatch_labels
+                        the augmented minibatch in the engine's input buffers: the one the last step prefetched for the next (default),
+                        or its own (--augment-inline)
+    An array larger than DUMP_CAP elements is flattened and sampled at DUMP_CAP positions drawn by RandomState(0) (sorted): the same
+    positions in every run with the same arguments."""
+    st = eng.store
+    vals = st.bulk_values()
+
+    def cat(trained):
+        parts = [np.asarray(vals[s['param'].auto_name], np.float32).ravel() for s in st.slots if s['trained'] == trained]
+        return np.concatenate(parts) if parts else np.zeros(0, np.float32)
+
+    arrays = dict(cost=eng.cost.get()[:1], output=eng.out.get_f32(), params=cat(True), bn_running_stats=cat(False),
+                  minibatch_crops=eng.x_in.get_f32(), minibatch_labels=eng.y_in.get())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, np.float32)
+        if a.size > DUMP_CAP:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, DUMP_CAP, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks with torch.distributed.run (one per GPU, RCCL)."""
     import torch
@@ -510,15 +547,23 @@ def main():
     ap.add_argument('--augment-inline', action='store_true',
                     help='augment the minibatch at the start of its own step on the main stream (default: the previous step does it '
                          'on the gradient-branch stream while ADAM runs)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--headline-only', action='store_true', help='the timed steps and the roofline only: none of the extra legs (forward_only, '
-                    'no_augment, config3, config5); what the extra legs themselves run')
-    ap.add_argument('--no-trainer', action='store_true', help="skip config.trainer_ms_per_minibatch (a short PoseRegNetTrainer.train() run)")
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, everything else this script measures or checks: the per-kernel-family roofline, the '
+                         'forward_only / no_augment / config3 / config5 legs, the trainer leg, the bf16 forward error, the CPU baselines, '
+                         'the forward parity and the exposed all-reduce time (default: the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines and the forward parity')
+    ap.add_argument('--headline-only', action='store_true', help='with --full: the timed steps and the roofline only: none of the extra legs '
+                    '(forward_only, no_augment, config3, config5); what the extra legs themselves run')
+    ap.add_argument('--no-trainer', action='store_true', help="with --full: skip config.trainer_ms_per_minibatch (a short "
+                    "PoseRegNetTrainer.train() run)")
     ap.add_argument('--sync-bn', action='store_true', help='all-gather BatchNorm partial statistics across ranks (parity mode)')
     ap.add_argument('--launch', choices=['native', 'python', 'graph', 'graph1'], default=None,
                     help='native = the step is one C call that issues every launch on two HIP streams (default); python = one '
                          'ctypes call per launch; graph / graph1 = explicit hipGraph with two lanes / one chain')
-    ap.add_argument('--profile-ops', action='store_true', help='print the per-kernel-family time table to stderr')
+    ap.add_argument('--profile-ops', action='store_true', help='print the per-kernel-family time table to stderr (times the families '
+                    'as --full does)')
     ap.add_argument('--workload', choices=['train', 'cascade'], default='train',
                     help="train (default): BASELINE configs[1]; cascade: configs[4] on this GPU -- every step crops its minibatch from "
                          "640x480 frames through the CoM-refinement cascade (crop -> CoM -> ScaleNet -> crop at --size) and trains the "
@@ -705,10 +750,14 @@ def main():
         if dist.get_backend() == 'nccl' and len(set(dist_info['devices'])) != world:
             raise SystemExit('bench.py: %d RCCL ranks on %d distinct GPUs (%s): one rank per GPU is the contract' % (
                 world, len(set(dist_info['devices'])), dist_info['devices']))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
     # how much of the step the main stream stood still for the gradient exchange (round 6): ten MORE steps, after the timed region,
     # with an event pair around every join with a collective (an event is a marker packet: not something the timed steps carry)
     exposed_ms = 0.0
-    if dp is not None and not emu:
+    if dp is not None and not emu and not args.full:
+        exposed_ms = None                   # measured with --full only
+    elif dp is not None and not emu:
         dp.measure_exposed = True
         for _ in range(10):
             step()
@@ -716,11 +765,12 @@ def main():
         exposed_ms = dp.exposed_ms() / 10.0
         dp.measure_exposed = False
     seg = step_plans[0][1].segment_counts() if hasattr(step_plans[0][1], 'segment_counts') else (1, 0)
-    dist_info.update(allreduce_ms_exposed=[round(exposed_ms, 4)], launch_segments_per_step=seg[0], host_issued_collectives_per_step=seg[1],
+    exposed = round(exposed_ms, 4) if exposed_ms is not None else None
+    dist_info.update(allreduce_ms_exposed=[exposed], launch_segments_per_step=seg[0], host_issued_collectives_per_step=seg[1],
                      allreduce_schedule=getattr(dp, 'schedule', None))
     if dist is not None:
         rows = [None] * world
-        dist.all_gather_object(rows, round(exposed_ms, 4))
+        dist.all_gather_object(rows, exposed)
         dist_info['allreduce_ms_exposed'] = rows
     cost = float(eng.cost.get()[0])
     ms = elapsed / args.steps * 1e3
@@ -732,7 +782,7 @@ def main():
     # event behind every launch; an event is a marker packet of its own that costs the queue ~5 us -- profiles/r02_join_probe.txt --
     # which inflated the average launch of the 10-20 us GEMMs by a third against the rocprofv3 kernel trace.)
     fam = {}
-    if rank == 0 and not emu:
+    if rank == 0 and not emu and (args.full or args.profile_ops):
         stream = torch.cuda.current_stream()
         allops = [('aug', o) for o in step_plans[0][0].launches()] + eng.all_launches()
         groups = {}
@@ -837,7 +887,7 @@ def main():
             fl = [((o.meta or {}).get('kernel', ''), (o.meta or {}).get('flops', 0.0)) for _, o in eng.all_launches()]
             mf = sum(f for k, f in fl if 'mfma' in k)
             res['config']['bf16_mfma_flop_share'] = round(sum(f for k, f in fl if 'mfma_bf16' in k) / mf, 4) if mf else None
-        if world == 1 and not emu and args.workload == 'train' and not args.headline_only:
+        if args.full and world == 1 and not emu and args.workload == 'train' and not args.headline_only:
             # the other legs BASELINE.md section 3 lists, after the timed region: the train step WITHOUT the augmentation launch, and the
             # deterministic forward alone (computeOutput's device function)
             plain = eng.step_plan()
@@ -855,7 +905,7 @@ def main():
                                      mode='fwd + bwd + ADAM on a resident minibatch, no augmentation launch, HIP events over %d steps' % args.steps)
             xb = np.ascontiguousarray(eng.x_in.buf.get().reshape(B, 1, S, S), np.float32)
             res['forward_only'] = forward_only_leg(rt, torch, net, B, S, xb)
-        if args.dtype == 'bf16':
+        if args.full and args.dtype == 'bf16':
             # forward error of the bf16 path against the fp32 path on the SAME (just trained) weights, deterministic mode (SURVEY.md
             # section 8(d) cfg 5: "parity reported vs fp32, not vs the 1e-3 mm bar").  The number to read is RELATIVE: the embedding of
             # this synthetic run is untrained and its PCA prior a random orthonormal basis, so "mm" obtained by pushing the difference
@@ -872,14 +922,14 @@ def main():
                                                                 nominal_mm=dict(max=round(float(np.abs(dj).max() * 150.0), 4),
                                                                                 mean=round(float(np.abs(dj).mean() * 150.0), 4),
                                                                                 note='untrained embedding through a random orthonormal prior: not a physical error'))
-        if world == 1 and not emu and args.workload == 'train' and S == 128 and args.dtype == 'f32' and not args.no_trainer:
+        if args.full and world == 1 and not emu and args.workload == 'train' and S == 128 and args.dtype == 'f32' and not args.no_trainer:
             # the drop-in class API next to the engine's number (same GPU, same build, right after the timed region)
             res['config']['trainer_ms_per_minibatch'] = trainer_ms_per_minibatch(rt, B, S)
-        if world == 1 and not emu and args.workload == 'train' and S == 128 and B == 128 and args.dtype == 'f32' and not args.headline_only:
+        if args.full and world == 1 and not emu and args.workload == 'train' and S == 128 and B == 128 and args.dtype == 'f32' and not args.headline_only:
             # the other single-GPU configurations of BASELINE.json, timed by whoever runs this script
             res['config3'] = config3_leg(rt, torch)
             res['config5'] = config5_leg()
-        if world == 1 and not args.no_cpu_baseline and not emu and args.workload == 'train':
+        if args.full and world == 1 and not args.no_cpu_baseline and not emu and args.workload == 'train':
             res['cpu_baseline'], extra = cpu_baseline(B, S)
             res.update(extra)
             if args.dtype == 'f32':

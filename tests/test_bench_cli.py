@@ -58,7 +58,7 @@ def test_gpus_2_with_gloo_ranks_sharing_the_one_mi355x():
 def test_one_gpu_line_carries_the_forward_only_and_no_augment_legs():
     """"crops/s (fwd only; fwd+bwd+ADAM; with/without augmentation)" in ONE line, plus the device's own clock and
     the participating device."""
-    rc, out, err = _bench(['--steps', '5', '--warmup', '2', '--no-cpu-baseline', '--no-trainer'], timeout=600)
+    rc, out, err = _bench(['--full', '--steps', '5', '--warmup', '2', '--no-cpu-baseline', '--no-trainer'], timeout=600)
     assert rc == 0, err[-3000:]
     res = json.loads([l for l in out.splitlines() if l.startswith('{')][0])
     fo, na = res['forward_only'], res['no_augment']
@@ -149,3 +149,48 @@ def test_cascade_workload_on_the_gpu_full_size():
     assert rc == 0, err[-3000:]
     res = json.loads([l for l in out.splitlines() if l.startswith('{')][0])
     assert res['value'] > 1000 and res['dtype'] == 'bf16' and res['config']['final_cost'] > 0
+
+
+DUMPED = ('bn_running_stats', 'cost', 'minibatch_crops', 'minibatch_labels', 'output', 'params')
+
+
+def _dumped(d):
+    assert sorted(f for f in os.listdir(d)) == sorted(n + '.npy' for n in DUMPED)
+    arrs = {n: np.load(os.path.join(d, n + '.npy')) for n in DUMPED}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    return arrs
+
+
+def test_dump_outputs_repeat_run_to_run(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step computed; with the same arguments two runs write the same arrays.  A plain
+    run carries the headline only (no roofline, no extra legs) and times exactly --steps steps."""
+    runs = []
+    for name in ('a', 'b'):
+        rc, out, err = _bench(['--batch', '4', '--size', '32', '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / name)],
+                              env=dict(DPP_BENCH_EMU='1'))
+        assert rc == 0, err[-3000:]
+        res = json.loads([l for l in out.splitlines() if l.startswith('{')][0])
+        assert res['steps'] == 3 and res['ms_per_step'] > 0 and res['roofline'] is None
+        assert not {'forward_only', 'no_augment', 'config3', 'config5', 'cpu_baseline'} & set(res)
+        arrs = _dumped(str(tmp_path / name))
+        assert arrs['output'].shape == (4, 30) and arrs['minibatch_crops'].size == 4 * 32 * 32 and arrs['minibatch_labels'].shape == (4, 30)
+        assert round(float(arrs['cost'][0]), 5) == res['config']['final_cost']
+        runs.append(arrs)
+    for n in DUMPED:
+        assert np.array_equal(runs[0][n], runs[1][n]), n
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """The plain bs128 run on the MI355X: headline fields only, and the dump holds the last timed step (its cost is the line's
+    final_cost; the full parameter vector is sampled to stay within 64 MB)."""
+    rc, out, err = _bench(['--steps', '5', '--warmup', '2', '--dump-outputs', str(tmp_path)], timeout=600)
+    assert rc == 0, err[-3000:]
+    res = json.loads([l for l in out.splitlines() if l.startswith('{')][0])
+    assert res['steps'] == 5 and res['ms_per_step'] > 0 and res['roofline'] is None and 'forward_only' not in res
+    assert 0.5 * res['ms_per_step'] < res['config']['hip_event_ms_per_step'] <= res['ms_per_step'] * 1.05
+    arrs = _dumped(str(tmp_path))
+    assert arrs['output'].shape == (128, 30) and arrs['minibatch_crops'].size == 128 * 128 * 128
+    assert arrs['params'].size == 2 << 20
+    assert round(float(arrs['cost'][0]), 5) == res['config']['final_cost']

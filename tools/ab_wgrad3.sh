@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/r03
 export DPP_EXPERIMENT=1
 run() {
-  python bench.py --steps 300 --warmup 30 --allow-ablation --no-cpu-baseline "$@" 2>&1 | python -c "
+  python bench.py --full --steps 300 --warmup 30 --allow-ablation --no-cpu-baseline "$@" 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -7,7 +7,7 @@ O=$R/gpurun_out/$ROUND
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # kernel trace of the measured configuration (bench defaults: native plan, two streams) -- kernel-trace only, no counters
-rocprofv3 --kernel-trace -d /tmp/p1 -o run -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --headline-only --no-trainer > /dev/null 2>&1
+rocprofv3 --kernel-trace -d /tmp/p1 -o run -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --headline-only --no-trainer > /dev/null 2>&1
 python $R/tools/prof_summary.py $(find /tmp/p1 -name '*_results.db' | head -1) 28 > $O/kernel_stats_bench.txt 2>&1
 # un-overlapped kernel durations, one line per (kernel, grid)
 DPP_NO_SIDE_STREAM=1 rocprofv3 --kernel-trace -d /tmp/p2 -o run -- python $R/tools/step_profile.py 8 > /dev/null 2>&1
@@ -51,12 +51,12 @@ python $R/tools/prof_summary.py $(find /tmp/p9 -name '*_results.db' | head -1) 3
 python $R/tools/branch_probe.py > $O/branch_probe.txt 2>/dev/null
 python $R/tools/launch_rate.py > $O/launch_rate.txt 2>/dev/null
 # the other bench modes of BASELINE.json
-python $R/bench.py --no-cpu-baseline --dtype bf16 > $O/bench_bf16_128.json 2>/dev/null
-python $R/bench.py --no-cpu-baseline --size 256 --steps 20 --warmup 5 > $O/bench_f32_256.json 2>/dev/null
-python $R/bench.py --no-cpu-baseline --size 256 --steps 20 --warmup 5 --dtype bf16 > $O/bench_bf16_256.json 2>/dev/null
-python $R/bench.py --no-cpu-baseline --batch 256 > $O/bench_bs256.json 2>/dev/null
-python $R/bench.py --no-cpu-baseline --workload cascade --size 256 --steps 20 --warmup 5 > $O/bench_cascade_f32_256.json 2>/dev/null
-python $R/bench.py --no-cpu-baseline --workload cascade --size 256 --steps 20 --warmup 5 --dtype bf16 > $O/bench_cascade_bf16_256.json 2>/dev/null
+python $R/bench.py --full --no-cpu-baseline --dtype bf16 > $O/bench_bf16_128.json 2>/dev/null
+python $R/bench.py --full --no-cpu-baseline --size 256 --steps 20 --warmup 5 > $O/bench_f32_256.json 2>/dev/null
+python $R/bench.py --full --no-cpu-baseline --size 256 --steps 20 --warmup 5 --dtype bf16 > $O/bench_bf16_256.json 2>/dev/null
+python $R/bench.py --full --no-cpu-baseline --batch 256 > $O/bench_bs256.json 2>/dev/null
+python $R/bench.py --full --no-cpu-baseline --workload cascade --size 256 --steps 20 --warmup 5 > $O/bench_cascade_f32_256.json 2>/dev/null
+python $R/bench.py --full --no-cpu-baseline --workload cascade --size 256 --steps 20 --warmup 5 --dtype bf16 > $O/bench_cascade_bf16_256.json 2>/dev/null
 python $R/tools/trainer_throughput.py 2>/dev/null | tail -1 > $O/trainer_throughput.txt
 python $R/tools/augment_bench.py > $O/augment_bench.json 2> $O/augment_bench.err
 python $R/tools/augment_bench.py --batch 4096 --iters 50 >> $O/augment_bench.json 2>> $O/augment_bench.err
@@ -66,5 +66,5 @@ cp $O/hbm_traffic.json $R/profiles/${ROUND}_hbm_traffic.json
 cp $O/mfma_busy.json $R/profiles/${ROUND}_mfma_busy.json
 cp $O/hbm_traffic_256_bf16.json $R/profiles/${ROUND}_hbm_traffic_256_bf16.json
 cp $O/hbm_traffic_forward.json $R/profiles/${ROUND}_hbm_traffic_forward.json
-python $R/bench.py > $O/bench.json 2> $O/bench.err
+python $R/bench.py --full > $O/bench.json 2> $O/bench.err
 ls -la $O
