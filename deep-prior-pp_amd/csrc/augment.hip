@@ -1045,6 +1045,205 @@ __global__ __launch_bounds__(DPP_THREADS) void crop_refine_kernel(const float* _
     }
 }
 
+// ---- HandDetector crop helpers (ABI v12): bilinearResize, resizeCrop, recropHand, getInverseCrop, applyCrop3D ----------
+// /root/reference/src/util/handdetector.py:132-202 (bilinearResize), :298-351 (getInverseCrop, resizeCrop), :353-380 (applyCrop3D),
+// :782-803 (recropHand).  One launch per batch, one thread per output pixel.
+constexpr int CW_NORMALIZE = 1, CW_BILINEAR = 2, CW_NO_RANGE = 4, CW_NO_THRESH = 8;     // dpp_crop_warp_ex flags
+
+// crop_window_value with applyCrop3D's options: `pad` outside the frame (getCrop's `background`), the detector's range test and
+// the z-threshold each optional
+__device__ __forceinline__ float crop_window_value_ex(const float* __restrict__ frame, int H, int W, const CropRec& r, long long sx, long long sy,
+                                                      int flags, float pad) {
+    const long long gx = r.xstart + sx, gy = r.ystart + sy;
+    float v = pad;
+    if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+        v = frame[(size_t)gy * W + gx];
+        if (!(flags & CW_NO_RANGE) && (v > r.max_depth || v < r.min_depth)) v = 0.0f;
+    }
+    if (!(flags & CW_NO_THRESH) && v != 0.0f) {
+        if (v < r.zstart) v = r.zstart;
+        else if (v > r.zend) v = 0.0f;
+    }
+    return v;
+}
+
+struct PlaneSrc {              // a dense [sh][sw] crop as a bilinearResize source
+    const float* s;
+    int sw;
+    __device__ __forceinline__ float operator()(int x, int y) const { return s[(size_t)y * sw + x]; }
+};
+
+struct WindowSrc {             // getCrop's window of one frame as a bilinearResize source
+    const float* f;
+    int H, W, flags;
+    float pad;
+    const CropRec* r;
+    __device__ __forceinline__ float operator()(int x, int y) const { return crop_window_value_ex(f, H, W, *r, x, y, flags, pad); }
+};
+
+// HandDetector.bilinearResize (handdetector.py:132-202) at destination pixel (col, row) of an sw x sh -> dw x dh resize: the
+// reference's arithmetic step for step.  It ran on NumPy 1, where a float32 element times a Python float is a float64, so the
+// weights and the weighted sum are f64 (no contraction: -ffp-contract=off), rounded once to f32.  More than two of the four taps
+// equal to `nd` -> nd; a tap equal to nd loses its weight, the reference's re-balancing in its order; weights scaled by
+// 1 / sum; all weights zero -> nd.  The host refuses sources narrower or shorter than 2 pixels (the reference's "Shape mismatch");
+// the clamp of x + 1 / y + 1 only keeps every read inside the source.
+template <class Src>
+__device__ __forceinline__ float bilinear_nd(const Src& src, int sw, int sh, int dw, int dh, int col, int row, float nd) {
+    const double x_ratio = (double)(sw - 1) / (double)dw, y_ratio = (double)(sh - 1) / (double)dh;
+    const double fy = (double)row * y_ratio, fx = (double)col * x_ratio;
+    const int y = (int)fy, x = (int)fx;
+    const double y_diff = fy - (double)y, y_diff_2 = 1. - y_diff;
+    const double x_diff = fx - (double)x, x_diff_2 = 1. - x_diff;
+    double y2x2 = y_diff_2 * x_diff_2, y2x = y_diff_2 * x_diff, yx2 = y_diff * x_diff_2, yx = y_diff * x_diff;
+    const int x1 = x + 1 < sw ? x + 1 : sw - 1, y1 = y + 1 < sh ? y + 1 : sh - 1;
+    const float a = src(x, y), b = src(x1, y), c = src(x, y1), d = src(x1, y1);
+    const bool na = a == nd, nb = b == nd, nc = c == nd, nd4 = d == nd;
+    if ((int)na + (int)nb + (int)nc + (int)nd4 > 2) return nd;
+    if (na) { y2x2 = 0.; y2x = 1. - yx - yx2; }
+    if (nb) { y2x = 0.; if (y2x2 != 0.) y2x2 = 1. - yx - yx2; }
+    if (nc) { yx2 = 0.; yx = 1. - y2x - y2x2; }
+    if (nd4) { yx = 0.; if (yx2 != 0.) yx2 = 1. - y2x - y2x2; }
+    if (!(y2x2 == 0. && y2x == 0. && yx2 == 0. && yx == 0.)) {
+        const double sc = 1. / (yx + yx2 + y2x + y2x2);
+        y2x2 *= sc; y2x *= sc; yx2 *= sc; yx *= sc;
+    }
+    if (y2x2 == 0. && y2x == 0. && yx2 == 0. && yx == 0.) return nd;
+    return (float)(y2x2 * (double)a + y2x * (double)b + yx2 * (double)c + yx * (double)d);
+}
+
+// crop_warp with the options of the reference's other callers of the window resize: bilinear mode (cropArea3D / applyCrop3D with
+// resizeMethod = RESIZE_BILINEAR), no detector range test (applyCrop3D crops an arbitrary image), z-threshold off, getCrop's pad value
+// and a fill value outside the paste of their own.  flags = 0 with fill_value = nd_value and pad 0 is crop_warp_kernel.
+__global__ __launch_bounds__(DPP_THREADS) void crop_warp_ex_kernel(const float* __restrict__ frames, int H, int W, const CropRec* __restrict__ rec,
+                                                                   int dsz, int flags, float nd_value, float fill_value, float pad_value,
+                                                                   float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int p = blockIdx.x * DPP_THREADS + threadIdx.x;
+    if (p >= dsz * dsz) return;
+    const CropRec r = rec[b];
+    const float* f = frames + (size_t)b * H * W;
+    const int y = p / dsz, x = p - y * dsz;
+    float v = fill_value;
+    const int rx = x - r.xs, ry = y - r.ys;
+    if (rx >= 0 && rx < r.szw && ry >= 0 && ry < r.szh) {
+        if (flags & CW_BILINEAR) {
+            const WindowSrc src{f, H, W, flags, pad_value, &r};
+            v = bilinear_nd(src, r.cw, r.ch, r.szw, r.szh, rx, ry, nd_value);
+        } else {
+            long long sx = (long long)floor((double)rx * r.ifx), sy = (long long)floor((double)ry * r.ify);
+            if (sx > r.cw - 1) sx = r.cw - 1;
+            if (sy > r.ch - 1) sy = r.ch - 1;
+            v = crop_window_value_ex(f, H, W, r, sx, sy, flags, pad_value);
+        }
+    }
+    if (flags & CW_NORMALIZE) {
+        if (v == 0.0f) v = r.far_v;
+        v = (v - r.norm_off) / r.norm_div;
+    }
+    out[(size_t)b * dsz * dsz + p] = v;
+}
+
+// resizeCrop on B same-size crops: cv2 2.4 resizeNN (source index min(floor(x * ifx), sw - 1)) or bilinearResize
+__global__ __launch_bounds__(DPP_THREADS) void resize_crops_kernel(const float* __restrict__ src, int sh, int sw, int dh, int dw, int bilinear,
+                                                                   float nd_value, double ifx, double ify, float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int p = blockIdx.x * DPP_THREADS + threadIdx.x;
+    if (p >= dh * dw) return;
+    const float* s = src + (size_t)b * sh * sw;
+    const int y = p / dw, x = p - y * dw;
+    float v;
+    if (bilinear) {
+        v = bilinear_nd(PlaneSrc{s, sw}, sw, sh, dw, dh, x, y, nd_value);
+    } else {
+        long long sx = (long long)floor((double)x * ifx), sy = (long long)floor((double)y * ify);
+        if (sx > sw - 1) sx = sw - 1;
+        if (sy > sh - 1) sy = sh - 1;
+        v = s[(size_t)sy * sw + sx];
+    }
+    out[(size_t)b * dh * dw + p] = v;
+}
+
+// recropHand (handdetector.py:782-803) on B crops in mm: cv2.warpPerspective(crop, dot(M, Mnew), (tw, th), INTER_NEAREST,
+// BORDER_CONSTANT background) -- the product and cofactor inverse of the augmentation (mat3_mul, mat3_inv), formed once per
+// workgroup, and the 64-wide-block coordinates of aug_warp_pixel --, then isclose(warped, nv_val) -> background (NumPy 1: f64, as
+// in aug_warp_pixel) and the z-threshold against the f32 zrange[b] = (zstart, zend).
+__global__ __launch_bounds__(DPP_THREADS) void recrop_kernel(const float* __restrict__ crops, int h, int w, const double* __restrict__ M,
+                                                             const double* __restrict__ Mnew, int th, int tw, float background, double nv_val,
+                                                             int thresh, const float* __restrict__ zrange, float* __restrict__ out) {
+    __shared__ double s_m[9];
+    const int b = blockIdx.y;
+    if (threadIdx.x == 0) {
+        double A[9], Bm[9], P[9], T[9];
+        for (int i = 0; i < 9; ++i) { A[i] = M[(size_t)b * 9 + i]; Bm[i] = Mnew[(size_t)b * 9 + i]; }
+        mat3_mul(A, Bm, P);
+        mat3_inv(P, T);
+        for (int i = 0; i < 9; ++i) s_m[i] = T[i];
+    }
+    __syncthreads();
+    const int p = blockIdx.x * DPP_THREADS + threadIdx.x;
+    if (p >= th * tw) return;
+    double m[9];
+    for (int i = 0; i < 9; ++i) m[i] = s_m[i];
+    const int y = p / tw, x = p - y * tw;
+    const int bx = (x >> 6) << 6;
+    const double x1 = (double)(x - bx), fbx = (double)bx, fy_ = (double)y;
+    const double X0 = m[0] * fbx + m[1] * fy_ + m[2];
+    const double Y0 = m[3] * fbx + m[4] * fy_ + m[5];
+    const double W0 = m[6] * fbx + m[7] * fy_ + m[8];
+    double Wv = W0 + m[6] * x1;
+    Wv = (Wv != 0.0) ? 1. / Wv : 0.;
+    const double fX = fmax(-2147483648.0, fmin(2147483647.0, (X0 + m[0] * x1) * Wv));
+    const double fY = fmax(-2147483648.0, fmin(2147483647.0, (Y0 + m[3] * x1) * Wv));
+    long long X = cv_round(fX), Y = cv_round(fY);
+    X = X < -32768 ? -32768 : (X > 32767 ? 32767 : X);
+    Y = Y < -32768 ? -32768 : (Y > 32767 ? 32767 : Y);
+    float v = background;
+    if (X >= 0 && X < w && Y >= 0 && Y < h) v = crops[(size_t)b * h * w + (size_t)Y * w + (size_t)X];
+    if (fabs((double)v - nv_val) <= 1e-8 + 1e-5 * fabs(nv_val)) v = background;
+    if (thresh) {
+        const float zlo = zrange[b * 2], zhi = zrange[b * 2 + 1];
+        if (v < zlo && v != 0.0f) v = zlo;
+        else if (v > zhi && v != 0.0f) v = 0.0f;
+    }
+    out[(size_t)b * th * tw + p] = v;
+}
+
+// getInverseCrop (handdetector.py:298-334): crop b resized to its window bounds[b] = (xstart, xend, ystart, yend) and pasted into an
+// H x W canvas of `background`, then the z-threshold over the whole frame.  The reference's three early returns (window entirely
+// left / above, entirely right / below, zero width or height) leave the bare canvas, z-threshold included.
+__global__ __launch_bounds__(DPP_THREADS) void inverse_crop_kernel(const float* __restrict__ crops, int ch, int cw, const int* __restrict__ bounds,
+                                                                   const float* __restrict__ zrange, int H, int W, int bilinear, float nd_value,
+                                                                   float background, int thresh, float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int p = blockIdx.x * DPP_THREADS + threadIdx.x;
+    if (p >= H * W) return;
+    const int xs = bounds[b * 4], xe = bounds[b * 4 + 1], ys = bounds[b * 4 + 2], ye = bounds[b * 4 + 3];
+    const int gy = p / W, gx = p - gy * W;
+    float v = background;
+    const bool early = (xe < 0 && xs < 0) || (ye < 0 && ys < 0) || (xe > W && xs > W) || (ye > H && ys > H) || xe == xs || ye == ys;
+    if (!early) {
+        if (gx >= (xs > 0 ? xs : 0) && gx < (xe < W ? xe : W) && gy >= (ys > 0 ? ys : 0) && gy < (ye < H ? ye : H)) {
+            const float* s = crops + (size_t)b * ch * cw;
+            const int dw = xe - xs, dh = ye - ys, col = gx - xs, row = gy - ys;
+            if (bilinear) {
+                v = bilinear_nd(PlaneSrc{s, cw}, cw, ch, dw, dh, col, row, nd_value);
+            } else {
+                const double ifx = 1. / ((double)dw / (double)cw), ify = 1. / ((double)dh / (double)ch);
+                long long sx = (long long)floor((double)col * ifx), sy = (long long)floor((double)row * ify);
+                if (sx > cw - 1) sx = cw - 1;
+                if (sy > ch - 1) sy = ch - 1;
+                v = s[(size_t)sy * cw + sx];
+            }
+        }
+        if (thresh && v != 0.0f) {
+            const float zlo = zrange[b * 2], zhi = zrange[b * 2 + 1];
+            if (v < zlo) v = zlo;
+            else if (v > zhi) v = 0.0f;
+        }
+    }
+    out[(size_t)b * H * W + p] = v;
+}
+
 }  // namespace
 
 extern "C" size_t dpp_augment_record_bytes(void) { return sizeof(AugRec); }
@@ -1170,5 +1369,46 @@ extern "C" int dpp_crop_refine(const float* frames, const void* records, int B, 
     DPP_LAUNCH(crop_refine_kernel, dim3(B), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
                static_cast<const CropRec*>(records), com_in, cube, net_out, cam, gt3d_orig, J, pca_mean, pca_comp, E, com_out, com3d_out,
                gt3d_crop, out_y);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_crop_warp_ex(const float* frames, const void* records, int B, int H, int W, int dsz, int flags, float nd_value,
+                                float fill_value, float pad_value, float* out, dpp_stream_t stream) {
+    if (!frames || !records || !out || B < 1 || H < 1 || W < 1 || dsz < 1 || (flags & ~15)) return DPP_E_BADARG;
+    dim3 grid(dpp_cdiv(dsz * dsz, DPP_THREADS), B);
+    DPP_LAUNCH(crop_warp_ex_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
+               static_cast<const CropRec*>(records), dsz, flags, nd_value, fill_value, pad_value, out);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_resize_crops(const float* src, int B, int sh, int sw, int dh, int dw, int bilinear, float nd_value, float* out,
+                                dpp_stream_t stream) {
+    if (!src || !out || src == out || B < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1) return DPP_E_BADARG;
+    if (bilinear && (sw < 2 || sh < 2)) return DPP_E_BADARG;           // bilinearResize: "Shape mismatch"
+    const double ifx = 1. / ((double)dw / (double)sw), ify = 1. / ((double)dh / (double)sh);
+    dim3 grid(dpp_cdiv(dh * dw, DPP_THREADS), B);
+    DPP_LAUNCH(resize_crops_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), src, sh, sw, dh, dw, bilinear ? 1 : 0,
+               nd_value, ifx, ify, out);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_recrop(const float* crops, int B, int h, int w, const double* M, const double* Mnew, int th, int tw, float background,
+                          double nv_val, int thresh_z, const float* zrange, float* out, dpp_stream_t stream) {
+    if (!crops || !M || !Mnew || !out || crops == out || B < 1 || h < 1 || w < 1 || th < 1 || tw < 1) return DPP_E_BADARG;
+    if (thresh_z && !zrange) return DPP_E_BADARG;
+    dim3 grid(dpp_cdiv(th * tw, DPP_THREADS), B);
+    DPP_LAUNCH(recrop_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), crops, h, w, M, Mnew, th, tw, background, nv_val,
+               thresh_z ? 1 : 0, zrange, out);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_inverse_crop(const float* crops, int B, int ch, int cw, const int* bounds, const float* zrange, int H, int W, int bilinear,
+                                float nd_value, float background, int thresh_z, float* out, dpp_stream_t stream) {
+    if (!crops || !bounds || !out || crops == out || B < 1 || ch < 1 || cw < 1 || H < 1 || W < 1) return DPP_E_BADARG;
+    if (bilinear && (cw < 2 || ch < 2)) return DPP_E_BADARG;
+    if (thresh_z && !zrange) return DPP_E_BADARG;
+    dim3 grid(dpp_cdiv(H * W, DPP_THREADS), B);
+    DPP_LAUNCH(inverse_crop_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), crops, ch, cw, bounds, zrange, H, W,
+               bilinear ? 1 : 0, nd_value, background, thresh_z ? 1 : 0, out);
     return dpp_launch_status();
 }

@@ -675,6 +675,39 @@ def crop_warp(rt, frames, records, B, H, W, dsz, out, normalize=True, nd_value=0
                   (frames, records, out), name, dict(kernel='crop_warp', flops=10.0 * B * dsz * dsz, bytes=8.0 * B * dsz * dsz))
 
 
+CROP_NORMALIZE, CROP_BILINEAR, CROP_NO_RANGE, CROP_NO_THRESH = 1, 2, 4, 8      # dpp_crop_warp_ex flags
+
+
+def crop_warp_ex(rt, frames, records, B, H, W, dsz, out, flags=0, nd_value=0.0, fill_value=None, pad_value=0.0, name='crop_warp_ex'):
+    """dpp_crop_warp_ex: the initial crop with the bilinear mode and applyCrop3D's options (fill_value defaults to nd_value)."""
+    fill = float(nd_value) if fill_value is None else float(fill_value)
+    taps = 4 if flags & CROP_BILINEAR else 1
+    return Launch(rt.lib.dpp_crop_warp_ex, (frames.ptr, records.ptr, B, H, W, dsz, int(flags), float(nd_value), fill, float(pad_value), out.ptr),
+                  (frames, records, out), name,
+                  dict(kernel='crop_warp', flops=(30.0 if taps == 4 else 10.0) * B * dsz * dsz, bytes=(4.0 * taps + 4.0) * B * dsz * dsz))
+
+
+def resize_crops(rt, src, B, sh, sw, dh, dw, out, bilinear=False, nd_value=0.0, name='resize_crops'):
+    """dpp_resize_crops: resizeCrop of B same-size crops, nearest neighbour or bilinearResize."""
+    return Launch(rt.lib.dpp_resize_crops, (src.ptr, B, sh, sw, dh, dw, int(bool(bilinear)), float(nd_value), out.ptr), (src, out), name,
+                  dict(kernel='resize_crops', flops=(30.0 if bilinear else 2.0) * B * dh * dw, bytes=4.0 * B * (sh * sw + dh * dw)))
+
+
+def recrop(rt, crops, B, h, w, M, Mnew, th, tw, out, background=0.0, nv_val=0.0, zrange=None, name='recrop'):
+    """dpp_recrop: recropHand of B crops (M, Mnew [B][9] float64; zrange [B][2] float32 or None for thresh_z=False)."""
+    return Launch(rt.lib.dpp_recrop, (crops.ptr, B, h, w, M.ptr, Mnew.ptr, th, tw, float(background), float(nv_val), int(zrange is not None),
+                                      _p(zrange), out.ptr),
+                  (crops, M, Mnew, zrange, out), name, dict(kernel='recrop', flops=20.0 * B * th * tw, bytes=4.0 * B * (h * w + th * tw)))
+
+
+def inverse_crop(rt, crops, B, ch, cw, bounds, H, W, out, bilinear=False, nd_value=0.0, background=0.0, zrange=None, name='inverse_crop'):
+    """dpp_inverse_crop: getInverseCrop of B crops into [B][H][W] frames (bounds [B][4] int32; zrange [B][2] float32 or None)."""
+    return Launch(rt.lib.dpp_inverse_crop, (crops.ptr, B, ch, cw, bounds.ptr, _p(zrange), H, W, int(bool(bilinear)), float(nd_value),
+                                            float(background), int(zrange is not None), out.ptr),
+                  (crops, bounds, zrange, out), name,
+                  dict(kernel='inverse_crop', flops=(30.0 if bilinear else 4.0) * B * H * W, bytes=4.0 * B * (ch * cw + H * W)))
+
+
 def crop_refine(rt, frames, records, B, H, W, com_in, cube, net_out, cam, com_out, gt3d_orig=None, J=0, pca_mean=None, pca_comp=None, E=0,
                 com3d_out=None, gt3d_crop=None, out_y=None, name='crop_refine'):
     """dpp_crop_refine: the refined crop centre from a refinement net's output (+ optionally the labels of the re-cropped frame)."""

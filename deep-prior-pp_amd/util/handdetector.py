@@ -1,13 +1,19 @@
 """
 HandDetector -- the augmentation slice of /root/reference/src/util/handdetector.py (comToBounds / comToTransform
-:204-258, moveCoM / rotateHand / scaleHand / recropHand :678-803, sampleRandomPoses :805-909).
+:204-258, moveCoM / rotateHand / scaleHand / recropHand :678-803, sampleRandomPoses :805-909) and its crop helpers
+(bilinearResize :132-202, getInverseCrop / resizeCrop / applyCrop3D :298-380).
 
 The crop warps run on the MI355X through the fused augmentation kernels (csrc/augment.hip); this class keeps the
 reference's per-crop method signatures for callers and computes only the tiny 3x3 crop geometry on the host.
 cropArea3D (handdetector.py:382-490, docom=False: the call the importers make for every frame) runs on the device too;
-`crop_frames` is its batched form fused with Dataset.imgStackDepthOnly.  CoM refinement by a ScaleNet (refineCoM,
-handdetector.py:634-676) goes through the net's computeOutput.  Whole-frame detection / tracking (detect, track) are not
-provided yet.
+`crop_frames` is its batched form fused with Dataset.imgStackDepthOnly.  recropHand, resizeCrop, bilinearResize,
+getInverseCrop and applyCrop3D are device-backed as well, with batched forms `recrop_crops`, `resize_crops` and
+`inverse_crops` (one launch per batch each).  CoM refinement by a ScaleNet (refineCoM, handdetector.py:634-676) goes
+through the net's computeOutput.  Whole-frame detection / tracking (detect, track) are not provided yet.
+
+resizeMethod is honoured where the reference reads it: RESIZE_CV2_NN (the default) is cv2's nearest-neighbour resize,
+RESIZE_BILINEAR the reference's own ND-aware bilinearResize.  RESIZE_CV2_LINEAR (cv2 INTER_LINEAR) is not built: the new
+methods raise NotImplementedError for it, and cropArea3D still crops with nearest neighbour under it (a known gap).
 """
 import numpy
 
@@ -262,21 +268,24 @@ class HandDetector(object):
         frame = numpy.asarray(self.dpt, numpy.float32)[None]
         cube = numpy.asarray(size, numpy.float32)[None]
         nd = self.getNDValue()
+        # RESIZE_BILINEAR switches every resize of the crop (the final one and the refinement net's input) to bilinearResize;
+        # RESIZE_CV2_LINEAR is not built and still gives the nearest-neighbour crop (see the module docstring)
+        rm = HandDetector.RESIZE_BILINEAR if self.resizeMethod == HandDetector.RESIZE_BILINEAR else HandDetector.RESIZE_CV2_NN
         crops, Ms, coms = crop_frames(frame, numpy.asarray(com, numpy.float32)[None], cube, self.fx, self.fy, dsize[0], normalize=False,
-                                      nd_value=nd, docom=docom, return_com=True)
+                                      nd_value=nd, docom=docom, return_com=True, resize_method=rm)
         if docom and self.refineNet is not None and self.importer is not None:
             # handdetector.py:429-440: a ScaleNet regresses the offset of the true CoM from the crop; crop again around it.  The net
             # looks at resizeCrop(cropped, dsize): the window resized to dsize AS IT IS (:430), not the aspect-preserving paste
             # (at the net's own input size: the reference passes dsize, which has to be that size there)
             dims = self.refineNet.cfgParams.inputDim
             rs = int((dims[0] if isinstance(dims[0], (list, tuple)) else dims)[2])
-            rz, _ = crop_frames(frame, coms[0][None], cube, self.fx, self.fy, rs, normalize=False, nd_value=nd, stretch=True)
+            rz, _ = crop_frames(frame, coms[0][None], cube, self.fx, self.fy, rs, normalize=False, nd_value=nd, stretch=True, resize_method=rm)
             newCom3D = self.refineCoM(rz[0], size, coms[0]) + self.importer.jointImgTo3D(coms[0])
             com2 = numpy.asarray(self.importer.joint3DToImg(newCom3D), numpy.float64)
             if numpy.allclose(com2, 0.):
                 com2[2] = crops[0][crops[0].shape[0] // 2, crops[0].shape[1] // 2]
             crops, Ms, coms = crop_frames(frame, com2.astype(numpy.float32)[None], cube, self.fx, self.fy, dsize[0], normalize=False,
-                                          nd_value=nd, return_com=True)
+                                          nd_value=nd, return_com=True, resize_method=rm)
         return crops[0], Ms[0].astype(numpy.float64), (coms[0].astype(numpy.float64) if docom else com)
 
     def refineCoM(self, cropped, size, com):
@@ -343,6 +352,96 @@ class HandDetector(object):
             com[1] += max(ystart, 0)
         return com
 
+    # ---- crop helpers on the device (handdetector.py:132-202, 298-380, 782-803) ---------------------------------------------
+    def _resize_mode(self, what):
+        if self.resizeMethod == self.RESIZE_CV2_NN:
+            return self.RESIZE_CV2_NN
+        if self.resizeMethod == self.RESIZE_BILINEAR:
+            return self.RESIZE_BILINEAR
+        if self.resizeMethod == self.RESIZE_CV2_LINEAR:
+            raise NotImplementedError("%s: RESIZE_CV2_LINEAR (cv2 INTER_LINEAR: fixed-point coordinates, float coefficient tables, 2x downscale "
+                                      "as INTER_AREA) is not built -- it cannot be pinned without OpenCV; use RESIZE_CV2_NN or RESIZE_BILINEAR" % what)
+        raise NotImplementedError("Unknown resize method!")
+
+    @staticmethod
+    def bilinearResize(src, dsize, ndValue):
+        """Bilinear resize that spares out undefined depth (handdetector.py:132-202), on the device: src (h, w) -> float32
+        (dsize[1], dsize[0]).  A tap equal to ndValue drops out and the remaining weights are renormalised; more than two such
+        taps give ndValue.  The arithmetic is the reference's on NumPy 1 (float64 weights and sum, one rounding to float32).
+        A source narrower or shorter than 2 pixels raises UserWarning("Shape mismatch") like the reference."""
+        src = numpy.asarray(src)
+        if src.ndim != 2:
+            raise NotImplementedError("2-D depth maps only")
+        return resize_crops(src[None], dsize, HandDetector.RESIZE_BILINEAR, ndValue)[0]
+
+    def resizeCrop(self, crop, sz):
+        """Resize a crop to sz = (w, h) with self.resizeMethod (handdetector.py:336-351): cv2 INTER_NEAREST or bilinearResize with
+        getNDValue().  Computed in float32 (depth in mm); returned in crop's dtype under nearest neighbour, float32 under bilinear."""
+        mode = self._resize_mode('resizeCrop')
+        crop = numpy.asarray(crop)
+        if crop.ndim != 2:
+            raise NotImplementedError("2-D depth maps only")
+        nd = self.getNDValue() if mode == self.RESIZE_BILINEAR else 0.
+        rz = resize_crops(crop[None], sz, mode, nd)[0]
+        return rz if mode == self.RESIZE_BILINEAR else rz.astype(crop.dtype, copy=False)
+
+    def recropHand(self, crop, M, Mnew, target_size, background_value=0., nv_val=0., thresh_z=True, com=None, size=(250, 250, 250)):
+        """Warp a crop in mm by dot(M, Mnew) to target_size = (w, h) (handdetector.py:782-803): cv2.warpPerspective INTER_NEAREST,
+        border background_value, pixels close to nv_val -> background_value, then (thresh_z) the cube's z range around com.
+        RESIZE_BILINEAR raises NotImplementedError like the reference."""
+        if self.resizeMethod == self.RESIZE_BILINEAR:
+            raise NotImplementedError
+        self._resize_mode('recropHand')
+        if thresh_z is True:
+            assert com is not None
+            _, _, _, _, zstart, zend = self.comToBounds(com, size)
+            zr = numpy.array([[zstart, zend]], numpy.float64)
+        else:
+            zr = None
+        crop = numpy.asarray(crop)
+        out = _recrop(crop[None], numpy.asarray(M, numpy.float64)[None], numpy.asarray(Mnew, numpy.float64)[None], target_size,
+                      background_value, nv_val, zr)
+        return out[0]
+
+    def getInverseCrop(self, crop, sz, xstart, xend, ystart, yend, zstart, zend, thresh_z=True, background=0):
+        """Paste a crop back into a frame of shape sz (handdetector.py:298-334): the crop resized (self.resizeMethod) to the window
+        (xend - xstart, yend - ystart) on a canvas of `background`, then (thresh_z) the z-threshold over the whole frame.  A window
+        entirely outside the frame or of zero size gives the bare canvas.  float32."""
+        mode = self._resize_mode('getInverseCrop')
+        crop = numpy.asarray(crop)
+        if crop.ndim != 2 or len(sz) != 2:
+            raise NotImplementedError("2-D depth maps only")
+        nd = self.getNDValue() if mode == self.RESIZE_BILINEAR else 0.
+        bounds = numpy.array([[xstart, xend, ystart, yend, zstart, zend]], numpy.float64)
+        return inverse_crops(crop[None], sz, bounds, thresh_z=thresh_z, background=background, method=mode, nd_value=nd)[0]
+
+    def applyCrop3D(self, dpt, com, size, dsize, thresh_z=True, background=None):
+        """cropArea3D's crop applied to an arbitrary image `dpt` (handdetector.py:353-380): the window of the metric cube around com
+        (no detector range test), z-thresholded when thresh_z, resized with self.resizeMethod and pasted centred into dsize.
+        background is both getCrop's pad value outside the frame and the fill outside the paste; background=None fills with
+        getNDValue() and pads with what numpy.pad(..., constant_values=None) gives on a float32 array, NaN on current NumPy.
+        float32 (dsize square)."""
+        mode = self._resize_mode('applyCrop3D')
+        if len(size) != 3 or len(dsize) != 2:
+            raise ValueError("Size must be 3D and dsize 2D bounding box")
+        if dsize[0] != dsize[1]:
+            raise NotImplementedError("square destination sizes only")
+        if numpy.isclose(com[2], 0.):
+            raise NotImplementedError("applyCrop3D around an ill-defined CoM (com[2] == 0) is not built")
+        dpt = numpy.asarray(dpt, numpy.float32)
+        if dpt.ndim != 2:
+            raise NotImplementedError("2-D depth maps only")
+        if background is None:
+            pad = float(numpy.pad(numpy.zeros((1, 1), numpy.float32), ((1, 0), (0, 0)), mode='constant', constant_values=None)[0, 0])
+            fill = self.getNDValue()
+        else:
+            pad = fill = background
+        nd = self.getNDValue()
+        flags = _CROP_NO_RANGE | (0 if thresh_z is True else _CROP_NO_THRESH)
+        crops, _ = crop_frames(dpt[None], numpy.asarray(com, numpy.float32)[None], numpy.asarray(size, numpy.float32)[None], self.fx, self.fy,
+                               dsize[0], normalize=False, nd_value=nd, resize_method=mode, _flags=flags, _fill=fill, _pad=pad)
+        return crops[0]
+
     def detect(self, *args, **kwargs):
         raise NotImplementedError("hand detection / tracking (cv2.findContours slab analysis, handdetector.py:504-631) belongs to the realtime demo "
                                   "(util/realtimehandposepipeline.py is its only caller), which is out of scope (SURVEY.md section 2)")
@@ -350,15 +449,48 @@ class HandDetector(object):
     track = detect
 
 
+_CROP_NORMALIZE, _CROP_BILINEAR, _CROP_NO_RANGE, _CROP_NO_THRESH = 1, 2, 4, 8     # hipdp.ops.CROP_* (dpp_crop_warp_ex flags)
+
+
+def _bounds(com, size, fx, fy):
+    """comToBounds (handdetector.py:204-226) without the ill-defined branch, in the device's arithmetic (com as float32)."""
+    c0, c1, c2 = float(numpy.float32(com[0])), float(numpy.float32(com[1])), float(numpy.float32(com[2]))
+    s0, s1 = float(numpy.float32(size[0])), float(numpy.float32(size[1]))
+    return (int(numpy.floor((c0 * c2 / fx - s0 / 2.) / c2 * fx + 0.5)), int(numpy.floor((c0 * c2 / fx + s0 / 2.) / c2 * fx + 0.5)),
+            int(numpy.floor((c1 * c2 / fy - s1 / 2.) / c2 * fy + 0.5)), int(numpy.floor((c1 * c2 / fy + s1 / 2.) / c2 * fy + 0.5)))
+
+
+def _check_bilinear(sw, sh, dw, dh):
+    """bilinearResize raises UserWarning("Shape mismatch") when a tap leaves the source (handdetector.py:160-162); its last row
+    and column reach furthest."""
+    x = int((dw - 1) * (float(sw - 1) / dw)) if dw > 0 else 0
+    y = int((dh - 1) * (float(sh - 1) / dh)) if dh > 0 else 0
+    if sw < 2 or sh < 2 or x + 1 >= sw or y + 1 >= sh:
+        raise UserWarning("Shape mismatch")
+
+
+def _method(method):
+    if method == HandDetector.RESIZE_CV2_NN:
+        return False
+    if method == HandDetector.RESIZE_BILINEAR:
+        return True
+    if method == HandDetector.RESIZE_CV2_LINEAR:
+        raise NotImplementedError("RESIZE_CV2_LINEAR (cv2 INTER_LINEAR) is not built: it cannot be pinned without OpenCV")
+    raise NotImplementedError("Unknown resize method!")
+
+
 def crop_frames(frames, coms, cubes, fx, fy, dsize=128, normalize=True, nd_value=0., runtime=None, docom=False, return_com=False,
-                stretch=False):
+                stretch=False, resize_method=HandDetector.RESIZE_CV2_NN, _flags=0, _fill=None, _pad=0.):
     """Batched cropArea3D (+ Dataset.imgStackDepthOnly when normalize): frames (B, H, W) raw depth in mm, coms (B, 3) crop
     centres in image coordinates, cubes (B, 3) in mm -> (crops (B, dsize, dsize) float32, M (B, 3, 3) float32[, coms]).
     Two kernel launches for the whole batch (csrc/augment.hip: crop_prepare / crop_warp); docom=True re-centres every crop
     on the centre of mass of its first window (two more launches), as handdetector.py:413-427 does; stretch=True resizes the
-    window to dsize x dsize as it is (resizeCrop(cropped, dsize), the refinement net's input, :430)."""
+    window to dsize x dsize as it is (resizeCrop(cropped, dsize), the refinement net's input, :430).  resize_method
+    RESIZE_BILINEAR resizes the window with bilinearResize (ND value nd_value) instead of nearest neighbour; a window
+    narrower or shorter than 2 pixels then raises UserWarning("Shape mismatch")."""
     from hipdp import ops
     from hipdp.runtime import default_runtime
+    bilinear = _method(resize_method)
     rt = runtime or default_runtime()
     frames = numpy.ascontiguousarray(frames, numpy.float32)
     B, H, W = frames.shape
@@ -373,8 +505,126 @@ def crop_frames(frames, coms, cubes, fx, fy, dsize=128, normalize=True, nd_value
         ops.crop_com(rt, fr, rec, B, H, W, co2)(rt.stream)
         ops.crop_prepare(rt, fr, B, H, W, co2, cu, fx, fy, dsize, rec, M, stretch=stretch)(rt.stream)
         co = co2
-    ops.crop_warp(rt, fr, rec, B, H, W, dsize, out, normalize=normalize, nd_value=nd_value)(rt.stream)
+    if bilinear:
+        cube_h = numpy.ascontiguousarray(cubes, numpy.float32).reshape(B, 3)
+        com_h = co.get() if docom else numpy.ascontiguousarray(coms, numpy.float32).reshape(B, 3)
+        for i in range(B):
+            xs, xe, ys, ye = _bounds(com_h[i], cube_h[i], abs(fx), abs(fy))
+            wb, hb = xe - xs, ye - ys
+            if stretch:
+                dw, dh = dsize, dsize
+            elif wb > hb:
+                dw, dh = dsize, (hb * dsize) // wb
+            else:
+                dw, dh = (wb * dsize) // hb if hb else 0, dsize
+            _check_bilinear(wb, hb, dw, dh)
+    if bilinear or _flags or _fill is not None or _pad != 0.:
+        flags = _flags | (_CROP_NORMALIZE if normalize else 0) | (_CROP_BILINEAR if bilinear else 0)
+        ops.crop_warp_ex(rt, fr, rec, B, H, W, dsize, out, flags=flags, nd_value=nd_value, fill_value=_fill, pad_value=_pad)(rt.stream)
+    else:
+        ops.crop_warp(rt, fr, rec, B, H, W, dsize, out, normalize=normalize, nd_value=nd_value)(rt.stream)
     rt.synchronize()
     if return_com:
         return out.get(), M.get().reshape(B, 3, 3), co.get()
     return out.get(), M.get().reshape(B, 3, 3)
+
+
+def resize_crops(crops, sz, method=HandDetector.RESIZE_CV2_NN, nd_value=0., runtime=None):
+    """Batched resizeCrop: crops (B, h, w) -> float32 (B, sz[1], sz[0]) (sz in cv2's (w, h) order), cv2 INTER_NEAREST
+    (RESIZE_CV2_NN) or bilinearResize with nd_value (RESIZE_BILINEAR).  One launch."""
+    from hipdp import ops
+    from hipdp.runtime import default_runtime
+    bilinear = _method(method)
+    crops = numpy.ascontiguousarray(crops, numpy.float32)
+    if crops.ndim != 3:
+        raise ValueError("crops must be (B, h, w)")
+    B, sh, sw = crops.shape
+    dw, dh = int(sz[0]), int(sz[1])
+    if dw < 1 or dh < 1:
+        raise ValueError("empty destination size %r" % (tuple(sz),))
+    if bilinear:
+        _check_bilinear(sw, sh, dw, dh)
+    rt = runtime or default_runtime()
+    src = rt.upload(crops)
+    out = rt.alloc((B, dh, dw), zero=False)
+    ops.resize_crops(rt, src, B, sh, sw, dh, dw, out, bilinear=bilinear, nd_value=nd_value)(rt.stream)
+    rt.synchronize()
+    return out.get()
+
+
+def _recrop(crops, M, Mnew, target_size, background_value, nv_val, zrange, runtime=None):
+    from hipdp import ops
+    from hipdp.runtime import default_runtime
+    crops = numpy.ascontiguousarray(crops, numpy.float32)
+    if crops.ndim != 3:
+        raise ValueError("crops must be (B, h, w)")
+    B, h, w = crops.shape
+    tw, th = int(target_size[0]), int(target_size[1])
+    if tw < 1 or th < 1:
+        raise ValueError("empty target size %r" % (tuple(target_size),))
+    rt = runtime or default_runtime()
+    src = rt.upload(crops)
+    m = rt.upload(numpy.ascontiguousarray(M, numpy.float64).reshape(B, 9))
+    mn = rt.upload(numpy.ascontiguousarray(Mnew, numpy.float64).reshape(B, 9))
+    zr = None if zrange is None else rt.upload(numpy.ascontiguousarray(zrange, numpy.float64).reshape(B, 2).astype(numpy.float32))
+    out = rt.alloc((B, th, tw), zero=False)
+    ops.recrop(rt, src, B, h, w, m, mn, th, tw, out, background=background_value, nv_val=nv_val, zrange=zr)(rt.stream)
+    rt.synchronize()
+    return out.get()
+
+
+def recrop_crops(crops, M, Mnew, target_size, coms, sizes, fx, fy, background_value=0., nv_val=0., thresh_z=True, min_depth=None,
+                 max_depth=None, runtime=None):
+    """Batched recropHand (RESIZE_CV2_NN): crops (B, h, w) in mm, M / Mnew (B, 3, 3), target_size (w, h), coms (B, 3) and sizes
+    (B, 3) for the z range (comToBounds) -> float32 (B, h', w').  A crop whose com[2] is close to 0 takes comToBounds' ill-defined
+    branch, whose z range is the detector's [min_depth, max_depth] (then required).  One launch."""
+    crops = numpy.asarray(crops)
+    B = crops.shape[0]
+    zr = None
+    if thresh_z is True:
+        coms = numpy.asarray(coms).reshape(B, 3)
+        sizes = numpy.asarray(sizes).reshape(B, 3)
+        zr = numpy.empty((B, 2), numpy.float64)
+        for i in range(B):
+            if numpy.isclose(coms[i][2], 0.):
+                if min_depth is None or max_depth is None:
+                    raise ValueError("crop %d: ill-defined CoM (z == 0) needs min_depth / max_depth" % i)
+                zr[i] = (min_depth, max_depth)
+            else:
+                zr[i] = (float(coms[i][2]) - sizes[i][2] / 2., float(coms[i][2]) + sizes[i][2] / 2.)
+    return _recrop(crops, numpy.asarray(M, numpy.float64).reshape(B, 3, 3), numpy.asarray(Mnew, numpy.float64).reshape(B, 3, 3), target_size,
+                   background_value, nv_val, zr, runtime)
+
+
+def inverse_crops(crops, frame_shape, bounds, thresh_z=True, background=0., method=HandDetector.RESIZE_CV2_NN, nd_value=0., runtime=None):
+    """Batched getInverseCrop: crops (B, h, w) pasted into frames of frame_shape (H, W) at bounds (B, 6) = (xstart, xend, ystart,
+    yend, zstart, zend) per crop (comToBounds' order) -> float32 (B, H, W).  method: RESIZE_CV2_NN or RESIZE_BILINEAR (ND value
+    nd_value).  One launch."""
+    from hipdp import ops
+    from hipdp.runtime import default_runtime
+    bilinear = _method(method)
+    crops = numpy.ascontiguousarray(crops, numpy.float32)
+    if crops.ndim != 3:
+        raise ValueError("crops must be (B, h, w)")
+    B, ch, cw = crops.shape
+    H, W = int(frame_shape[0]), int(frame_shape[1])
+    bounds = numpy.asarray(bounds, numpy.float64).reshape(B, 6)
+    box = numpy.ascontiguousarray(bounds[:, :4]).astype(numpy.int64)
+    if not numpy.array_equal(box, bounds[:, :4]) or numpy.abs(box).max(initial=0) >= 2 ** 30:
+        raise ValueError("window bounds must be integers")
+    for xs, xe, ys, ye in box:
+        early = (xe < 0 and xs < 0) or (ye < 0 and ys < 0) or (xe > W and xs > W) or (ye > H and ys > H) or xe == xs or ye == ys
+        if early:
+            continue
+        if xe < xs or ye < ys:
+            raise ValueError("window of negative size: (%d, %d, %d, %d)" % (xs, xe, ys, ye))
+        if bilinear:
+            _check_bilinear(cw, ch, xe - xs, ye - ys)
+    rt = runtime or default_runtime()
+    src = rt.upload(crops)
+    bd = rt.upload(box.astype(numpy.int32))
+    zr = rt.upload(numpy.ascontiguousarray(bounds[:, 4:]).astype(numpy.float32)) if thresh_z is True else None
+    out = rt.alloc((B, H, W), zero=False)
+    ops.inverse_crop(rt, src, B, ch, cw, bd, H, W, out, bilinear=bilinear, nd_value=nd_value, background=background, zrange=zr)(rt.stream)
+    rt.synchronize()
+    return out.get()

@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 11
+#define DPP_ABI_VERSION 12
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -443,6 +443,37 @@ int dpp_crop_refine(const float* frames, const void* records, int B, int H, int 
                     const float* net_out, double fx, double fy, double ux, double uy, int flip_y, const float* gt3d_orig, int J,
                     const float* pca_mean, const float* pca_comp, int E, float* com_out, float* com3d_out, float* gt3d_crop,
                     float* out_y, dpp_stream_t stream);
+
+/* ---- HandDetector crop helpers (ABI v12) ----------------------------------------------------------------------------------------
+ * bilinear: HandDetector.bilinearResize (/root/reference/src/util/handdetector.py:132-202) -- the reference's arithmetic on NumPy 1:
+ * x_ratio = (sw - 1) / dw, int() truncation, the four tap weights in f64, more than two taps equal to nd_value -> nd_value, a tap
+ * equal to nd_value drops out with the reference's re-balancing, weights renormalised by 1 / sum, all-zero weights -> nd_value, the
+ * weighted sum in f64 rounded once to f32.  A source narrower or shorter than 2 pixels is DPP_E_BADARG (the reference raises
+ * "Shape mismatch").  Nearest neighbour is cv2.resize INTER_NEAREST of OpenCV 2.4 (resizeNN), as in dpp_crop_warp.
+ *
+ * crop_warp_ex: dpp_crop_warp with the options of cropArea3D / applyCrop3D (handdetector.py:353-380, 382-490) under every
+ * resizeMethod: flags bit 0 normalise (as dpp_crop_warp's `normalize`), bit 1 bilinear resize of the window (ND value nd_value),
+ * bit 2 no detector range test (applyCrop3D crops an arbitrary image), bit 3 no z-threshold (thresh_z = False).  fill_value fills the
+ * output outside the paste, pad_value the window outside the frame (getCrop's `background`).  flags = 0, fill_value = nd_value and
+ * pad_value = 0 give dpp_crop_warp's output.  Records from dpp_crop_prepare (stretch included). */
+int dpp_crop_warp_ex(const float* frames, const void* records, int B, int H, int W, int dsz, int flags, float nd_value, float fill_value,
+                     float pad_value, float* out, dpp_stream_t stream);
+/* resizeCrop (handdetector.py:336-351) of B same-size crops src [B][sh][sw] -> out [B][dh][dw]: nearest neighbour (bilinear == 0)
+ * or bilinearResize with nd_value. */
+int dpp_resize_crops(const float* src, int B, int sh, int sw, int dh, int dw, int bilinear, float nd_value, float* out, dpp_stream_t stream);
+/* recropHand (handdetector.py:782-803), batched, on crops in mm [B][h][w] -> out [B][th][tw]: cv2.warpPerspective with the matrix
+ * dot(M[b], Mnew[b]) (M, Mnew: [B][9] f64, row-major; product and cofactor inverse in the order of the augmentation's warp),
+ * INTER_NEAREST, BORDER_CONSTANT background; then isclose(warped, nv_val) -> background and, when thresh_z, the z-threshold against
+ * zrange [B][2] = (zstart, zend) in f32 (the host takes them from comToBounds; may be NULL when !thresh_z). */
+int dpp_recrop(const float* crops, int B, int h, int w, const double* M, const double* Mnew, int th, int tw, float background,
+               double nv_val, int thresh_z, const float* zrange, float* out, dpp_stream_t stream);
+/* getInverseCrop (handdetector.py:298-334), batched: crop b [ch][cw] resized (nearest neighbour, or bilinearResize with nd_value)
+ * to its window bounds [B][4] = (xstart, xend, ystart, yend) and pasted into out [B][H][W], a canvas of `background`; then, when
+ * thresh_z, the z-threshold against zrange [B][2] over the whole frame.  The reference's early returns (window entirely left of /
+ * above the frame, entirely right of / below it, zero width or height) give the bare canvas without the threshold.  A window of
+ * negative width or height pastes nothing (the reference fails in cv2.resize; the host refuses it). */
+int dpp_inverse_crop(const float* crops, int B, int ch, int cw, const int* bounds, const float* zrange, int H, int W, int bilinear,
+                     float nd_value, float background, int thresh_z, float* out, dpp_stream_t stream);
 
 /* ---- PCA prior set-up and evaluation on the device --------------------------------------------
  * pose_sample: HandDetector.sampleRandomPoses (/root/reference/src/util/handdetector.py:805-909) for n samples: sample i augments
