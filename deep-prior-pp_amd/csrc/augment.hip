@@ -831,6 +831,9 @@ struct CropRec {
     float far_v, norm_off, norm_div;
 };
 
+__device__ __forceinline__ void crop_geometry(float mn, float mx, const float c[3], const float* __restrict__ cube_b, double fx, double fy,
+                                              int dsz, int stretch, CropRec& r, float* __restrict__ M);
+
 __global__ __launch_bounds__(DPP_THREADS) void crop_prepare_kernel(const float* __restrict__ frames, int H, int W,
                                                                    const float* __restrict__ com, const float* __restrict__ cube,
                                                                    double fx, double fy, int dsz, int stretch,
@@ -862,10 +865,20 @@ __global__ __launch_bounds__(DPP_THREADS) void crop_prepare_kernel(const float* 
     if (tid != 0) return;
     for (int w = 1; w < DPP_THREADS / DPP_WAVE; ++w) { mn = fminf(mn, s_mn[w]); mx = fmaxf(mx, s_mx[w]); }
     CropRec r;
+    const float c[3] = {com[b * 3], com[b * 3 + 1], com[b * 3 + 2]};
+    crop_geometry(mn, mx, c, cube + b * 3, fx, fy, dsz, stretch, r, M_out ? M_out + (size_t)b * 9 : nullptr);
+    rec[b] = r;
+}
+
+// The crop geometry of one frame from its depth range (mn, mx) and centre c: the detector's valid range, the window of the metric
+// cube, the resized size / paste offset and the crop transform M (9 floats, may be null).  Shared by crop_prepare_kernel (range from
+// its own pass over the frame) and the realtime kernels below (range from frame_range_kernel's partials): one body, so their records
+// are byte-identical.  The clamp of the range is idempotent: a record's own (min_depth, max_depth) may be passed back in.
+__device__ __forceinline__ void crop_geometry(float mn, float mx, const float c[3], const float* __restrict__ cube_b, double fx, double fy,
+                                              int dsz, int stretch, CropRec& r, float* __restrict__ M) {
     r.max_depth = fminf(1500.0f, mx);                          // handdetector.py:60-61
     r.min_depth = fmaxf(10.0f, mn);
-    const float c[3] = {com[b * 3], com[b * 3 + 1], com[b * 3 + 2]};
-    const double size[3] = {(double)cube[b * 3], (double)cube[b * 3 + 1], (double)cube[b * 3 + 2]};
+    const double size[3] = {(double)cube_b[0], (double)cube_b[1], (double)cube_b[2]};
     int bd[4];
     com_to_bounds(c, size, fx, fy, bd);
     r.xstart = bd[0]; r.ystart = bd[2];
@@ -886,9 +899,7 @@ __global__ __launch_bounds__(DPP_THREADS) void crop_prepare_kernel(const float* 
     r.far_v = c[2] + (float)(size[2] / 2.);
     r.norm_off = c[2];
     r.norm_div = (float)(size[2] / 2.);
-    rec[b] = r;
-    if (M_out) {
-        float* M = M_out + (size_t)b * 9;
+    if (M) {
         M[0] = (float)sc; M[1] = 0.f; M[2] = (float)(sc * (double)(-bd[0]) + (double)r.xs);
         M[3] = 0.f; M[4] = (float)sc; M[5] = (float)(sc * (double)(-bd[2]) + (double)r.ys);
         M[6] = 0.f; M[7] = 0.f; M[8] = 1.f;
@@ -1048,7 +1059,7 @@ __global__ __launch_bounds__(DPP_THREADS) void crop_refine_kernel(const float* _
 // ---- HandDetector crop helpers (ABI v12): bilinearResize, resizeCrop, recropHand, getInverseCrop, applyCrop3D ----------
 // /root/reference/src/util/handdetector.py:132-202 (bilinearResize), :298-351 (getInverseCrop, resizeCrop), :353-380 (applyCrop3D),
 // :782-803 (recropHand).  One launch per batch, one thread per output pixel.
-constexpr int CW_NORMALIZE = 1, CW_BILINEAR = 2, CW_NO_RANGE = 4, CW_NO_THRESH = 8;     // dpp_crop_warp_ex flags
+constexpr int CW_NORMALIZE = 1, CW_BILINEAR = 2, CW_NO_RANGE = 4, CW_NO_THRESH = 8, CW_FLIP_X = 16;     // dpp_crop_warp_ex flags
 
 // crop_window_value with applyCrop3D's options: `pad` outside the frame (getCrop's `background`), the detector's range test and
 // the z-threshold each optional
@@ -1122,7 +1133,8 @@ __global__ __launch_bounds__(DPP_THREADS) void crop_warp_ex_kernel(const float* 
     if (p >= dsz * dsz) return;
     const CropRec r = rec[b];
     const float* f = frames + (size_t)b * H * W;
-    const int y = p / dsz, x = p - y * dsz;
+    const int y = p / dsz, xo = p - y * dsz;
+    const int x = (flags & CW_FLIP_X) ? dsz - 1 - xo : xo;      // crop[:, ::-1]: output column xo holds column dsz - 1 - xo
     float v = fill_value;
     const int rx = x - r.xs, ry = y - r.ys;
     if (rx >= 0 && rx < r.szw && ry >= 0 && ry < r.szh) {
@@ -1242,6 +1254,235 @@ __global__ __launch_bounds__(DPP_THREADS) void inverse_crop_kernel(const float* 
         }
     }
     out[(size_t)b * H * W + p] = v;
+}
+
+// ---- realtime tracking (ABI v13): HandDetector.track + RealtimeHandposePipeline.detect / estimatePose as device steps -----------
+// /root/reference/src/util/handdetector.py:504-567, /root/reference/src/util/realtimehandposepipeline.py:296-370.  One frame is one
+// chain of dependent launches, so what counts is their number and that none of them walks the frame with a single workgroup.
+constexpr int FR_BANDS = 64;            // workgroups per frame of the depth-range pass (= one wave of partials to reduce)
+
+// min / max of frame b over FR_BANDS workgroups -> partial[b][band][2].  Interleaved 16-byte loads, four in flight per thread; a
+// lane past the end re-reads its first element (harmless for min / max).  Every band writes its partial, also an empty one.
+__global__ __launch_bounds__(DPP_THREADS) void frame_range_kernel(const float* __restrict__ frames, int H, int W, float* __restrict__ partial) {
+    __shared__ float s_mn[DPP_THREADS / DPP_WAVE], s_mx[DPP_THREADS / DPP_WAVE];
+    const int b = blockIdx.y, band = blockIdx.x, tid = threadIdx.x;
+    const float* f = frames + (size_t)b * H * W;
+    const int npx = H * W;
+    const int t = band * DPP_THREADS + tid, nt = FR_BANDS * DPP_THREADS;
+    float mn = 3.4e38f, mx = -3.4e38f;
+    int i0 = 0;
+    if ((npx & 3) == 0 && (reinterpret_cast<uintptr_t>(f) & 15) == 0) {
+        const float4* f4 = reinterpret_cast<const float4*>(f);
+        const int n4 = npx >> 2;
+        for (int i = t; i < n4; i += 4 * nt) {
+            float4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = i + u * nt;
+                v[u] = f4[j < n4 ? j : i];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                mn = fminf(mn, fminf(fminf(v[u].x, v[u].y), fminf(v[u].z, v[u].w)));
+                mx = fmaxf(mx, fmaxf(fmaxf(v[u].x, v[u].y), fmaxf(v[u].z, v[u].w)));
+            }
+        }
+        i0 = npx;
+    }
+    for (int i = i0 + t; i < npx; i += nt) { const float v = f[i]; mn = fminf(mn, v); mx = fmaxf(mx, v); }
+    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+    if ((tid & 63) == 0) { s_mn[tid >> 6] = mn; s_mx[tid >> 6] = mx; }
+    __syncthreads();
+    if (tid != 0) return;
+    for (int w = 1; w < DPP_THREADS / DPP_WAVE; ++w) { mn = fminf(mn, s_mn[w]); mx = fmaxf(mx, s_mx[w]); }
+    partial[((size_t)b * FR_BANDS + band) * 2] = mn;
+    partial[((size_t)b * FR_BANDS + band) * 2 + 1] = mx;
+}
+
+// (min, max) of frame b from its FR_BANDS partials: one wave, lane = band; every lane returns the result
+__device__ __forceinline__ void frame_range_reduce(const float* __restrict__ partial, int b, int lane, float& mn, float& mx) {
+    mn = partial[((size_t)b * FR_BANDS + lane) * 2];
+    mx = partial[((size_t)b * FR_BANDS + lane) * 2 + 1];
+    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+}
+
+// a centre that cannot be cropped around: its depth is numpy.isclose to 0 (comToBounds' "CoM ill-defined" test) or it is not finite
+__device__ __forceinline__ bool com_ill_defined(const float c[3]) {
+    const bool finite = fabs((double)c[0]) <= 3.4e38 && fabs((double)c[1]) <= 3.4e38 && fabs((double)c[2]) <= 3.4e38;   // false for NaN
+    return !finite || fabs((double)c[2]) <= 1e-8;
+}
+
+// the record of an EMPTY window: crop_warp writes its fill value everywhere (0 when normalised), nothing divides by zero; M = identity
+__device__ __forceinline__ void crop_empty_record(float min_depth, float max_depth, CropRec& r, float* __restrict__ M) {
+    r.xstart = 0; r.ystart = 0; r.cw = 0; r.ch = 0; r.szw = 0; r.szh = 0; r.xs = 0; r.ys = 0;
+    r.ifx = 1.; r.ify = 1.;
+    r.min_depth = min_depth; r.max_depth = max_depth; r.zstart = 0.f; r.zend = 0.f;
+    r.far_v = 0.f; r.norm_off = 0.f; r.norm_div = 1.f;
+    if (M) { for (int i = 0; i < 9; ++i) M[i] = (i % 4 == 0) ? 1.f : 0.f; }
+}
+
+// crop_prepare_kernel without its pass over the frame: one wave per frame reduces the partials, lane 0 writes the record.  An
+// ill-defined centre (a lost track whose next frame is already queued) gets the empty window instead of a division by zero.
+__global__ __launch_bounds__(DPP_WAVE) void crop_prepare_ranged_kernel(const float* __restrict__ partial, const float* __restrict__ com,
+                                                                       const float* __restrict__ cube, double fx, double fy, int dsz, int stretch,
+                                                                       CropRec* __restrict__ rec, float* __restrict__ M_out) {
+    const int b = blockIdx.x;
+    float mn, mx;
+    frame_range_reduce(partial, b, threadIdx.x, mn, mx);
+    if (threadIdx.x != 0) return;
+    CropRec r;
+    const float c[3] = {com[b * 3], com[b * 3 + 1], com[b * 3 + 2]};
+    float* M = M_out ? M_out + (size_t)b * 9 : nullptr;
+    if (com_ill_defined(c)) crop_empty_record(fmaxf(10.0f, mn), fminf(1500.0f, mx), r, M);
+    else crop_geometry(mn, mx, c, cube + b * 3, fx, fy, dsz, stretch, r, M);
+    rec[b] = r;
+}
+
+// HandDetector.track's centre update (crop_refine_kernel's: the same float32 roundings and centre-pixel fallback) fused with the
+// prepare of the final crop around the new centre (record, M, com3D) and a status word: 1 = lost, when the new centre's depth is
+// numpy.isclose to 0 (comToBounds' "CoM ill-defined" branch, handdetector.py:204-213, which no device kernel implements; an all-zero
+// centre is a case of it) or not finite, or when com_in already was.  A lost frame gets an EMPTY window (crop_warp then writes zeros, nothing divides by zero or
+// leaves the frame), M = identity and com3D = 0.  One lane per frame does all of it, reads before writes: com_out may be com_in (the
+// tracker's state buffer, updated in place -- the next reader is the next frame's first prepare, a later launch) and rec_out may be rec_in.
+__global__ __launch_bounds__(DPP_WAVE) void track_refine_kernel(const float* __restrict__ frames, int H, int W, const CropRec* rec_in,
+                                                                const float* com_in, const float* __restrict__ cube,
+                                                                const float* __restrict__ net_out, AugCam cam, double fx, double fy, int dsz,
+                                                                float* com_out, float* __restrict__ com3d_out, CropRec* rec_out,
+                                                                float* __restrict__ M_out, int* __restrict__ status) {
+    const int b = blockIdx.x;
+    if (threadIdx.x != 0) return;
+    const CropRec r0 = rec_in[b];
+    const float half = (float)((double)cube[b * 3 + 2] / 2.);              // size[2] / 2. as a floatX constant
+    float c3[3], n3[3], c2[3];
+    to3d(cam, com_in[b * 3], com_in[b * 3 + 1], com_in[b * 3 + 2], c3);
+    for (int d = 0; d < 3; ++d) n3[d] = net_out[b * 3 + d] * half + c3[d];   // float32 arrays: two roundings
+    toimg(cam, n3[0], n3[1], n3[2], true, c2);
+    if (fabs((double)c2[0]) <= 1e-8 && fabs((double)c2[1]) <= 1e-8 && fabs((double)c2[2]) <= 1e-8)
+        c2[2] = crop_window_value(frames + (size_t)b * H * W, H, W, r0, r0.cw / 2, r0.ch / 2);
+    const float c1[3] = {com_in[b * 3], com_in[b * 3 + 1], com_in[b * 3 + 2]};
+    const bool lost = com_ill_defined(c2) || com_ill_defined(c1);            // (a frame queued behind a lost one stays lost)
+    for (int d = 0; d < 3; ++d) com_out[b * 3 + d] = c2[d];
+    status[b] = lost ? 1 : 0;
+    float* M = M_out ? M_out + (size_t)b * 9 : nullptr;
+    CropRec r;
+    float q3[3] = {0.f, 0.f, 0.f};
+    if (lost) {
+        crop_empty_record(r0.min_depth, r0.max_depth, r, M);
+    } else {
+        crop_geometry(r0.min_depth, r0.max_depth, c2, cube + b * 3, fx, fy, dsz, 0, r, M);
+        to3d(cam, c2[0], c2[1], c2[2], q3);
+    }
+    rec_out[b] = r;
+    for (int d = 0; d < 3; ++d) com3d_out[b * 3 + d] = q3[d];
+}
+
+// RealtimeHandposePipeline.estimatePose's sign rules and its caller's pose * cube_z / 2. + com3D (realtimehandposepipeline.py:356-369,
+// :198), float32 operation by operation, then importer.joints3DToImg of the result (:407).  flags: bit 0 HAND_RIGHT (column 0
+// negated), bit 1 config['invX'] (column 1, as the reference has it), bit 2 config['invY'] (column 0).  One thread per joint.
+__global__ __launch_bounds__(DPP_THREADS) void pose_finish_kernel(const float* __restrict__ net_out, int B, int J, const float* __restrict__ cube,
+                                                                  const float* __restrict__ com3d, AugCam cam, int flags,
+                                                                  float* __restrict__ pose3d, float* __restrict__ pose_img) {
+    const int i = blockIdx.x * DPP_THREADS + threadIdx.x;
+    if (i >= B * J) return;
+    const int b = i / J;
+    float p[3] = {net_out[(size_t)i * 3], net_out[(size_t)i * 3 + 1], net_out[(size_t)i * 3 + 2]};
+    if (flags & 2) p[1] = -p[1];
+    if (flags & 4) p[0] = -p[0];
+    if (flags & 1) p[0] = -p[0];
+    const float cz = cube[b * 3 + 2];
+    float q[3];
+    for (int d = 0; d < 3; ++d) {
+        float v = p[d] * cz;               // three float32 roundings: * cube_z, / 2., + com3D
+        v = v / 2.0f;
+        q[d] = v + com3d[b * 3 + d];
+        pose3d[(size_t)i * 3 + d] = q[d];
+    }
+    float u[3];
+    toimg(cam, q[0], q[1], q[2], true, u);
+    for (int d = 0; d < 3; ++d) pose_img[(size_t)i * 3 + d] = u[d];
+}
+
+__device__ __forceinline__ void com_to_bounds(const double com[3], const double size[3], double fx, double fy, int b[4]) {
+    const double c0 = com[0], c1 = com[1], c2 = com[2];
+    b[0] = (int)floor((c0 * c2 / fx - size[0] / 2.) / c2 * fx + 0.5);
+    b[1] = (int)floor((c0 * c2 / fx + size[0] / 2.) / c2 * fx + 0.5);
+    b[2] = (int)floor((c1 * c2 / fy - size[1] / 2.) / c2 * fy + 0.5);
+    b[3] = (int)floor((c1 * c2 / fy + size[1] / 2.) / c2 * fy + 0.5);
+}
+
+// HandDetector.refineCoMIterative (handdetector.py:546-567): num_iter times bounds -> getCrop -> calculateCoM -> fallback -> back to
+// frame coordinates with the reference's max(xstart, 0) (sic).  One workgroup per frame runs ALL iterations; the centre stays
+// float64 between them as on the host.  Window sums in float64 (column / row sums are integers, a sum of float32 depths of
+// 10..1500 mm over at most a frame is exact: the order is free); the mean as NumPy forms it: sum / num, * num, / num.
+// A centre whose depth is isclose to 0 ("CoM ill-defined") stops the frame with status 1 (com_out: the centre so far).
+__global__ __launch_bounds__(DPP_THREADS) void refine_com_iterative_kernel(const float* __restrict__ frames, int H, int W,
+                                                                           const float* __restrict__ partial, const float* __restrict__ com_in,
+                                                                           const float* __restrict__ cube, double fx, double fy, int num_iter,
+                                                                           float* __restrict__ com_out, int* __restrict__ status) {
+    __shared__ double s_red[4][DPP_THREADS / DPP_WAVE];
+    __shared__ CropRec s_r;
+    __shared__ double s_com[3];
+    __shared__ int s_stop;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* f = frames + (size_t)b * H * W;
+    float mn, mx;
+    frame_range_reduce(partial, b, lane, mn, mx);
+    const double size[3] = {(double)cube[b * 3], (double)cube[b * 3 + 1], (double)cube[b * 3 + 2]};
+    if (tid == 0) {
+        for (int d = 0; d < 3; ++d) s_com[d] = (double)com_in[b * 3 + d];
+        s_stop = 0;
+        s_r.max_depth = fminf(1500.0f, mx);
+        s_r.min_depth = fmaxf(10.0f, mn);
+    }
+    for (int it = 0; it < num_iter; ++it) {
+        if (tid == 0) {
+            if (fabs(s_com[2]) <= 1e-8 || !(fabs(s_com[0]) <= 1e300 && fabs(s_com[1]) <= 1e300 && fabs(s_com[2]) <= 1e300)) {
+                s_stop = 1;
+            } else {
+                int bd[4];
+                com_to_bounds(s_com, size, fx, fy, bd);
+                s_r.xstart = bd[0]; s_r.ystart = bd[2]; s_r.cw = bd[1] - bd[0]; s_r.ch = bd[3] - bd[2];
+                s_r.zstart = (float)(s_com[2] - size[2] / 2.);            // the window is a float32 array: its thresholds round to it
+                s_r.zend = (float)(s_com[2] + size[2] / 2.);
+            }
+        }
+        __syncthreads();
+        if (s_stop) break;
+        const CropRec r = s_r;
+        // only the part of the window inside the frame can hold valid pixels
+        const int y0 = r.ystart < 0 ? -r.ystart : 0, y1 = (r.ystart + r.ch > H) ? H - r.ystart : r.ch;
+        const int x0 = r.xstart < 0 ? -r.xstart : 0, x1 = (r.xstart + r.cw > W) ? W - r.xstart : r.cw;
+        double sx = 0.0, sy = 0.0, sd = 0.0, cnt = 0.0;
+        for (int y = y0 + wave; y < y1; y += DPP_THREADS / DPP_WAVE) {
+            double rs = 0.0, rc = 0.0, rx = 0.0;
+            for (int x = x0 + lane; x < x1; x += DPP_WAVE) {
+                float v = crop_window_value(f, H, W, r, x, y);
+                if (v < r.min_depth || v > r.max_depth) v = 0.0f;       // calculateCoM's own range test
+                if (v > 0.0f) { rx += x; rs += (double)v; rc += 1.0; }
+            }
+            sx += rx; sd += rs; cnt += rc; sy += rc * (double)y;
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sd += __shfl_xor(sd, o); cnt += __shfl_xor(cnt, o);
+        }
+        if (lane == 0) { s_red[0][wave] = sx; s_red[1][wave] = sy; s_red[2][wave] = sd; s_red[3][wave] = cnt; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < DPP_THREADS / DPP_WAVE; ++w) { sx += s_red[0][w]; sy += s_red[1][w]; sd += s_red[2][w]; cnt += s_red[3][w]; }
+            double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+            if (cnt > 0.0) { c0 = sx / cnt * cnt / cnt; c1 = sy / cnt * cnt / cnt; c2 = sd / cnt; }
+            if (fabs(c0) <= 1e-8 && fabs(c1) <= 1e-8 && fabs(c2) <= 1e-8 && r.cw > 0 && r.ch > 0)     // numpy.allclose(com, 0.)
+                c2 = (double)crop_window_value(f, H, W, r, r.cw / 2, r.ch / 2);
+            s_com[0] = c0 + (double)(r.xstart > 0 ? r.xstart : 0);
+            s_com[1] = c1 + (double)(r.ystart > 0 ? r.ystart : 0);
+            s_com[2] = c2;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        for (int d = 0; d < 3; ++d) com_out[b * 3 + d] = (float)s_com[d];
+        status[b] = s_stop;
+    }
 }
 
 }  // namespace
@@ -1374,7 +1615,7 @@ extern "C" int dpp_crop_refine(const float* frames, const void* records, int B, 
 
 extern "C" int dpp_crop_warp_ex(const float* frames, const void* records, int B, int H, int W, int dsz, int flags, float nd_value,
                                 float fill_value, float pad_value, float* out, dpp_stream_t stream) {
-    if (!frames || !records || !out || B < 1 || H < 1 || W < 1 || dsz < 1 || (flags & ~15)) return DPP_E_BADARG;
+    if (!frames || !records || !out || B < 1 || H < 1 || W < 1 || dsz < 1 || (flags & ~31)) return DPP_E_BADARG;
     dim3 grid(dpp_cdiv(dsz * dsz, DPP_THREADS), B);
     DPP_LAUNCH(crop_warp_ex_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
                static_cast<const CropRec*>(records), dsz, flags, nd_value, fill_value, pad_value, out);
@@ -1410,5 +1651,55 @@ extern "C" int dpp_inverse_crop(const float* crops, int B, int ch, int cw, const
     dim3 grid(dpp_cdiv(H * W, DPP_THREADS), B);
     DPP_LAUNCH(inverse_crop_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), crops, ch, cw, bounds, zrange, H, W,
                bilinear ? 1 : 0, nd_value, background, thresh_z ? 1 : 0, out);
+    return dpp_launch_status();
+}
+
+extern "C" size_t dpp_frame_range_bytes(int B) { return (size_t)(B > 0 ? B : 0) * FR_BANDS * 2 * sizeof(float); }
+
+extern "C" int dpp_frame_range(const float* frames, int B, int H, int W, float* partial, dpp_stream_t stream) {
+    if (!frames || !partial || B < 1 || H < 1 || W < 1) return DPP_E_BADARG;
+    DPP_LAUNCH(frame_range_kernel, dim3(FR_BANDS, B), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W, partial);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_crop_prepare_ranged(const float* partial, int B, const float* com, const float* cube, double fx, double fy, int dsz,
+                                       int stretch, void* records, float* M_out, dpp_stream_t stream) {
+    if (!partial || !com || !cube || !records || B < 1 || dsz < 1 || fx == 0.0 || fy == 0.0) return DPP_E_BADARG;
+    DPP_LAUNCH(crop_prepare_ranged_kernel, dim3(B), dim3(DPP_WAVE), 0, static_cast<hipStream_t>(stream), partial, com, cube, fabs(fx), fabs(fy),
+               dsz, stretch, static_cast<CropRec*>(records), M_out);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_track_refine(const float* frames, const void* records_in, int B, int H, int W, const float* com_in, const float* cube,
+                                const float* net_out, double fx, double fy, double ux, double uy, int flip_y, double crop_fx, double crop_fy,
+                                int dsz, float* com_out, float* com3d_out, void* records_out, float* M_out, int* status,
+                                dpp_stream_t stream) {
+    if (!frames || !records_in || !com_in || !cube || !net_out || !com_out || !com3d_out || !records_out || !status || B < 1 || H < 1 ||
+        W < 1 || dsz < 1 || fx == 0.0 || fy == 0.0 || crop_fx == 0.0 || crop_fy == 0.0)
+        return DPP_E_BADARG;
+    AugCam cam;
+    cam.fx = fx; cam.fy = fy; cam.ux = ux; cam.uy = uy; cam.flip_y = flip_y;
+    DPP_LAUNCH(track_refine_kernel, dim3(B), dim3(DPP_WAVE), 0, static_cast<hipStream_t>(stream), frames, H, W,
+               static_cast<const CropRec*>(records_in), com_in, cube, net_out, cam, fabs(crop_fx), fabs(crop_fy), dsz, com_out, com3d_out,
+               static_cast<CropRec*>(records_out), M_out, status);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_pose_finish(const float* net_out, int B, int J, const float* cube, const float* com3d, double fx, double fy, double ux,
+                               double uy, int flip_y, int flags, float* pose3d, float* pose_img, dpp_stream_t stream) {
+    if (!net_out || !cube || !com3d || !pose3d || !pose_img || B < 1 || J < 1 || fx == 0.0 || fy == 0.0 || (flags & ~7)) return DPP_E_BADARG;
+    AugCam cam;
+    cam.fx = fx; cam.fy = fy; cam.ux = ux; cam.uy = uy; cam.flip_y = flip_y;
+    DPP_LAUNCH(pose_finish_kernel, dim3(dpp_cdiv(B * J, DPP_THREADS)), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), net_out, B, J,
+               cube, com3d, cam, flags, pose3d, pose_img);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_refine_com_iterative(const float* frames, const float* partial, int B, int H, int W, const float* com_in, const float* cube,
+                                        double fx, double fy, int num_iter, float* com_out, int* status, dpp_stream_t stream) {
+    if (!frames || !partial || !com_in || !cube || !com_out || !status || B < 1 || H < 1 || W < 1 || num_iter < 0 || fx == 0.0 || fy == 0.0)
+        return DPP_E_BADARG;
+    DPP_LAUNCH(refine_com_iterative_kernel, dim3(B), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W, partial, com_in, cube,
+               fabs(fx), fabs(fy), num_iter, com_out, status);
     return dpp_launch_status();
 }

@@ -675,7 +675,7 @@ def crop_warp(rt, frames, records, B, H, W, dsz, out, normalize=True, nd_value=0
                   (frames, records, out), name, dict(kernel='crop_warp', flops=10.0 * B * dsz * dsz, bytes=8.0 * B * dsz * dsz))
 
 
-CROP_NORMALIZE, CROP_BILINEAR, CROP_NO_RANGE, CROP_NO_THRESH = 1, 2, 4, 8      # dpp_crop_warp_ex flags
+CROP_NORMALIZE, CROP_BILINEAR, CROP_NO_RANGE, CROP_NO_THRESH, CROP_FLIP_X = 1, 2, 4, 8, 16      # dpp_crop_warp_ex flags
 
 
 def crop_warp_ex(rt, frames, records, B, H, W, dsz, out, flags=0, nd_value=0.0, fill_value=None, pad_value=0.0, name='crop_warp_ex'):
@@ -716,6 +716,52 @@ def crop_refine(rt, frames, records, B, H, W, com_in, cube, net_out, cam, com_ou
                   (frames.ptr, records.ptr, B, H, W, com_in.ptr, cube.ptr, net_out.ptr, float(fx), float(fy), float(ux), float(uy), int(flip),
                    _p(gt3d_orig), int(J), _p(pca_mean), _p(pca_comp), int(E), com_out.ptr, _p(com3d_out), _p(gt3d_crop), _p(out_y)),
                   (frames, records, com_in, cube, net_out, gt3d_orig, pca_mean, pca_comp, com_out, com3d_out, gt3d_crop, out_y), name)
+
+
+def frame_range_workspace(rt, B):
+    """The per-band (min, max) partials of B frames: what frame_range writes and crop_prepare_ranged / refine_com_iterative read."""
+    return rt.alloc(max(1, int(rt.lib.dpp_frame_range_bytes(B)) // 4), np.float32, zero=False)
+
+
+def frame_range(rt, frames, B, H, W, partial, name='frame_range'):
+    """dpp_frame_range: the depth range of every frame, many workgroups per frame -- the ONE pass over the whole frame of a tracked frame."""
+    return Launch(rt.lib.dpp_frame_range, (frames.ptr, B, H, W, partial.ptr), (frames, partial), name,
+                  dict(kernel='frame_range', flops=2.0 * B * H * W, bytes=4.0 * B * H * W))
+
+
+def crop_prepare_ranged(rt, partial, B, com, cube, fx, fy, dsz, records, M_out=None, stretch=False, name='crop_prepare_ranged'):
+    """dpp_crop_prepare_ranged: crop_prepare's records from frame_range's partials (no pass over the frame)."""
+    return Launch(rt.lib.dpp_crop_prepare_ranged, (partial.ptr, B, com.ptr, cube.ptr, float(fx), float(fy), dsz, int(bool(stretch)), records.ptr,
+                                                   _p(M_out)),
+                  (partial, com, cube, records, M_out), name)
+
+
+def track_refine(rt, frames, records_in, B, H, W, com_in, cube, net_out, cam, crop_fx, crop_fy, dsz, com_out, com3d_out, records_out, status,
+                 M_out=None, name='track_refine'):
+    """dpp_track_refine: the tracked centre from the refinement net's output, fused with the prepare of the final crop around it."""
+    fx, fy, ux, uy, flip = cam
+    return Launch(rt.lib.dpp_track_refine,
+                  (frames.ptr, records_in.ptr, B, H, W, com_in.ptr, cube.ptr, net_out.ptr, float(fx), float(fy), float(ux), float(uy), int(flip),
+                   float(crop_fx), float(crop_fy), dsz, com_out.ptr, com3d_out.ptr, records_out.ptr, _p(M_out), status.ptr),
+                  (frames, records_in, com_in, cube, net_out, com_out, com3d_out, records_out, M_out, status), name)
+
+
+POSE_HAND_RIGHT, POSE_INV_X, POSE_INV_Y = 1, 2, 4      # dpp_pose_finish flags
+
+
+def pose_finish(rt, net_out, B, J, cube, com3d, cam, flags, pose3d, pose_img, name='pose_finish'):
+    """dpp_pose_finish: estimatePose's sign rules, pose * cube_z / 2 + com3D and joints3DToImg of the result."""
+    fx, fy, ux, uy, flip = cam
+    return Launch(rt.lib.dpp_pose_finish, (net_out.ptr, B, J, cube.ptr, com3d.ptr, float(fx), float(fy), float(ux), float(uy), int(flip), int(flags),
+                                           pose3d.ptr, pose_img.ptr),
+                  (net_out, cube, com3d, pose3d, pose_img), name)
+
+
+def refine_com_iterative(rt, frames, partial, B, H, W, com_in, cube, fx, fy, num_iter, com_out, status, name='refine_com_iterative'):
+    """dpp_refine_com_iterative: refineCoMIterative of B frames, all iterations in one launch."""
+    return Launch(rt.lib.dpp_refine_com_iterative, (frames.ptr, partial.ptr, B, H, W, com_in.ptr, cube.ptr, float(fx), float(fy), int(num_iter),
+                                                    com_out.ptr, status.ptr),
+                  (frames, partial, com_in, cube, com_out, status), name)
 
 
 def copy2d(rt, src, lds, dst, ldd, rows, cols, relu=False, name='copy2d'):

@@ -1,0 +1,218 @@
+"""
+Realtime tracking on the device: a depth frame in, the followed hand's 3-D joints out, ONE launch plan per frame.
+
+What the reference does per frame on the host in tracking mode (/root/reference/src/util/realtimehandposepipeline.py:296-370,
+/root/reference/src/util/handdetector.py:504-544) -- HandDetector(frame), track(lastcom, cube, doHandSize=False),
+cropArea3D(com=loc), the normalisation of :332-336, estimatePose and pose * cube_z / 2 + com3D -- is here
+
+    frame_range                                   the frame's depth range, many workgroups, the ONE pass over the whole frame
+    crop_prepare_ranged(lastcom, stretch)         track's window: getCrop + resizeCrop(cropped, dsize), handdetector.py:512-519
+    crop_warp(normalised) -> crop_center x2       refineCoM's three inputs, :634-669
+    the refinement net's forward plan
+    track_refine                                  com' = joint3DToImg(out * cube_z/2 + jointImgTo3D(lastcom)), fallback, status; the
+                                                  final crop's record, M and com3D; lastcom := com' (device state, in place)
+    crop_warp_ex(normalised[, flipped])           cropArea3D(com=loc) + :332-336 (+ crop[:, ::-1] for HAND_RIGHT, :351)
+    the pose net's forward plan
+    pose_finish                                   the sign rules of :356-369, pose * cube_z / 2. + com3D (:198), joints3DToImg (:407)
+
+track() has no calculateCoM re-centring: this is hipdp/cascade.py's chain minus crop_com.  Tracking is sequential (frame t is
+cropped around the centre found in frame t - 1), so the centre never leaves the device between frames: the host uploads a frame,
+runs the plan and downloads one small result block.
+
+LOST frames.  Where the refined centre's depth is numpy.isclose to 0 the reference takes comToBounds' "CoM ill-defined" branch
+(handdetector.py:204-213) and crops the MIDDLE of the frame; no device kernel implements that branch.  track_refine flags such a
+frame instead (status 1), gives it an empty crop window (an all-zero net input, finite outputs), and the tracker refuses further
+frames until reset(com).
+"""
+import numpy as np
+
+from . import ops
+from .augmenter import camera_tuple
+
+OK, LOST = 0, 1
+
+
+def _net_side(net):
+    dims = net.cfgParams.inputDim
+    d0 = dims[0] if isinstance(dims[0], (list, tuple)) else dims
+    return int(d0[2])
+
+
+def _engine_b1(net, rt, what):
+    net.setDeterministic()
+    eng = net._engine(rt)
+    if eng.N != 1:
+        raise ValueError("%s must be built for a batch of one (batchSize=%d): one frame is one plan" % (what, eng.N))
+    if any(t.shape[3] != 1 for t in eng.x_ins):
+        raise ValueError("%s must take single-channel depth crops" % what)
+    return eng
+
+
+def refine_stage(rt, frame, H, W, partial, rec, com_in, cube, ceng, cam, fx, fy, dsz_final, com_out, com3d, rec_out, status, M=None):
+    """The (op, side) list of HandDetector.track for ONE frame whose depth-range partials are in `partial`: window around com_in,
+    the refinement net's inputs, its forward plan, track_refine.  Shared by HandTracker's plan and HandDetector.track."""
+    nin = len(ceng.x_ins)
+    if nin not in (1, 3):
+        raise NotImplementedError("Number of inputs is {}".format(nin))
+    if ceng.out_dim != 3:
+        raise ValueError("the refinement net must regress one 3-D offset")
+    rs = int(ceng.x_ins[0].shape[1])
+    in0 = ceng.x_ins[0].buf.reshape(1, rs, rs)
+    out = [(ops.crop_prepare_ranged(rt, partial, 1, com_in, cube, fx, fy, rs, rec, None, stretch=True), False),
+           (ops.crop_warp(rt, frame, rec, 1, H, W, rs, in0, normalize=True, nd_value=0.0, name='track_in0'), False)]
+    for k in range(1, nin):                        # 1/2 and 1/4 CENTRE crops, handdetector.py:657-669
+        f = 2 ** k
+        out.append((ops.crop_center(rt, in0, 1, rs, rs, ceng.x_ins[k].buf, rs // f, rs // f, name='track_in%d' % k), False))
+    out.extend(ceng.fwd.ops)
+    out.append((ops.track_refine(rt, frame, rec, 1, H, W, com_in, cube, ceng.out.buf, cam, fx, fy, dsz_final, com_out, com3d, rec_out, status,
+                                 M_out=M), False))
+    return out
+
+
+class HandTracker(object):
+    def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, hand_right=False, invX=False, invY=False, fx=None, fy=None):
+        """
+        :param importer:   the dataset importer (camera; NYU / MSRA flip the y axis)
+        :param poseNet:    the pose regressor, built for a batch of one; its output is J x 3 normalised joints
+        :param comrefNet:  a ScaleNet-like net (numInputs 1 or 3) regressing the normalised 3-D offset of the hand centre, batch of one
+        :param H, W:       frame size
+        :param cube:       metric cube (mm) around the hand
+        :param hand_right, invX, invY: estimatePose's mirroring (realtimehandposepipeline.py:347-369)
+        :param fx, fy:     what the reference hands to HandDetector (config['fx'], config['fy']); default: the importer's
+        """
+        self.rt, self.H, self.W = rt, int(H), int(W)
+        self.importer = importer
+        self.cam = camera_tuple(importer)
+        self.fx = abs(float(importer.fx if fx is None else fx))
+        self.fy = abs(float(importer.fy if fy is None else fy))
+        self.ceng = _engine_b1(comrefNet, rt, 'comrefNet')
+        self.peng = _engine_b1(poseNet, rt, 'poseNet')
+        if len(self.peng.x_ins) != 1 or self.peng.out_dim % 3:
+            raise ValueError("the pose net takes one crop and regresses J x 3 coordinates")
+        self.rs, self.ds, self.J = int(self.ceng.x_ins[0].shape[1]), int(self.peng.x_in.shape[1]), self.peng.out_dim // 3
+        f32 = np.float32
+        J3 = self.J * 3
+        self.frames = [rt.alloc((1, self.H, self.W), f32, zero=False) for _ in range(2)]      # t and t + 1 (process_sequence)
+        self.partial = ops.frame_range_workspace(rt, 1)
+        self.rec = rt.alloc(rt.lib.dpp_crop_record_bytes(), np.uint8)
+        self.cube = rt.alloc((1, 3), f32)
+        # everything the host reads per frame is ONE block: pose (mm), pose in image coordinates, centre (= the state), com3D, M, status
+        self.res = rt.alloc(2 * J3 + 16, f32)
+        self.pose3d, self.pose_img = self.res.view(0, (1, self.J, 3)), self.res.view(J3, (1, self.J, 3))
+        self.com, self.com3d = self.res.view(2 * J3, (1, 3)), self.res.view(2 * J3 + 3, (1, 3))
+        self.M, self.status = self.res.view(2 * J3 + 6, (1, 9)), self.res.view(2 * J3 + 15, (1,), np.int32)
+        self.crop = self.peng.x_in.buf.reshape(1, self.ds, self.ds)          # the pose net's input IS the final crop
+        self.flags = 0
+        self.set_hand(hand_right)
+        self.set_inv(invX, invY)
+        self._plans = {}
+        self.lost = True                                                       # no centre yet
+        self.set_cube(cube)
+        self.runs = 0
+
+    # ---- device state -----------------------------------------------------------------------------------------------------
+    def reset(self, com):
+        """Start (again) from the centre `com` (image coordinates, z in mm)."""
+        com = np.asarray(com, np.float32).reshape(3)
+        if not np.all(np.isfinite(com)) or np.isclose(com[2], 0.):
+            raise ValueError("reset needs a centre with a depth: %r" % (com,))
+        self.com.set(com)
+        self.lost = False
+
+    def set_cube(self, cube):
+        cube = np.asarray(cube, np.float32).reshape(3)
+        if not (cube > 0).all():
+            raise ValueError("the cube must have a positive size: %r" % (cube,))
+        self.cube.set(cube)
+        self.cube_host = cube
+
+    def set_hand(self, right):
+        """HAND_RIGHT mirrors the pose net's input and the x coordinate of its output.  (The mirroring is an argument of two
+        launches, so each combination of hand / invX / invY has a plan of its own, recorded the first time it is used.)"""
+        self.flags = (self.flags & ~ops.POSE_HAND_RIGHT) | (ops.POSE_HAND_RIGHT if right else 0)
+
+    def set_inv(self, invX, invY):
+        self.flags = (self.flags & ~(ops.POSE_INV_X | ops.POSE_INV_Y)) | (ops.POSE_INV_X if invX else 0) | (ops.POSE_INV_Y if invY else 0)
+
+    # ---- the per-frame plan -----------------------------------------------------------------------------------------------
+    def plan(self, slot=0):
+        key = (slot, self.flags)
+        if key not in self._plans:
+            rt, H, W, fr = self.rt, self.H, self.W, self.frames[slot]
+            p = ops.Plan('track')
+            p.add(ops.frame_range(rt, fr, 1, H, W, self.partial))
+            # the state buffer is read (prepare, track_refine) and then rewritten by ONE lane of track_refine: in place
+            for op, side in refine_stage(rt, fr, H, W, self.partial, self.rec, self.com, self.cube, self.ceng, self.cam, self.fx, self.fy,
+                                         self.ds, self.com, self.com3d, self.rec, self.status, self.M):
+                p.add(op, side)
+            wf = ops.CROP_NORMALIZE | (ops.CROP_FLIP_X if self.flags & ops.POSE_HAND_RIGHT else 0)
+            p.add(ops.crop_warp_ex(rt, fr, self.rec, 1, H, W, self.ds, self.crop, flags=wf, nd_value=0.0, name='track_crop'))
+            for op, side in self.peng.fwd.ops:
+                p.add(op, side)
+            p.add(ops.pose_finish(rt, self.peng.out.buf, 1, self.J, self.cube, self.com3d, self.cam, self.flags, self.pose3d, self.pose_img))
+            self._plans[key] = p
+        return self._plans[key]
+
+    def _result(self, res, crop=None):
+        J3 = self.J * 3
+        st = int(res[2 * J3 + 15:2 * J3 + 16].view(np.int32)[0])
+        out = dict(pose=res[:J3].reshape(self.J, 3), pose_img=res[J3:2 * J3].reshape(self.J, 3), com=res[2 * J3:2 * J3 + 3],
+                   com3D=res[2 * J3 + 3:2 * J3 + 6], M=res[2 * J3 + 6:2 * J3 + 15].reshape(3, 3), status=st)
+        if crop is not None:
+            out['crop'] = crop
+        return out
+
+    def _check(self, frame):
+        if self.lost:
+            raise RuntimeError("the track is lost (or was never started): call reset(com) with a new centre")
+        frame = np.asarray(frame, np.float32)
+        if frame.shape != (self.H, self.W):
+            raise ValueError("frame shape %s, expected %s" % (frame.shape, (self.H, self.W)))
+        return frame
+
+    def process(self, frame, return_crop=False):
+        """One frame, synchronously: one upload, one plan, one download.  Returns dict(pose [J][3] mm, pose_img [J][3], com [3] image
+        coordinates, com3D [3], M [3][3], status[, crop]) -- `crop` as the pose net saw it (normalised; mirrored for HAND_RIGHT).
+        status LOST: see the module docstring; the other entries are finite but meaningless and the tracker needs reset(com)."""
+        frame = self._check(frame)
+        self.frames[0].set(frame)
+        self.plan(0).run(self.rt)
+        self.runs += 1
+        self.rt.synchronize()
+        out = self._result(self.res.get(), self.crop.get()[0] if return_crop else None)
+        self.lost = out['status'] != OK
+        return out
+
+    def process_sequence(self, frames, return_crops=False):
+        """A sequence of frames: the upload of frame t + 1 runs under the plan of frame t (two frame buffers, copy stream), the result
+        of frame t is read while frame t + 1 is in flight.  Same values as process() frame by frame.  Stops at a lost frame (its
+        result is the last one returned)."""
+        rt = self.rt
+        staged = hasattr(rt, 'staged_upload')
+        results, pending, free = [], None, [None, None]
+
+        def resolve(p):
+            res, crop = p
+            out = self._result(res.get(), crop.get()[0] if crop is not None else None)
+            results.append(out)
+            return out['status'] == OK
+        for n, frame in enumerate(frames):
+            frame = self._check(frame)
+            k = n & 1
+            if staged:
+                rt.wait_event(rt.staged_upload(self.frames[k], frame[None], free[k]))
+            else:
+                self.frames[k].set(frame)
+            self.plan(k).run(rt)
+            self.runs += 1
+            free[k] = rt.record_event() if staged else None
+            handle = (rt.read_async(self.res), rt.read_async(self.crop) if return_crops else None)
+            if pending is not None and not resolve(pending):
+                self.lost = True              # frame n ran on a meaningless centre: dropped
+                rt.synchronize()
+                return results
+            pending = handle
+        if pending is not None and not resolve(pending):
+            self.lost = True
+        rt.synchronize()
+        return results

@@ -9,7 +9,9 @@ cropArea3D (handdetector.py:382-490, docom=False: the call the importers make fo
 `crop_frames` is its batched form fused with Dataset.imgStackDepthOnly.  recropHand, resizeCrop, bilinearResize,
 getInverseCrop and applyCrop3D are device-backed as well, with batched forms `recrop_crops`, `resize_crops` and
 `inverse_crops` (one launch per batch each).  CoM refinement by a ScaleNet (refineCoM, handdetector.py:634-676) goes
-through the net's computeOutput.  Whole-frame detection / tracking (detect, track) are not provided yet.
+through the net's computeOutput.  track (handdetector.py:504-544, doHandSize=False) runs on the device with the kernels of the
+realtime tracker (hipdp/tracker.py), refineCoMIterative has a batched device form (`refine_com_iterative`); whole-frame detection
+(detect: cv2 contour analysis) and hand-size estimation are not built.
 
 resizeMethod is honoured where the reference reads it: RESIZE_CV2_NN (the default) is cv2's nearest-neighbour resize,
 RESIZE_BILINEAR the reference's own ND-aware bilinearResize.  RESIZE_CV2_LINEAR (cv2 INTER_LINEAR) is not built: the new
@@ -443,10 +445,54 @@ class HandDetector(object):
         return crops[0]
 
     def detect(self, *args, **kwargs):
-        raise NotImplementedError("hand detection / tracking (cv2.findContours slab analysis, handdetector.py:504-631) belongs to the realtime demo "
-                                  "(util/realtimehandposepipeline.py is its only caller), which is out of scope (SURVEY.md section 2)")
+        """Not built: the reference finds the hand by contour analysis of depth slabs (cv2.findContours / contourArea / moments,
+        handdetector.py:569-632), which cannot be pinned without OpenCV.  Seed a track with a known centre instead (track, or
+        util.realtimehandposepipeline's init_com / whole-frame centre of mass)."""
+        raise NotImplementedError("hand detection (cv2.findContours slab analysis, handdetector.py:569-632) is not built: it cannot be pinned "
+                                  "without OpenCV; seed the track with a known centre (RealtimeHandposePipeline(init_com=...) or reset(com))")
 
-    track = detect
+    def track(self, com, size=(250, 250, 250), dsize=(128, 128), doHandSize=True):
+        """Follow the hand from the previous frame's centre `com` (handdetector.py:504-544): the window of the cube around com,
+        resized to dsize as it is, goes through the refinement net; returns (new centre in image coordinates, size).  One frame
+        through the kernels of hipdp.tracker (frame_range, crop_prepare_ranged, crop_warp, the net's plan, track_refine).
+        dsize must be the refinement net's input size, as in the reference.  doHandSize=True (hand-size estimation from
+        cv2.findContours, :527-542) is not built.  A centre whose depth is close to 0 cannot be tracked from (comToBounds'
+        ill-defined branch is not built either): ValueError."""
+        if self.refineNet is None or self.importer is None:
+            raise RuntimeError("Need refineNet for this")
+        if doHandSize is True:
+            raise NotImplementedError("track(doHandSize=True): hand-size estimation needs cv2.findContours (handdetector.py:527-542), which is "
+                                      "not built; pass doHandSize=False")
+        if numpy.isclose(com[2], 0.):
+            raise ValueError("track from an ill-defined CoM (com[2] == 0) is not built")
+        if dsize[0] != dsize[1]:
+            raise NotImplementedError("square destination sizes only")
+        from hipdp import ops, tracker
+        from hipdp.augmenter import camera_tuple
+        from hipdp.runtime import default_runtime
+        rt = default_runtime()
+        ceng = tracker._engine_b1(self.refineNet, rt, 'refineNet')
+        if int(ceng.x_ins[0].shape[1]) != int(dsize[0]):
+            raise ValueError("dsize %r is not the refinement net's input size %d" % (tuple(dsize), ceng.x_ins[0].shape[1]))
+        frame = numpy.ascontiguousarray(self.dpt, numpy.float32)
+        H, W = frame.shape
+        fr = rt.upload(frame[None])
+        st = rt.alloc(16, numpy.float32)                     # centre in, centre out, com3D, status
+        com_in, com_out, com3d, status = st.view(0, (1, 3)), st.view(3, (1, 3)), st.view(6, (1, 3)), st.view(9, (1,), numpy.int32)
+        host = numpy.zeros(16, numpy.float32)
+        host[0:3] = numpy.asarray(com, numpy.float32)
+        st.set(host)
+        cube = rt.upload(numpy.asarray(size, numpy.float32).reshape(1, 3))
+        partial = ops.frame_range_workspace(rt, 1)
+        rec = rt.alloc(rt.lib.dpp_crop_record_bytes(), numpy.uint8)
+        ops.frame_range(rt, fr, 1, H, W, partial)(rt.stream)
+        plan = ops.Plan('track1')
+        for op, side in tracker.refine_stage(rt, fr, H, W, partial, rec, com_in, cube, ceng, camera_tuple(self.importer), self.fx, self.fy,
+                                             int(dsize[0]), com_out, com3d, rec, status):
+            plan.add(op, side)
+        plan.run(rt)
+        rt.synchronize()
+        return st.get()[3:6].copy(), size
 
 
 _CROP_NORMALIZE, _CROP_BILINEAR, _CROP_NO_RANGE, _CROP_NO_THRESH = 1, 2, 4, 8     # hipdp.ops.CROP_* (dpp_crop_warp_ex flags)
@@ -628,3 +674,29 @@ def inverse_crops(crops, frame_shape, bounds, thresh_z=True, background=0., meth
     ops.inverse_crop(rt, src, B, ch, cw, bd, H, W, out, bilinear=bilinear, nd_value=nd_value, background=background, zrange=zr)(rt.stream)
     rt.synchronize()
     return out.get()
+
+
+def refine_com_iterative(frames, coms, cubes, fx, fy, num_iter, runtime=None, return_status=False):
+    """Batched HandDetector.refineCoMIterative (handdetector.py:546-567) on the device: frames (B, H, W) raw depth in mm (the
+    detector's range [max(10, min), min(1500, max)] is applied per frame as the constructor does), coms (B, 3), cubes (B, 3) ->
+    float32 (B, 3).  Two launches for the whole batch: the depth ranges, then one workgroup per frame runs all num_iter iterations
+    with a float64 centre (window sums in float64, where the host method sums depth in the frame's dtype).  A frame whose centre's
+    depth becomes close to 0 (comToBounds' ill-defined branch) is finished by the host method."""
+    from hipdp import ops
+    from hipdp.runtime import default_runtime
+    rt = runtime or default_runtime()
+    frames = numpy.ascontiguousarray(frames, numpy.float32)
+    B, H, W = frames.shape
+    fr = rt.upload(frames)
+    co = rt.upload(numpy.ascontiguousarray(coms, numpy.float32).reshape(B, 3))
+    cu = rt.upload(numpy.ascontiguousarray(cubes, numpy.float32).reshape(B, 3))
+    partial = ops.frame_range_workspace(rt, B)
+    out, status = rt.alloc((B, 3), zero=False), rt.alloc((B,), numpy.int32)
+    ops.frame_range(rt, fr, B, H, W, partial)(rt.stream)
+    ops.refine_com_iterative(rt, fr, partial, B, H, W, co, cu, abs(fx), abs(fy), int(num_iter), out, status)(rt.stream)
+    rt.synchronize()
+    res, st = out.get(), status.get()
+    for i in numpy.nonzero(st)[0]:
+        hd = HandDetector(frames[i].copy(), abs(fx), abs(fy))
+        res[i] = hd.refineCoMIterative(numpy.asarray(coms[i], numpy.float64), int(num_iter), tuple(float(c) for c in numpy.asarray(cubes[i])))
+    return (res, st) if return_status else res

@@ -1,0 +1,270 @@
+"""
+RealtimeHandposePipeline -- the headless part of /root/reference/src/util/realtimehandposepipeline.py: a depth frame goes in, the hand
+is followed from the previous frame's centre, 3-D joints come out.
+
+Built: the constants and constructor, initNets, detect (tracking mode, :296-337), estimatePose (:339-370), processKey's state
+changes, reset, and a headless processVideo(device) that returns the poses in mm and runs every frame as ONE device plan
+(hipdp.tracker.HandTracker).  detect() + estimatePose() called separately go through the per-call API (HandDetector.track,
+cropArea3D, computeOutput) and give the same numbers as the fused plan.
+
+Not built: HandDetector.detect (contour analysis of depth slabs with cv2.findContours, it cannot be pinned without OpenCV) and with
+it the detection mode of detect(); hand-size calibration (STATE_INIT, estimateHandsize: cv2 contours as well); show, addStatusBar
+and the cv2 windows; the producer / consumer processes of processVideoThreaded (their shared state is plain attributes here:
+`.value` holders instead of multiprocessing.Value, a dict instead of Manager().dict()).
+
+Because detect is missing, the first frame needs a SEED: init_com= (image coordinates, z in mm, e.g. a dataset's annotation of the
+first frame), which also switches tracking on; or seed_com=True, an explicitly NON-reference seed -- the centre of mass of the whole
+range-limited frame (what cropArea3D(com=None) uses) refined by refineCoMIterative(com, 5, cube), the step the reference's detect
+applies to its own seed (handdetector.py:610).  With tracking off, or an all-zero last centre and no seed, detect raises the
+NotImplementedError of HandDetector.detect.
+
+A LOST track (the tracked centre's depth is close to 0: the reference would crop the middle of the frame through comToBounds'
+"CoM ill-defined" branch, which is not built) gives a zero crop, eye(3) and a zero com3D -- the answer of :326-327 -- and clears
+the last centre, so that the next frame needs a seed again.
+"""
+import copy
+import time
+
+import numpy
+
+from net.poseregnet import PoseRegNet, PoseRegNetParams
+from net.resnet import ResNet, ResNetParams
+from net.scalenet import ScaleNet, ScaleNetParams
+from util.handdetector import HandDetector, refine_com_iterative
+
+
+class _Value(object):
+    """Stand-in for multiprocessing.Value: the reference reads and writes `.value`."""
+
+    def __init__(self, value):
+        self.value = value
+
+
+class RealtimeHandposePipeline(object):
+    """Realtime pipeline for handpose estimation"""
+
+    # states of pipeline
+    STATE_IDLE = 0
+    STATE_INIT = 1
+    STATE_RUN = 2
+
+    # different hands
+    HAND_LEFT = 0
+    HAND_RIGHT = 1
+
+    # different detectors
+    DETECTOR_COM = 0
+
+    def __init__(self, poseNet, config, di, verbose=False, comrefNet=None, init_com=None, seed_com=False):
+        """
+        :param poseNet:   network for pose estimation (a built net, or PoseRegNetParams / ResNetParams, with loadFile or not)
+        :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=])
+        :param di:        depth importer
+        :param comrefNet: refinement network of the hand centre (a built net or ScaleNetParams)
+        :param init_com:  seed of the track, image coordinates (switches tracking on)
+        :param seed_com:  NON-reference seed from the frame's own centre of mass (module docstring)
+        """
+        self.importer = di
+        self.poseNet = poseNet
+        self.comrefNet = comrefNet
+        self.initialconfig = copy.deepcopy(config)
+        self.sync = dict(config=config, fid=0, crop=numpy.ones((128, 128), dtype='float32'),
+                         com3D=numpy.asarray([0, 0, 300], dtype='float32'), frame=numpy.ones((240, 320), dtype='float32'), M=numpy.eye(3))
+        self.stop = _Value(False)
+        self.verbose = verbose
+        self.hand = _Value(self.HAND_LEFT)
+        self.state = _Value(self.STATE_IDLE)
+        self.detection = _Value(self.DETECTOR_COM)
+        self.handsizes = []
+        self.numinitframes = 50
+        self.tracking = _Value(init_com is not None or bool(seed_com))
+        self.init_com = None if init_com is None else numpy.asarray(init_com, numpy.float32).copy()
+        self.seed_com = bool(seed_com)
+        self.lastcom = (0, 0, 0) if init_com is None else self.init_com.copy()
+        self.show_pose = False
+        self.show_crop = False
+        self._tracker = None
+
+    def initNets(self):
+        """Build the nets from their parameters (loading loadFile where set) and compile their forward plans (:118-141)."""
+        if isinstance(self.poseNet, PoseRegNetParams):
+            self.poseNet = PoseRegNet(numpy.random.RandomState(23455), cfgParams=self.poseNet)
+        elif isinstance(self.poseNet, ResNetParams):
+            self.poseNet = ResNet(numpy.random.RandomState(23455), cfgParams=self.poseNet)
+        elif not isinstance(self.poseNet, (PoseRegNet, ResNet)):
+            raise RuntimeError("Unknown pose estimation method!")
+        self.poseNet.setDeterministic()
+        self.poseNet.computeOutput(numpy.zeros(self.poseNet.cfgParams.inputDim, dtype='float32'))
+        if self.comrefNet is not None:
+            if isinstance(self.comrefNet, ScaleNetParams):
+                self.comrefNet = ScaleNet(numpy.random.RandomState(23455), cfgParams=self.comrefNet)
+            elif not isinstance(self.comrefNet, ScaleNet):
+                raise RuntimeError("Unknown refine method!")
+            self.comrefNet.setDeterministic()
+            dims = self.comrefNet.cfgParams.inputDim
+            dims = dims if isinstance(dims[0], (list, tuple)) else [dims]
+            ins = [numpy.zeros(sz, dtype='float32') for sz in dims]
+            self.comrefNet.computeOutput(ins if len(ins) > 1 else ins[0])
+
+    # ---- sizes ------------------------------------------------------------------------------------------------------------
+    def _pose_dsize(self):
+        d = self.poseNet.cfgParams.inputDim
+        return (int(d[2]), int(d[3]))
+
+    def _refine_dsize(self):
+        dims = self.comrefNet.cfgParams.inputDim
+        d0 = dims[0] if isinstance(dims[0], (list, tuple)) else dims
+        return (int(d0[2]), int(d0[3]))
+
+    def _seed(self, frame):
+        """The NON-reference seed: whole-frame centre of mass + refineCoMIterative(com, 5, cube)."""
+        cfg = self.sync['config']
+        hd = HandDetector(numpy.asarray(frame, numpy.float32).copy(), cfg['fx'], cfg['fy'], importer=self.importer)
+        com = hd.calculateCoM(hd.dpt)
+        if numpy.allclose(com, 0.):
+            return numpy.zeros(3, numpy.float32)
+        cube = numpy.asarray(cfg['cube'], numpy.float32)
+        return refine_com_iterative(numpy.asarray(frame, numpy.float32)[None], com[None], cube[None], cfg['fx'], cfg['fy'], 5)[0]
+
+    def _need_seed(self, frame):
+        """The centre to track from, seeding it where there is none; without a seed: HandDetector.detect's NotImplementedError."""
+        if self.state.value == self.STATE_INIT:
+            raise NotImplementedError("hand-size calibration (STATE_INIT: estimateHandsize from cv2.findContours) is not built")
+        if self.tracking.value and not numpy.allclose(self.lastcom, 0):
+            return numpy.asarray(self.lastcom, numpy.float32)
+        if self.tracking.value and self.seed_com:
+            com = self._seed(frame)
+            if not numpy.isclose(com[2], 0.):
+                return com
+        cfg = self.sync['config']
+        return HandDetector(numpy.zeros((2, 2), numpy.float32), cfg['fx'], cfg['fy']).detect(size=cfg['cube'], doHandSize=False)
+
+    # ---- the reference's per-call API ---------------------------------------------------------------------------------------
+    def detect(self, frame):
+        """Follow the hand into `frame` (:296-337, tracking mode): (normalised crop, transformation M, com3D)."""
+        cfg = self.sync['config']
+        lastcom = self._need_seed(frame)
+        hd = HandDetector(frame, cfg['fx'], cfg['fy'], importer=self.importer, refineNet=self.comrefNet)
+        loc, handsz = hd.track(lastcom, cfg['cube'], dsize=self._refine_dsize(), doHandSize=False)
+        self.lastcom = loc
+        self.handsizes = []
+        if numpy.allclose(loc, 0) or numpy.isclose(loc[2], 0.):
+            self.lastcom = (0, 0, 0)                   # lost (module docstring)
+            return numpy.zeros(self._pose_dsize()[::-1], dtype='float32'), numpy.eye(3), numpy.zeros(3, numpy.float32)
+        crop, M, com = hd.cropArea3D(com=loc, size=cfg['cube'], dsize=self._pose_dsize())
+        com3D = self.importer.jointImgTo3D(com)
+        sc = (cfg['cube'][2] / 2.)
+        crop[crop == 0] = com3D[2] + sc
+        crop.clip(com3D[2] - sc, com3D[2] + sc)        # (the reference discards this result as well, :334)
+        crop -= com3D[2]
+        crop /= sc
+        return crop, M, com3D
+
+    def estimatePose(self, crop, com3D):
+        """Estimate the hand pose (:339-370): normalised joint positions (J, 3); the caller forms pose * cube[2] / 2. + com3D."""
+        if self.hand.value == self.HAND_LEFT:
+            inp = crop[None, None, :, :].astype('float32')
+        else:
+            inp = crop[None, None, :, ::-1].astype('float32')
+        jts = self.poseNet.computeOutput(numpy.ascontiguousarray(inp))
+        jj = jts[0].reshape((-1, 3))
+        cfg = self.sync['config']
+        if 'invX' in cfg:
+            if cfg['invX'] is True:
+                jj[:, 1] *= (-1.)
+        if 'invY' in cfg:
+            if cfg['invY'] is True:
+                jj[:, 0] *= (-1.)
+        if self.hand.value == self.HAND_RIGHT:
+            jj[:, 0] *= (-1.)
+        return jj
+
+    # ---- the fused path -----------------------------------------------------------------------------------------------------
+    def tracker(self, H, W):
+        """The device tracker for H x W frames, its state brought in line with the pipeline's (cube, hand, invX / invY)."""
+        from hipdp.runtime import default_runtime
+        from hipdp.tracker import HandTracker
+        cfg = self.sync['config']
+        t = self._tracker
+        if t is None or (t.H, t.W) != (H, W) or (t.fx, t.fy) != (abs(float(cfg['fx'])), abs(float(cfg['fy']))):
+            t = self._tracker = HandTracker(default_runtime(), self.importer, self.poseNet, self.comrefNet, H, W, cfg['cube'],
+                                            fx=cfg['fx'], fy=cfg['fy'])
+        if tuple(numpy.float32(cfg['cube'])) != tuple(t.cube_host):
+            t.set_cube(cfg['cube'])
+        t.set_hand(self.hand.value == self.HAND_RIGHT)
+        t.set_inv(cfg.get('invX') is True, cfg.get('invY') is True)
+        return t
+
+    def processFrame(self, frame):
+        """detect + estimatePose + the de-normalisation of one frame as ONE device plan: the tracker's result dict (pose in mm)."""
+        frame = numpy.asarray(frame, numpy.float32)
+        lastcom = self._need_seed(frame)
+        t = self.tracker(*frame.shape)
+        if t.lost or not numpy.array_equal(numpy.asarray(lastcom, numpy.float32), numpy.asarray(getattr(self, '_devcom', (0, 0, 0)), numpy.float32)):
+            t.reset(lastcom)                           # the host's centre changed behind the device's back (seed, reset, detect())
+        res = t.process(frame)
+        self.lastcom = (0, 0, 0) if res['status'] else res['com'].copy()
+        self._devcom = self.lastcom
+        self.sync.update(fid=self.sync['fid'] + 1, com3D=res['com3D'], M=res['M'])
+        return res
+
+    def processVideo(self, device, max_frames=None):
+        """Headless processVideo (:235-294): every frame of `device` through the fused plan; returns the poses in mm, (frames, J, 3).
+        Stops at the end of a FileDevice, after max_frames, on `q`, or at a lost track (whose frame is not returned)."""
+        self.initNets()
+        device.start()
+        poses = []
+        times = []
+        while not self.stop.value and (max_frames is None or len(poses) < max_frames):
+            try:
+                ret, frame = device.getDepth()
+            except IndexError:
+                break
+            if ret is False:
+                print("Error while reading frame.")
+                break
+            start = time.time()
+            res = self.processFrame(frame)
+            times.append(time.time() - start)
+            if res['status']:
+                print("Track lost in frame {}.".format(len(poses)))
+                break
+            poses.append(res['pose'].copy())
+            if self.verbose is True:
+                print("{}ms frame".format(times[-1] * 1000.))
+        device.stop()
+        self.frame_times = times
+        J = self.poseNet.cfgParams.outputDim[1] // 3
+        return numpy.asarray(poses, numpy.float32).reshape(-1, J, 3)
+
+    # ---- state ------------------------------------------------------------------------------------------------------------
+    def processKey(self, key):
+        """The state changes of the reference's keys (:493-525); `s` toggles flags that only its cv2 windows read."""
+        if key == ord('q'):
+            self.stop.value = True
+        elif key == ord('h'):
+            self.hand.value = self.HAND_RIGHT if self.hand.value == self.HAND_LEFT else self.HAND_LEFT
+        elif key == ord('+'):
+            cfg = self.sync['config']
+            cfg['cube'] = tuple([lst + 10 for lst in list(cfg['cube'])])
+            self.sync.update(config=cfg)
+        elif key == ord('-'):
+            cfg = self.sync['config']
+            cfg['cube'] = tuple([lst - 10 for lst in list(cfg['cube'])])
+            self.sync.update(config=cfg)
+        elif key == ord('r'):
+            self.reset()
+        elif key == ord('i'):
+            raise NotImplementedError("hand-size calibration (STATE_INIT: estimateHandsize from cv2.findContours) is not built")
+        elif key == ord('t'):
+            self.tracking.value = not self.tracking.value
+        elif key == ord('s'):
+            self.show_crop = not self.show_crop
+            self.show_pose = not self.show_pose
+
+    def reset(self):
+        """Reset stateful parts (:527-536); the track starts again from init_com (or needs a new seed)."""
+        self.state.value = self.STATE_IDLE
+        self.sync.update(config=copy.deepcopy(self.initialconfig))
+        self.detection.value = self.DETECTOR_COM
+        self.lastcom = (0, 0, 0) if self.init_com is None else self.init_com.copy()

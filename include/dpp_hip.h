@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 12
+#define DPP_ABI_VERSION 13
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -474,6 +474,37 @@ int dpp_recrop(const float* crops, int B, int h, int w, const double* M, const d
  * negative width or height pastes nothing (the reference fails in cv2.resize; the host refuses it). */
 int dpp_inverse_crop(const float* crops, int B, int ch, int cw, const int* bounds, const float* zrange, int H, int W, int bilinear,
                      float nd_value, float background, int thresh_z, float* out, dpp_stream_t stream);
+
+/* ---- realtime tracking: a depth frame in, the followed hand's pose out (ABI v13) --------------------------------------------
+ * HandDetector.track / refineCoMIterative (handdetector.py:504-567) and RealtimeHandposePipeline.detect / estimatePose
+ * (realtimehandposepipeline.py:296-370) as device steps, so that one frame is one launch plan with its state (the last centre) on
+ * the device (hipdp/tracker.py).
+ * frame_range: min / max of every frame over many workgroups -> partial (dpp_frame_range_bytes(B) bytes); once per frame.
+ * crop_prepare_ranged: dpp_crop_prepare from those partials instead of a pass of its own over the frame: the same records and M.
+ *   A centre whose depth is isclose to 0 or that is not finite gets an EMPTY window (see track_refine) instead of a division by zero.
+ * track_refine: dpp_crop_refine's centre update (com' = joint3DToImg(net_out * cube_z/2 + jointImgTo3D(com_in)), centre-pixel
+ *   fallback from records_in) fused with the prepare of the final dsz x dsz crop around com' (records_out, M_out [B][9] or NULL,
+ *   com3d_out = jointImgTo3D(com')) and status [B]: 0 ok, 1 lost -- the new centre's depth is isclose to 0 (comToBounds' "CoM
+ *   ill-defined" branch) or not finite, or com_in already was; a lost frame gets an empty window (its crop is all fill value / zeros when normalised), M =
+ *   identity and com3D = 0.  (fx, fy, ux, uy, flip_y) is the importer's camera, (crop_fx, crop_fy) what HandDetector was given.
+ *   com_out may be com_in and records_out may be records_in.
+ * dpp_crop_warp_ex flag DPP_CROP_FLIP_X: output column x takes the value of column dsz - 1 - x (crop[:, ::-1], HAND_RIGHT).
+ * pose_finish: net_out [B][J][3] -> pose3d = signs(net_out) * cube_z / 2. + com3d (float32 step by step) and pose_img =
+ *   joints3DToImg(pose3d); flags: 1 HAND_RIGHT (x negated), 2 invX (column 1 negated, as the reference has it), 4 invY (column 0).
+ * refine_com_iterative: refineCoMIterative for B frames, all num_iter iterations in one launch (one workgroup per frame, float64
+ *   state); status [B] = 1 where a centre's depth became isclose to 0 (the host handles that frame). */
+#define DPP_CROP_FLIP_X 16
+size_t dpp_frame_range_bytes(int B);
+int dpp_frame_range(const float* frames, int B, int H, int W, float* partial, dpp_stream_t stream);
+int dpp_crop_prepare_ranged(const float* partial, int B, const float* com, const float* cube, double fx, double fy, int dsz, int stretch,
+                            void* records, float* M_out, dpp_stream_t stream);
+int dpp_track_refine(const float* frames, const void* records_in, int B, int H, int W, const float* com_in, const float* cube,
+                     const float* net_out, double fx, double fy, double ux, double uy, int flip_y, double crop_fx, double crop_fy, int dsz,
+                     float* com_out, float* com3d_out, void* records_out, float* M_out, int* status, dpp_stream_t stream);
+int dpp_pose_finish(const float* net_out, int B, int J, const float* cube, const float* com3d, double fx, double fy, double ux, double uy,
+                    int flip_y, int flags, float* pose3d, float* pose_img, dpp_stream_t stream);
+int dpp_refine_com_iterative(const float* frames, const float* partial, int B, int H, int W, const float* com_in, const float* cube,
+                             double fx, double fy, int num_iter, float* com_out, int* status, dpp_stream_t stream);
 
 /* ---- PCA prior set-up and evaluation on the device --------------------------------------------
  * pose_sample: HandDetector.sampleRandomPoses (/root/reference/src/util/handdetector.py:805-909) for n samples: sample i augments
