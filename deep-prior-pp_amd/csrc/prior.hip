@@ -10,30 +10,13 @@
 //
 // All of it is bandwidth-trivial (168 MB of samples); it is here so that the training script's set-up and evaluation need no host
 // pass over the data.  Reductions are two-level with fixed order (deterministic).  Compiled with -ffp-contract=off like
-// augment.hip: the sampling restates NumPy arithmetic that rounds after every operation.
-#include "dpp_common.h"
+// augment.hip and crop.hip: the sampling restates NumPy arithmetic that rounds after every operation.
+#include "geom.h"
 
 namespace {
 
-struct PoseCam {
-    double fx, fy, ux, uy;
-    int flip_y;
-};
-
-// joint3DToImg / jointImgTo3D on float32 arrays evaluated in float64 and stored as float32, as util.handdetector's host
-// restatement does (importers.py:80-119)
-__device__ __forceinline__ void ps_to_img(const PoseCam& c, double x, double y, double z, float out[3]) {
-    if (z == 0.0) { out[0] = (float)c.ux; out[1] = (float)c.uy; out[2] = 0.0f; return; }
-    out[0] = (float)(x / z * c.fx + c.ux);
-    out[1] = (float)(c.flip_y ? (c.uy - y / z * c.fy) : (y / z * c.fy + c.uy));
-    out[2] = (float)z;
-}
-__device__ __forceinline__ void ps_to_3d(const PoseCam& c, double u, double v, double d, float out[3]) {
-    out[0] = (float)((u - c.ux) * d / c.fx);
-    out[1] = (float)((c.flip_y ? (c.uy - v) : (v - c.uy)) * d / c.fy);
-    out[2] = (float)d;
-}
-
+// joint3DToImg / jointImgTo3D here are geom.h's toimg (f32in = false: float32 arrays evaluated in float64 and stored as float32, as
+// util.handdetector's host restatement does, importers.py:80-119) and to3d.
 constexpr int PM_NONE = 0, PM_COM = 1, PM_ROT = 2, PM_SC = 3, PM_ROTCOM = 4, PM_ROTCOMSC = 5;
 
 // one thread per (sample, joint)
@@ -42,7 +25,7 @@ __global__ __launch_bounds__(DPP_THREADS) void pose_sample_kernel(const float* _
                                                                   const int* __restrict__ ridx, const double* __restrict__ off,
                                                                   const double* __restrict__ sc, const double* __restrict__ rot,
                                                                   const double* __restrict__ rot3, long n,
-                                                                  PoseCam cam, float* __restrict__ out_poses, float* __restrict__ out_com,
+                                                                  AugCam cam, float* __restrict__ out_poses, float* __restrict__ out_com,
                                                                   float* __restrict__ out_cube) {
     const long t = (long)blockIdx.x * DPP_THREADS + threadIdx.x;
     if (t >= n * J) return;
@@ -105,7 +88,7 @@ __global__ __launch_bounds__(DPP_THREADS) void pose_sample_kernel(const float* _
         if (m == PM_ROT) {
 #pragma unroll
             for (int d = 0; d < 3; ++d) { q[d] = p[d] + ncom[d]; ref[d] = ncom[d]; }
-            ps_to_img(cam, com[0], com[1], com[2], ctr2);
+            toimg(cam, com[0], com[1], com[2], false, ctr2);
         } else {
 #pragma unroll
             for (int d = 0; d < 3; ++d) q[d] = (p[d] + com[d]) - ncom[d];
@@ -116,17 +99,17 @@ __global__ __launch_bounds__(DPP_THREADS) void pose_sample_kernel(const float* _
             }
 #pragma unroll
             for (int d = 0; d < 3; ++d) { q[d] = q[d] + com[d]; ref[d] = com[d]; }
-            ps_to_img(cam, ncom[0], ncom[1], ncom[2], ctr2);
+            toimg(cam, ncom[0], ncom[1], ncom[2], false, ctr2);
         }
         float j2[3], r2[3], b3[3];
-        ps_to_img(cam, q[0], q[1], q[2], j2);
+        toimg(cam, q[0], q[1], q[2], false, j2);
         const double alpha = rot[i] * 3.141592653589793 / 180.;
         const double ca = cos(alpha), sa = sin(alpha);
         const float pp0 = j2[0] - ctr2[0], pp1 = j2[1] - ctr2[1];
         r2[0] = (float)((double)pp0 * ca - (double)pp1 * sa) + ctr2[0];
         r2[1] = (float)((double)pp0 * sa + (double)pp1 * ca) + ctr2[1];
         r2[2] = j2[2];
-        ps_to_3d(cam, r2[0], r2[1], r2[2], b3);
+        to3d(cam, r2[0], r2[1], r2[2], b3);
 #pragma unroll
         for (int d = 0; d < 3; ++d) o[d] = (b3[d] - ref[d]) / half;
     }
@@ -395,7 +378,7 @@ static int pose_sample_launch(const float* base_poses, const float* base_com, co
                               dpp_stream_t stream) {
     if (!base_poses || !base_com || !base_cube || !mode || !ridx || !off || !sc || (!rot && !rot3) || !out_poses || n_base < 1 || J < 1 || n < 1)
         return DPP_E_BADARG;
-    PoseCam cam = {fx, fy, ux, uy, flip_y};
+    AugCam cam = {fx, fy, ux, uy, flip_y};
     const long total = n * J;
     DPP_LAUNCH(pose_sample_kernel, dim3((unsigned)((total + DPP_THREADS - 1) / DPP_THREADS)), dim3(DPP_THREADS), 0,
                static_cast<hipStream_t>(stream), base_poses, base_com, base_cube, J, mode, ridx, off, sc, rot, rot3, n, cam, out_poses, out_com,

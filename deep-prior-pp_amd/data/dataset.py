@@ -5,7 +5,7 @@ Training stacks of cropped sequences (class / method names of /root/reference/sr
 consume and the `(N, J, 3)` labels: undefined depth (0) becomes the far plane of the frame's cube, then
 `(d - com_z) / (cube_z / 2)` (or the [0, 1] form), labels `gt3Dcrop / (cube_z / 2)` (dataset.py:91-106).  The whole
 sequence is normalised as one float32 array expression (the device form of the same arithmetic is `crop_frames(...,
-normalize=True)`, csrc/augment.hip, which the importers' cascade path uses).
+normalize=True)`, csrc/crop.hip, which the importers' cascade path uses).
 Pinned by tests/golden/dataset.npz (the reference's own output on seeded sequences).
 """
 import numpy

@@ -3,7 +3,7 @@ HandDetector -- the augmentation slice of /root/reference/src/util/handdetector.
 :204-258, moveCoM / rotateHand / scaleHand / recropHand :678-803, sampleRandomPoses :805-909) and its crop helpers
 (bilinearResize :132-202, getInverseCrop / resizeCrop / applyCrop3D :298-380).
 
-The crop warps run on the MI355X through the fused augmentation kernels (csrc/augment.hip); this class keeps the
+The crop warps run on the MI355X through the crop kernels (csrc/crop.hip); this class keeps the
 reference's per-crop method signatures for callers and computes only the tiny 3x3 crop geometry on the host.
 cropArea3D (handdetector.py:382-490, docom=False: the call the importers make for every frame) runs on the device too;
 `crop_frames` is its batched form fused with Dataset.imgStackDepthOnly.  recropHand, resizeCrop, bilinearResize,
@@ -529,7 +529,7 @@ def crop_frames(frames, coms, cubes, fx, fy, dsize=128, normalize=True, nd_value
                 stretch=False, resize_method=HandDetector.RESIZE_CV2_NN, _flags=0, _fill=None, _pad=0.):
     """Batched cropArea3D (+ Dataset.imgStackDepthOnly when normalize): frames (B, H, W) raw depth in mm, coms (B, 3) crop
     centres in image coordinates, cubes (B, 3) in mm -> (crops (B, dsize, dsize) float32, M (B, 3, 3) float32[, coms]).
-    Two kernel launches for the whole batch (csrc/augment.hip: crop_prepare / crop_warp); docom=True re-centres every crop
+    Two kernel launches for the whole batch (csrc/crop.hip: crop_prepare / crop_warp); docom=True re-centres every crop
     on the centre of mass of its first window (two more launches), as handdetector.py:413-427 does; stretch=True resizes the
     window to dsize x dsize as it is (resizeCrop(cropped, dsize), the refinement net's input, :430).  resize_method
     RESIZE_BILINEAR resizes the window with bilinearResize (ND value nd_value) instead of nearest neighbour; a window

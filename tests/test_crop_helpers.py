@@ -1,4 +1,4 @@
-"""HandDetector crop helpers on the device (csrc/augment.hip, ABI v12): bilinearResize, resizeCrop, recropHand, getInverseCrop,
+"""HandDetector crop helpers on the device (csrc/crop.hip, ABI v12): bilinearResize, resizeCrop, recropHand, getInverseCrop,
 applyCrop3D and cropArea3D under resizeMethod = RESIZE_BILINEAR, and their batched forms.  The bilinear restatement
 (tests/crop_ref.py) is pinned to the reference's own functions by tests/golden/resize.npz; the kernels are held to it and to
 oracle/augment.py bit for bit.  Every body runs on the SIMT emulator (CPU tier) and on the MI355X (-m gpu)."""

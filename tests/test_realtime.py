@@ -1,4 +1,4 @@
-"""The realtime path (hipdp/tracker.py, util/realtimehandposepipeline.py, util/cameradevice.py; ABI v13 kernels of csrc/augment.hip):
+"""The realtime path (hipdp/tracker.py, util/realtimehandposepipeline.py, util/cameradevice.py; ABI v13 kernels of csrc/crop.hip):
 a depth frame in, the tracked hand's pose out, one device plan per frame.  Kernels against tests/track_ref.py (pinned to the
 reference by tests/golden/track.npz) and against the crop kernels that are already pinned; the tracker plan stage by stage, free
 running against the host-carried per-call API, its structure, a lost track, and the class API on an on-disk sequence.  Every kernel /
