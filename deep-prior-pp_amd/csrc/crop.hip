@@ -5,7 +5,8 @@
 //   realtime tracking       frame_range, crop_prepare_ranged, track_refine, pose_finish, refine_com_iterative (HandDetector.track,
 //                           RealtimeHandposePipeline; ABI v13)
 // They share CropRec, crop_geometry and crop_window_value; each section below names the reference lines it restates.  The training-time
-// augmentation of finished crops is augment.hip; the camera, bounds and warp-coordinate arithmetic both units use is geom.h.
+// augmentation of finished crops is augment.hip; finding the hand in a whole frame (connected components) is components.hip; the
+// camera, bounds and warp-coordinate arithmetic and the workgroup reductions these units share are geom.h.
 // Compiled with -ffp-contract=off like augment.hip: the reference's NumPy/OpenCV arithmetic rounds after every operation, so no fused
 // multiply-add may be formed here (pixel coordinates at rounding boundaries would move).
 #include "geom.h"
@@ -149,19 +150,6 @@ __device__ __forceinline__ void com_window_sums(const float* __restrict__ f, int
         }
         sx += rx; sd += rs; cnt += rc; sy += rc * (double)y;
     }
-}
-
-// The four sums over the workgroup: wave shuffle, then LDS, then thread 0 -- the only thread that gets `true` and the totals.
-__device__ __forceinline__ bool com_block_sums(double& sx, double& sy, double& sd, double& cnt, double (*s_red)[DPP_THREADS / DPP_WAVE]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int o = 32; o > 0; o >>= 1) {
-        sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sd += __shfl_xor(sd, o); cnt += __shfl_xor(cnt, o);
-    }
-    if (lane == 0) { s_red[0][wave] = sx; s_red[1][wave] = sy; s_red[2][wave] = sd; s_red[3][wave] = cnt; }
-    __syncthreads();
-    if (tid != 0) return false;
-    for (int w = 1; w < DPP_THREADS / DPP_WAVE; ++w) { sx += s_red[0][w]; sy += s_red[1][w]; sd += s_red[2][w]; cnt += s_red[3][w]; }
-    return true;
 }
 
 // One band of window rows: its sums -> partial[b][band][4].
@@ -436,8 +424,6 @@ __global__ __launch_bounds__(DPP_THREADS) void inverse_crop_kernel(const float* 
 // ---- realtime tracking (ABI v13): HandDetector.track + RealtimeHandposePipeline.detect / estimatePose as device steps -----------
 // /root/reference/src/util/handdetector.py:504-567, /root/reference/src/util/realtimehandposepipeline.py:296-370.  One frame is one
 // chain of dependent launches, so what counts is their number and that none of them walks the frame with a single workgroup.
-constexpr int FR_BANDS = 64;            // workgroups per frame of the depth-range pass (= one wave of partials to reduce)
-
 // min / max of frame b over FR_BANDS workgroups -> partial[b][band][2].  Interleaved 16-byte loads, four in flight per thread; a
 // lane past the end re-reads its first element (harmless for min / max).  Every band writes its partial, also an empty one.
 __global__ __launch_bounds__(DPP_THREADS) void frame_range_kernel(const float* __restrict__ frames, int H, int W, float* __restrict__ partial) {
@@ -470,13 +456,6 @@ __global__ __launch_bounds__(DPP_THREADS) void frame_range_kernel(const float* _
     if (!block_minmax(mn, mx, s_mn, s_mx)) return;
     partial[((size_t)b * FR_BANDS + band) * 2] = mn;
     partial[((size_t)b * FR_BANDS + band) * 2 + 1] = mx;
-}
-
-// (min, max) of frame b from its FR_BANDS partials: one wave, lane = band; every lane returns the result
-__device__ __forceinline__ void frame_range_reduce(const float* __restrict__ partial, int b, int lane, float& mn, float& mx) {
-    mn = partial[((size_t)b * FR_BANDS + lane) * 2];
-    mx = partial[((size_t)b * FR_BANDS + lane) * 2 + 1];
-    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
 }
 
 // a centre that cannot be cropped around: its depth is numpy.isclose to 0 (comToBounds' "CoM ill-defined" test) or it is not finite

@@ -1,4 +1,5 @@
-// geom.h -- the camera, crop-bounds and warp-coordinate arithmetic that augment.hip, crop.hip and prior.hip share.
+// geom.h -- the camera, crop-bounds and warp-coordinate arithmetic that augment.hip, crop.hip, components.hip and prior.hip share,
+// and the workgroup reductions of the whole-frame kernels (crop.hip, components.hip).
 //
 // Everything here restates NumPy / OpenCV 2.4 arithmetic that rounds after every operation and is pinned bit for bit to the reference,
 // so every unit that includes this header is compiled with -ffp-contract=off (csrc/Makefile names them).  One body per rule: a fix
@@ -113,5 +114,29 @@ __device__ __forceinline__ float z_threshold(float v, float zlo, float zhi) {
 
 // numpy.isclose(v, ref) of a float32 pixel against recropHand's nv_val (handdetector.py:782-803; NumPy 1: the comparison is float64)
 __device__ __forceinline__ bool is_close(float v, double ref) { return fabs((double)v - ref) <= 1e-8 + 1e-5 * fabs(ref); }
+
+
+// ---- workgroup reductions that crop.hip and components.hip share ---------------------------------------------------------------
+// The four sums over the workgroup: wave shuffle, then LDS, then thread 0 -- the only thread that gets `true` and the totals.
+__device__ __forceinline__ bool com_block_sums(double& sx, double& sy, double& sd, double& cnt, double (*s_red)[DPP_THREADS / DPP_WAVE]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int o = 32; o > 0; o >>= 1) {
+        sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sd += __shfl_xor(sd, o); cnt += __shfl_xor(cnt, o);
+    }
+    if (lane == 0) { s_red[0][wave] = sx; s_red[1][wave] = sy; s_red[2][wave] = sd; s_red[3][wave] = cnt; }
+    __syncthreads();
+    if (tid != 0) return false;
+    for (int w = 1; w < DPP_THREADS / DPP_WAVE; ++w) { sx += s_red[0][w]; sy += s_red[1][w]; sd += s_red[2][w]; cnt += s_red[3][w]; }
+    return true;
+}
+
+constexpr int FR_BANDS = 64;            // workgroups per frame of the depth-range pass (= one wave of partials to reduce)
+
+// (min, max) of frame b from its FR_BANDS partials: one wave, lane = band; every lane returns the result
+__device__ __forceinline__ void frame_range_reduce(const float* __restrict__ partial, int b, int lane, float& mn, float& mx) {
+    mn = partial[((size_t)b * FR_BANDS + lane) * 2];
+    mx = partial[((size_t)b * FR_BANDS + lane) * 2 + 1];
+    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+}
 
 }  // namespace

@@ -764,6 +764,67 @@ def refine_com_iterative(rt, frames, partial, B, H, W, com_in, cube, fx, fy, num
                   (frames, partial, com_in, cube, com_out, status), name)
 
 
+DETECT_FOUND, DETECT_NO_SIZE = 1, 2          # DPP_DETECT_*: status bits of detect_seed / hand_size
+KEY_BACKGROUND = 255
+# one record of dpp_label_components' statistics (include/dpp_hip.h), meaningful at roots
+COMPONENT_STAT = np.dtype([('count', np.int32), ('ixmin', np.int32), ('xmax', np.int32), ('iymin', np.int32), ('ymax', np.int32),
+                           ('pad', np.int32), ('sum_x', np.uint64), ('sum_y', np.uint64)])
+
+
+class ComponentWorkspace(object):
+    """What labelling B frames of H x W needs on the device, allocated once: keys, the union-find parents, labels, the per-root
+    statistics and the selection words (cleared by slab_keys / mask_keys inside the plan)."""
+
+    def __init__(self, rt, B, H, W, stats=True):
+        lib = rt.lib
+        nb = int(lib.dpp_label_workspace_bytes(B, H, W))
+        if nb == 0 or int(lib.dpp_component_stats_bytes(1, 1, 1)) != COMPONENT_STAT.itemsize:
+            raise DppError("component labelling cannot index %d frames of %d x %d" % (B, H, W))
+        self.B, self.H, self.W = B, H, W
+        self.keys = rt.alloc((B, H, W), np.uint8, zero=False)
+        self.parent = rt.alloc(nb // 4, np.int32, zero=False)
+        self.labels = rt.alloc((B, H, W), np.int32, zero=False)
+        self.stats = rt.alloc(int(lib.dpp_component_stats_bytes(B, H, W)), np.uint8, zero=False) if stats else None
+        self.state = rt.alloc(int(lib.dpp_detect_state_bytes(B)) // 8, np.int64)
+
+
+def slab_keys(rt, frames, partial, ws, name='slab_keys'):
+    """dpp_slab_keys: detect's 20 depth slabs as one uint8 key per pixel, from frame_range's partials."""
+    B, H, W = ws.B, ws.H, ws.W
+    return Launch(rt.lib.dpp_slab_keys, (frames.ptr, partial.ptr, B, H, W, ws.keys.ptr, ws.state.ptr), (frames, partial, ws), name,
+                  dict(kernel='slab_keys', flops=4.0 * B * H * W, bytes=5.0 * B * H * W))
+
+
+def mask_keys(rt, frames, com, cube, ws, name='mask_keys'):
+    """dpp_mask_keys: the hand's depth range com_z -+ cube_z / 2 as a binary key."""
+    B, H, W = ws.B, ws.H, ws.W
+    return Launch(rt.lib.dpp_mask_keys, (frames.ptr, B, H, W, com.ptr, cube.ptr, ws.keys.ptr, ws.state.ptr), (frames, com, cube, ws), name,
+                  dict(kernel='mask_keys', flops=4.0 * B * H * W, bytes=5.0 * B * H * W))
+
+
+def label_components(rt, ws, stats=True, name='label_components'):
+    """dpp_label_components on the workspace's keys: canonical 8-connected labels (+ per-root statistics)."""
+    B, H, W = ws.B, ws.H, ws.W
+    st = ws.stats if stats else None
+    return Launch(rt.lib.dpp_label_components, (ws.keys.ptr, B, H, W, ws.parent.ptr, ws.labels.ptr, _p(st)), (ws,), name, kernels=4 if st else 3)
+
+
+def detect_seed(rt, frames, partial, ws, com_out, status, name='detect_seed'):
+    """dpp_detect_seed: the nearest component of more than 200 px and the centre of mass of its window."""
+    B, H, W = ws.B, ws.H, ws.W
+    return Launch(rt.lib.dpp_detect_seed, (frames.ptr, partial.ptr, ws.keys.ptr, ws.labels.ptr, ws.stats.ptr, B, H, W, ws.state.ptr, com_out.ptr,
+                                           status.ptr),
+                  (frames, partial, ws, com_out, status), name, kernels=2)
+
+
+def hand_size(rt, ws, com, cube_in, fx, fy, cube_out, status, tol=0.0, name='hand_size'):
+    """dpp_hand_size: estimateHandsize from the bounding box of the largest labelled component."""
+    B, H, W = ws.B, ws.H, ws.W
+    return Launch(rt.lib.dpp_hand_size, (ws.keys.ptr, ws.labels.ptr, ws.stats.ptr, B, H, W, ws.state.ptr, com.ptr, cube_in.ptr, float(fx), float(fy),
+                                         float(tol), cube_out.ptr, status.ptr),
+                  (ws, com, cube_in, cube_out, status), name, kernels=2)
+
+
 def copy2d(rt, src, lds, dst, ldd, rows, cols, relu=False, name='copy2d'):
     return Launch(rt.lib.dpp_copy2d, (src.ptr, lds, dst.ptr, ldd, rows, cols, int(bool(relu))), (src, dst), name)
 

@@ -19,10 +19,15 @@ track() has no calculateCoM re-centring: this is hipdp/cascade.py's chain minus 
 cropped around the centre found in frame t - 1), so the centre never leaves the device between frames: the host uploads a frame,
 runs the plan and downloads one small result block.
 
+ACQUIRING the hand.  The plan above follows a hand from a centre somebody supplied.  acquire(frame) finds one: the detector plan of
+hipdp/detect.py (connected components: the nearest object of more than 200 px, its window's centre of mass, refineCoMIterative(5))
+runs on the tracker's own frame buffer and depth-range partials and writes its centre straight into the device state; the host
+reads back the tracker's one result block (centre, seed, cube, found).  A process(frame) that follows gives the bits of reset(that centre) + process(frame).
+
 LOST frames.  Where the refined centre's depth is numpy.isclose to 0 the reference takes comToBounds' "CoM ill-defined" branch
 (handdetector.py:204-213) and crops the MIDDLE of the frame; no device kernel implements that branch.  track_refine flags such a
 frame instead (status 1), gives it an empty crop window (an all-zero net input, finite outputs), and the tracker refuses further
-frames until reset(com).
+frames until reset(com) or a successful acquire(frame).
 """
 import numpy as np
 
@@ -97,7 +102,7 @@ class HandTracker(object):
         self.rec = rt.alloc(rt.lib.dpp_crop_record_bytes(), np.uint8)
         self.cube = rt.alloc((1, 3), f32)
         # everything the host reads per frame is ONE block: pose (mm), pose in image coordinates, centre (= the state), com3D, M, status
-        self.res = rt.alloc(2 * J3 + 16, f32)
+        self.res = rt.alloc(2 * J3 + 16 + 8, f32)                              # (+ the detector's seed / cube / status words: acquire)
         self.pose3d, self.pose_img = self.res.view(0, (1, self.J, 3)), self.res.view(J3, (1, self.J, 3))
         self.com, self.com3d = self.res.view(2 * J3, (1, 3)), self.res.view(2 * J3 + 3, (1, 3))
         self.M, self.status = self.res.view(2 * J3 + 6, (1, 9)), self.res.view(2 * J3 + 15, (1,), np.int32)
@@ -106,6 +111,8 @@ class HandTracker(object):
         self.set_hand(hand_right)
         self.set_inv(invX, invY)
         self._plans = {}
+        self._detector = None
+        self._slot = 0                                                         # frame buffer of the last frame
         self.lost = True                                                       # no centre yet
         self.set_cube(cube)
         self.runs = 0
@@ -118,6 +125,39 @@ class HandTracker(object):
             raise ValueError("reset needs a centre with a depth: %r" % (com,))
         self.com.set(com)
         self.lost = False
+
+    def detector(self):
+        """The whole-frame detector on this tracker's buffers: frame slot 0, the depth-range partials, the centre (its output) and the cube."""
+        if self._detector is None:
+            from .detect import FrameDetector
+            self._detector = FrameDetector(self.rt, self.H, self.W, self.fx, self.fy, 1, frames=self.frames[0], partial=self.partial,
+                                           com=self.com, cube=self.cube, res=self.res.view(2 * self.J * 3 + 16, (8,)))
+        return self._detector
+
+    def acquire(self, frame, do_hand_size=False):
+        """Find the hand in `frame` and start (again) from it: one upload, the detector plan, one download of the tracker's result block.  Returns dict(com [3]
+        image coordinates, cube [3] -- measured with do_hand_size, else the tracker's; the tracker's own cube is not changed --, found).
+        Not found: the centre is (0, 0, 0) and the track is lost."""
+        frame = self._frame(frame)
+        det = self.detector()
+        self.frames[0].set(frame)
+        self._slot = 0
+        det.plan(do_hand_size).run(self.rt)
+        self.rt.synchronize()
+        res, J3 = self.res.get(), self.J * 3                                    # the tracker's block: centre and detector words together
+        coms, cubes, found, _, _ = det.parse(res[2 * J3 + 16:], res[2 * J3:2 * J3 + 3], None if do_hand_size else self.cube_host)
+        ok = bool(found[0]) and bool(np.all(np.isfinite(coms[0]))) and not np.isclose(coms[0][2], 0.)
+        self.lost = not ok
+        return dict(com=coms[0], cube=cubes[0], found=ok)
+
+    def hand_size(self, tol=0.0):
+        """The hand's cube around the current centre in the frame last handed to process() or acquire():
+        HandDetector.estimateHandsizeComponents on the device state.  An empty depth range gives the tracker's cube.  After
+        process_sequence the last frame may sit in the other frame buffer, which the detector does not see: RuntimeError."""
+        if self._slot != 0:
+            raise RuntimeError("hand_size measures the frame of the last process() / acquire(); the last frame came through process_sequence")
+        cubes, _ = self.detector().hand_size(tol=tol)
+        return cubes[0]
 
     def set_cube(self, cube):
         cube = np.asarray(cube, np.float32).reshape(3)
@@ -165,6 +205,9 @@ class HandTracker(object):
     def _check(self, frame):
         if self.lost:
             raise RuntimeError("the track is lost (or was never started): call reset(com) with a new centre")
+        return self._frame(frame)
+
+    def _frame(self, frame):
         frame = np.asarray(frame, np.float32)
         if frame.shape != (self.H, self.W):
             raise ValueError("frame shape %s, expected %s" % (frame.shape, (self.H, self.W)))
@@ -176,6 +219,7 @@ class HandTracker(object):
         status LOST: see the module docstring; the other entries are finite but meaningless and the tracker needs reset(com)."""
         frame = self._check(frame)
         self.frames[0].set(frame)
+        self._slot = 0
         self.plan(0).run(self.rt)
         self.runs += 1
         self.rt.synchronize()
@@ -204,6 +248,7 @@ class HandTracker(object):
             else:
                 self.frames[k].set(frame)
             self.plan(k).run(rt)
+            self._slot = k
             self.runs += 1
             free[k] = rt.record_event() if staged else None
             handle = (rt.read_async(self.res), rt.read_async(self.crop) if return_crops else None)

@@ -10,8 +10,11 @@ cropArea3D (handdetector.py:382-490, docom=False: the call the importers make fo
 getInverseCrop and applyCrop3D are device-backed as well, with batched forms `recrop_crops`, `resize_crops` and
 `inverse_crops` (one launch per batch each).  CoM refinement by a ScaleNet (refineCoM, handdetector.py:634-676) goes
 through the net's computeOutput.  track (handdetector.py:504-544, doHandSize=False) runs on the device with the kernels of the
-realtime tracker (hipdp/tracker.py), refineCoMIterative has a batched device form (`refine_com_iterative`); whole-frame detection
-(detect: cv2 contour analysis) and hand-size estimation are not built.
+realtime tracker (hipdp/tracker.py), refineCoMIterative has a batched device form (`refine_com_iterative`).  Whole-frame detection
+and hand-size estimation as the reference has them (detect, estimateHandsize: cv2 contour analysis) are not built; what they are for
+-- the nearest sufficiently large connected object, and the bounding box of the largest object in the hand's depth range -- is, by
+8-connected component labelling on the device (csrc/components.hip, hipdp/detect.py): `label_components`, `find_hands`,
+HandDetector.detectComponents and estimateHandsizeComponents.
 
 resizeMethod is honoured where the reference reads it: RESIZE_CV2_NN (the default) is cv2's nearest-neighbour resize,
 RESIZE_BILINEAR the reference's own ND-aware bilinearResize.  RESIZE_CV2_LINEAR (cv2 INTER_LINEAR) is not built: the new
@@ -451,6 +454,47 @@ class HandDetector(object):
         raise NotImplementedError("hand detection (cv2.findContours slab analysis, handdetector.py:569-632) is not built: it cannot be pinned "
                                   "without OpenCV; seed the track with a known centre (RealtimeHandposePipeline(init_com=...) or reset(com))")
 
+    _COMPONENT_DEVIATIONS = """Deviations from the reference, which walks cv2.findContours' contour list:
+          1. a component's pixel count stands in for cv2.contourArea (the > 200 threshold, and "largest");
+          2. among the components of the winning slab the raster-first one (smallest y * W + x) wins, not cv2's contour order;
+          3. a depth exactly on a slab boundary belongs to the nearer slab only (the reference keeps it in both)."""
+
+    def detectComponents(self, size=(250, 250, 250), doHandSize=True):
+        """Detect the hand as the closest object to the camera, by connected components on the device: the depth range in 20 slabs,
+        nearest first; the first slab with an 8-connected component of more than 200 px; the centre of mass of the +-100 px window
+        around that component's centroid inside the slab; refineCoMIterative(com, 5, size); with doHandSize the cube from the bounding
+        box of the largest component of the depth range com_z -+ size_z / 2 (estimateHandsizeComponents).  Returns (com, size) with
+        detect's convention (handdetector.py:569-632): no hand gives ((0, 0, 0), size).
+        """
+        coms, cubes, found = find_hands(numpy.asarray(self.dpt, numpy.float32)[None], numpy.asarray(size, numpy.float32)[None], self.fx,
+                                        self.fy, do_hand_size=doHandSize is True)
+        if not found[0]:
+            return numpy.array((0, 0, 0), numpy.float64), size
+        if doHandSize is True:
+            return coms[0].astype(numpy.float64), tuple(float(c) for c in cubes[0])
+        return coms[0].astype(numpy.float64), size
+    detectComponents.__doc__ += "\n        " + _COMPONENT_DEVIATIONS
+
+    def estimateHandsizeComponents(self, com, cube=(250, 250, 250), tol=0.):
+        """estimateHandsize (handdetector.py:911-937) without a contour argument: the bounding box is that of the largest 8-connected
+        component of the pixels with com_z - cube_z / 2 <= d <= com_z + cube_z / 2 (detect's part_ref, :616-624), measured on the
+        device.  Returns the metric cube (x, y, z); an empty depth range returns `cube` unchanged.
+        """
+        from hipdp import ops
+        from hipdp.runtime import default_runtime
+        rt = default_runtime()
+        frame = numpy.ascontiguousarray(self.dpt, numpy.float32)
+        H, W = frame.shape
+        det = _detector(rt, H, W, self.fx, self.fy, 1)
+        det.frames.set(frame[None])
+        det.com.set(numpy.asarray(com, numpy.float32).reshape(1, 3))
+        det.cube.set(numpy.asarray(cube, numpy.float32).reshape(1, 3))
+        cubes, status = det.hand_size(tol=tol)
+        if status[0] & ops.DETECT_NO_SIZE:
+            return tuple(cube)
+        return tuple(float(c) for c in cubes[0])
+    estimateHandsizeComponents.__doc__ += "\n        " + _COMPONENT_DEVIATIONS
+
     def track(self, com, size=(250, 250, 250), dsize=(128, 128), doHandSize=True):
         """Follow the hand from the previous frame's centre `com` (handdetector.py:504-544): the window of the cube around com,
         resized to dsize as it is, goes through the refinement net; returns (new centre in image coordinates, size).  One frame
@@ -674,6 +718,73 @@ def inverse_crops(crops, frame_shape, bounds, thresh_z=True, background=0., meth
     ops.inverse_crop(rt, src, B, ch, cw, bd, H, W, out, bilinear=bilinear, nd_value=nd_value, background=background, zrange=zr)(rt.stream)
     rt.synchronize()
     return out.get()
+
+
+_DEVICE_CACHE = {}                 # (kind, id(runtime), shape, ...) -> FrameDetector / ComponentWorkspace: allocated once per shape
+_DEVICE_CACHE_MAX = 4
+
+
+def _cached(key, make):
+    """The device workspaces of the batched detection calls are large (40 bytes per pixel of statistics): one per shape is kept and
+    used again, the oldest of more than a few dropped."""
+    if key not in _DEVICE_CACHE:
+        while len(_DEVICE_CACHE) >= _DEVICE_CACHE_MAX:
+            _DEVICE_CACHE.pop(next(iter(_DEVICE_CACHE)))
+        _DEVICE_CACHE[key] = (make(), key[1])
+    return _DEVICE_CACHE[key][0]
+
+
+def label_components(keys, runtime=None, return_stats=False):
+    """8-connected component labelling on the device: keys (B, H, W) uint8, 255 = background -> labels (B, H, W) int32, the smallest
+    linear index y * W + x of the pixel's component of equal key, -1 for background.  With return_stats also a dict of arrays, one
+    entry per component ordered by (frame, root): frame, root, key, count, xmin, xmax, ymin, ymax, sum_x, sum_y (integers, exact)."""
+    from hipdp import ops
+    from hipdp.runtime import default_runtime
+    rt = runtime or default_runtime()
+    keys = numpy.ascontiguousarray(keys, numpy.uint8)
+    if keys.ndim != 3:
+        raise ValueError("keys must be (B, H, W)")
+    B, H, W = keys.shape
+    ws = _cached(('labels', rt, B, H, W, bool(return_stats)), lambda: ops.ComponentWorkspace(rt, B, H, W, stats=return_stats))
+    ws.keys.set(keys)
+    ops.label_components(rt, ws, stats=return_stats)(rt.stream)
+    rt.synchronize()
+    labels = ws.labels.get().reshape(B, H, W)
+    if not return_stats:
+        return labels
+    rec = ws.stats.get().view(ops.COMPONENT_STAT).reshape(B, H * W)
+    fb, root = numpy.nonzero(labels.reshape(B, H * W) == numpy.arange(H * W, dtype=numpy.int32)[None])
+    r = rec[fb, root]
+    stats = dict(frame=fb.astype(numpy.int32), root=root.astype(numpy.int32), key=keys.reshape(B, H * W)[fb, root], count=r['count'].copy(),
+                 xmin=~r['ixmin'], xmax=r['xmax'].copy(), ymin=~r['iymin'], ymax=r['ymax'].copy(),
+                 sum_x=r['sum_x'].astype(numpy.int64), sum_y=r['sum_y'].astype(numpy.int64))
+    return labels, stats
+
+
+def _detector(rt, H, W, fx, fy, B):
+    from hipdp import detect
+    return _cached(('detector', rt, B, H, W, abs(float(fx)), abs(float(fy))), lambda: detect.FrameDetector(rt, H, W, fx, fy, B))
+
+
+def find_hands(frames, cubes, fx, fy, do_hand_size=False, runtime=None, return_seed=False, chunk=8):
+    """Batched HandDetector.detectComponents: frames (B, H, W) raw depth in mm, cubes (B, 3) -> (coms (B, 3) float32 in image
+    coordinates, cubes (B, 3) float32, found (B,) bool).  One device plan per chunk of frames (hipdp.detect.FrameDetector, kept
+    per frame shape and used again by later calls): depth
+    range, slab keys, labelling, seed, refineCoMIterative(5) and, with do_hand_size, the hand's cube; a frame without a hand gets
+    com (0, 0, 0) and its input cube.  return_seed adds the centres before the refinement."""
+    from hipdp.runtime import default_runtime
+    rt = runtime or default_runtime()
+    frames = numpy.ascontiguousarray(frames, numpy.float32)
+    if frames.ndim != 3:
+        raise ValueError("frames must be (B, H, W)")
+    B, H, W = frames.shape
+    cubes = numpy.ascontiguousarray(cubes, numpy.float32).reshape(B, 3)
+    coms, sizes, found, seeds = (numpy.zeros((B, 3), numpy.float32), cubes.copy(), numpy.zeros(B, bool), numpy.zeros((B, 3), numpy.float32))
+    for i0 in range(0, B, chunk):
+        n = min(chunk, B - i0)
+        det = _detector(rt, H, W, fx, fy, n)
+        coms[i0:i0 + n], sizes[i0:i0 + n], found[i0:i0 + n], seeds[i0:i0 + n], _ = det.run(frames[i0:i0 + n], cubes[i0:i0 + n], do_hand_size)
+    return (coms, sizes, found, seeds) if return_seed else (coms, sizes, found)
 
 
 def refine_com_iterative(frames, coms, cubes, fx, fy, num_iter, runtime=None, return_status=False):

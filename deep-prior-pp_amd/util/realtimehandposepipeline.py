@@ -7,16 +7,20 @@ changes, reset, and a headless processVideo(device) that returns the poses in mm
 (hipdp.tracker.HandTracker).  detect() + estimatePose() called separately go through the per-call API (HandDetector.track,
 cropArea3D, computeOutput) and give the same numbers as the fused plan.
 
-Not built: HandDetector.detect (contour analysis of depth slabs with cv2.findContours, it cannot be pinned without OpenCV) and with
-it the detection mode of detect(); hand-size calibration (STATE_INIT, estimateHandsize: cv2 contours as well); show, addStatusBar
-and the cv2 windows; the producer / consumer processes of processVideoThreaded (their shared state is plain attributes here:
-`.value` holders instead of multiprocessing.Value, a dict instead of Manager().dict()).
+Not built: HandDetector.detect as the reference has it (contour analysis of depth slabs with cv2.findContours, it cannot be pinned
+without OpenCV) and with it the detection mode of detect(); the key-driven hand-size calibration (STATE_INIT, estimateHandsize: cv2
+contours as well); show, addStatusBar and the cv2 windows; the producer / consumer processes of processVideoThreaded (their shared
+state is plain attributes here: `.value` holders instead of multiprocessing.Value, a dict instead of Manager().dict()).
 
-Because detect is missing, the first frame needs a SEED: init_com= (image coordinates, z in mm, e.g. a dataset's annotation of the
-first frame), which also switches tracking on; or seed_com=True, an explicitly NON-reference seed -- the centre of mass of the whole
-range-limited frame (what cropArea3D(com=None) uses) refined by refineCoMIterative(com, 5, cube), the step the reference's detect
-applies to its own seed (handdetector.py:610).  With tracking off, or an all-zero last centre and no seed, detect raises the
-NotImplementedError of HandDetector.detect.
+The first frame needs a SEED: init_com= (image coordinates, z in mm, e.g. a dataset's annotation of the first frame), which also
+switches tracking on; or seed_detect=True, whole-frame detection by connected components on the device
+(HandDetector.detectComponents / HandTracker.acquire: the nearest 8-connected object of more than 200 px, the centre of mass of its
+window, refineCoMIterative(com, 5, cube) -- detect's steps with component labelling in the place of cv2's contours, see
+util.handdetector for the three deviations), used again after every LOST frame; or seed_com=True, an explicitly NON-reference seed
+-- the centre of mass of the whole range-limited frame (what cropArea3D(com=None) uses) refined the same way.  seed_detect takes
+precedence over seed_com.  A frame in which seed_detect finds no hand (and seed_com, if set, nothing either) is answered like a LOST
+one and the next frame is searched again.  With tracking off, or an all-zero last centre and no seed at all, detect raises the
+NotImplementedError of HandDetector.detect.  calibrateHandsize(device) is the headless counterpart of STATE_INIT (:312-324) on the component hand size.
 
 A LOST track (the tracked centre's depth is close to 0: the reference would crop the middle of the frame through comToBounds'
 "CoM ill-defined" branch, which is not built) gives a zero crop, eye(3) and a zero com3D -- the answer of :326-327 -- and clears
@@ -40,6 +44,10 @@ class _Value(object):
         self.value = value
 
 
+class _NoHand(Exception):
+    """seed_detect looked at a frame and found no hand (and there is no other seed): the frame is treated like a lost one."""
+
+
 class RealtimeHandposePipeline(object):
     """Realtime pipeline for handpose estimation"""
 
@@ -55,7 +63,7 @@ class RealtimeHandposePipeline(object):
     # different detectors
     DETECTOR_COM = 0
 
-    def __init__(self, poseNet, config, di, verbose=False, comrefNet=None, init_com=None, seed_com=False):
+    def __init__(self, poseNet, config, di, verbose=False, comrefNet=None, init_com=None, seed_com=False, seed_detect=False):
         """
         :param poseNet:   network for pose estimation (a built net, or PoseRegNetParams / ResNetParams, with loadFile or not)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=])
@@ -63,6 +71,8 @@ class RealtimeHandposePipeline(object):
         :param comrefNet: refinement network of the hand centre (a built net or ScaleNetParams)
         :param init_com:  seed of the track, image coordinates (switches tracking on)
         :param seed_com:  NON-reference seed from the frame's own centre of mass (module docstring)
+        :param seed_detect: seed, and re-seed after a lost frame, by connected-component detection on the device (switches tracking on;
+                          takes precedence over seed_com)
         """
         self.importer = di
         self.poseNet = poseNet
@@ -77,9 +87,10 @@ class RealtimeHandposePipeline(object):
         self.detection = _Value(self.DETECTOR_COM)
         self.handsizes = []
         self.numinitframes = 50
-        self.tracking = _Value(init_com is not None or bool(seed_com))
+        self.tracking = _Value(init_com is not None or bool(seed_com) or bool(seed_detect))
         self.init_com = None if init_com is None else numpy.asarray(init_com, numpy.float32).copy()
         self.seed_com = bool(seed_com)
+        self.seed_detect = bool(seed_detect)
         self.lastcom = (0, 0, 0) if init_com is None else self.init_com.copy()
         self.show_pose = False
         self.show_crop = False
@@ -126,16 +137,29 @@ class RealtimeHandposePipeline(object):
         cube = numpy.asarray(cfg['cube'], numpy.float32)
         return refine_com_iterative(numpy.asarray(frame, numpy.float32)[None], com[None], cube[None], cfg['fx'], cfg['fy'], 5)[0]
 
-    def _need_seed(self, frame):
+    def _detect_seed(self, frame):
+        """seed_detect for the per-call API: HandDetector.detectComponents' centre (doHandSize=False), zeros where there is no hand."""
+        from util.handdetector import find_hands
+        cfg = self.sync['config']
+        coms, _, found = find_hands(numpy.asarray(frame, numpy.float32)[None], numpy.asarray(cfg['cube'], numpy.float32)[None], cfg['fx'], cfg['fy'])
+        return coms[0] if found[0] else numpy.zeros(3, numpy.float32)
+
+    def _need_seed(self, frame, detect_tried=False):
         """The centre to track from, seeding it where there is none; without a seed: HandDetector.detect's NotImplementedError."""
         if self.state.value == self.STATE_INIT:
             raise NotImplementedError("hand-size calibration (STATE_INIT: estimateHandsize from cv2.findContours) is not built")
         if self.tracking.value and not numpy.allclose(self.lastcom, 0):
             return numpy.asarray(self.lastcom, numpy.float32)
+        if self.tracking.value and self.seed_detect and not detect_tried:
+            com = self._detect_seed(frame)
+            if not numpy.isclose(com[2], 0.):
+                return com
         if self.tracking.value and self.seed_com:
             com = self._seed(frame)
             if not numpy.isclose(com[2], 0.):
                 return com
+        if self.tracking.value and self.seed_detect:
+            raise _NoHand()                            # nothing in view: not an error, the next frame is looked at again
         cfg = self.sync['config']
         return HandDetector(numpy.zeros((2, 2), numpy.float32), cfg['fx'], cfg['fy']).detect(size=cfg['cube'], doHandSize=False)
 
@@ -143,7 +167,12 @@ class RealtimeHandposePipeline(object):
     def detect(self, frame):
         """Follow the hand into `frame` (:296-337, tracking mode): (normalised crop, transformation M, com3D)."""
         cfg = self.sync['config']
-        lastcom = self._need_seed(frame)
+        try:
+            lastcom = self._need_seed(frame)
+        except _NoHand:                                # the answer of :326-327, as for a lost track
+            self.lastcom = (0, 0, 0)
+            self.handsizes = []
+            return numpy.zeros(self._pose_dsize()[::-1], dtype='float32'), numpy.eye(3), numpy.zeros(3, numpy.float32)
         hd = HandDetector(frame, cfg['fx'], cfg['fy'], importer=self.importer, refineNet=self.comrefNet)
         loc, handsz = hd.track(lastcom, cfg['cube'], dsize=self._refine_dsize(), doHandSize=False)
         self.lastcom = loc
@@ -195,10 +224,30 @@ class RealtimeHandposePipeline(object):
         t.set_inv(cfg.get('invX') is True, cfg.get('invY') is True)
         return t
 
+    def _no_hand_result(self):
+        """What processFrame answers for a frame in which seed_detect finds no hand: the shape of a LOST frame's result (status 1,
+        zeros, M = identity); the pipeline keeps no centre, so the next frame is searched again."""
+        J = self.poseNet.cfgParams.outputDim[1] // 3
+        self.lastcom = (0, 0, 0)
+        self._devcom = self.lastcom
+        z3 = numpy.zeros(3, numpy.float32)
+        self.sync.update(fid=self.sync['fid'] + 1, com3D=z3, M=numpy.eye(3, dtype=numpy.float32))
+        return dict(pose=numpy.zeros((J, 3), numpy.float32), pose_img=numpy.zeros((J, 3), numpy.float32), com=z3.copy(), com3D=z3.copy(),
+                    M=numpy.eye(3, dtype=numpy.float32), status=1)
+
     def processFrame(self, frame):
         """detect + estimatePose + the de-normalisation of one frame as ONE device plan: the tracker's result dict (pose in mm)."""
         frame = numpy.asarray(frame, numpy.float32)
-        lastcom = self._need_seed(frame)
+        acquiring = self.seed_detect and self.tracking.value and self.state.value != self.STATE_INIT and numpy.allclose(self.lastcom, 0)
+        if acquiring:                                  # the centre goes from the detector plan into the tracker's state on the device
+            acq = self.tracker(*frame.shape).acquire(frame)
+            if acq['found']:
+                self.lastcom = acq['com'].copy()
+                self._devcom = self.lastcom
+        try:
+            lastcom = self._need_seed(frame, detect_tried=acquiring)
+        except _NoHand:
+            return self._no_hand_result()
         t = self.tracker(*frame.shape)
         if t.lost or not numpy.array_equal(numpy.asarray(lastcom, numpy.float32), numpy.asarray(getattr(self, '_devcom', (0, 0, 0)), numpy.float32)):
             t.reset(lastcom)                           # the host's centre changed behind the device's back (seed, reset, detect())
@@ -210,7 +259,8 @@ class RealtimeHandposePipeline(object):
 
     def processVideo(self, device, max_frames=None):
         """Headless processVideo (:235-294): every frame of `device` through the fused plan; returns the poses in mm, (frames, J, 3).
-        Stops at the end of a FileDevice, after max_frames, on `q`, or at a lost track (whose frame is not returned)."""
+        Stops at the end of a FileDevice, after max_frames, on `q`, or at a lost track (whose frame is not returned); with seed_detect
+        a lost frame, or one in which no hand is found, is skipped instead and the next frame is searched again."""
         self.initNets()
         device.start()
         poses = []
@@ -227,7 +277,9 @@ class RealtimeHandposePipeline(object):
             res = self.processFrame(frame)
             times.append(time.time() - start)
             if res['status']:
-                print("Track lost in frame {}.".format(len(poses)))
+                print("Track lost (or no hand) in frame {}.".format(len(times) - 1))
+                if self.seed_detect:
+                    continue
                 break
             poses.append(res['pose'].copy())
             if self.verbose is True:
@@ -236,6 +288,43 @@ class RealtimeHandposePipeline(object):
         self.frame_times = times
         J = self.poseNet.cfgParams.outputDim[1] // 3
         return numpy.asarray(poses, numpy.float32).reshape(-1, J, 3)
+
+    def calibrateHandsize(self, device, num_frames=None):
+        """Headless hand-size calibration, the counterpart of STATE_INIT (:312-324): `num_frames` (default numinitframes) frames of
+        `device`; for each the component hand size (HandDetector.estimateHandsizeComponents, on the device) around the centre the
+        detector acquires or, once there is one, the tracker follows; config['cube'] becomes the `int` median and the state
+        STATE_RUN.  A frame without a hand, or whose track is lost, contributes the current cube, as detect's no-hand return does.
+        Returns the new cube.  (processKey(ord('i')), the reference's cv2-contour calibration, stays not built.)"""
+        n = self.numinitframes if num_frames is None else int(num_frames)
+        self.initNets()
+        device.start()
+        self.handsizes = []
+        while len(self.handsizes) < n:
+            ret, frame = device.getDepth()
+            if ret is False:
+                raise RuntimeError("Error while reading frame.")
+            frame = numpy.asarray(frame, numpy.float32)
+            cfg = self.sync['config']
+            t = self.tracker(*frame.shape)
+            handsz = numpy.asarray(cfg['cube'], numpy.float32)
+            if numpy.allclose(self.lastcom, 0):
+                acq = t.acquire(frame, do_hand_size=True)
+                if acq['found']:
+                    handsz = acq['cube']
+                    self.lastcom = acq['com'].copy()
+                    self._devcom = self.lastcom
+            elif not self.processFrame(frame)['status']:
+                handsz = t.hand_size()
+            self.handsizes.append(tuple(float(c) for c in handsz))
+            if self.verbose is True:
+                print(numpy.median(numpy.asarray(self.handsizes), axis=0))
+        device.stop()
+        cfg = self.sync['config']
+        cfg['cube'] = tuple(int(c) for c in numpy.median(numpy.asarray(self.handsizes), axis=0).astype('int'))
+        self.sync.update(config=cfg)
+        self.state.value = self.STATE_RUN
+        self.handsizes = []
+        return cfg['cube']
 
     # ---- state ------------------------------------------------------------------------------------------------------------
     def processKey(self, key):

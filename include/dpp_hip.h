@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 13
+#define DPP_ABI_VERSION 14
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -505,6 +505,39 @@ int dpp_pose_finish(const float* net_out, int B, int J, const float* cube, const
                     int flip_y, int flags, float* pose3d, float* pose_img, dpp_stream_t stream);
 int dpp_refine_com_iterative(const float* frames, const float* partial, int B, int H, int W, const float* com_in, const float* cube,
                              double fx, double fy, int num_iter, float* com_out, int* status, dpp_stream_t stream);
+
+/* ---- whole-frame hand detection by connected components (ABI v14) -------------------------------------------------------------
+ * What HandDetector.detect / estimateHandsize (handdetector.py:569-632, :911-937) take from cv2.findContours, restated with
+ * 8-connected component labelling (csrc/components.hip): pixel count for contourArea, raster order for contour order, a depth
+ * exactly on a slab boundary in the nearer slab only.  All launches of a frame are stream-ordered; nothing returns to the host.
+ * slab_keys: keys [B][H][W] uint8 from frame_range's partials: the smallest i in [0, 20) with b_i <= d <= b_{i+1},
+ *   b_i = minDepth + i * (maxDepth - minDepth) / 20 in float64; 255 (background) for d == 0 and outside [minDepth, maxDepth].
+ * mask_keys: key 0 where d != 0 && com_z - cube_z / 2 <= d <= com_z + cube_z / 2 (float64, raw frame), else 255.
+ * label_components: labels [B][H][W] int32 = the smallest linear index y * W + x of the pixel's 8-connected component of equal
+ *   key, -1 for key 255.  workspace: dpp_label_workspace_bytes(B, H, W) bytes.  stats (may be NULL): dpp_component_stats_bytes(B, H,
+ *   W) bytes, one 40-byte record per pixel, meaningful at roots (labels[p] == p): int32 count, ~xmin, xmax, ~ymin, ymax, pad;
+ *   uint64 sum x, sum y.  Three launches, four with stats.
+ * detect_seed: state (dpp_detect_state_bytes(B) bytes; slab_keys / mask_keys clear their word of it).  Among the components of
+ *   more than 200 px the smallest key, then the smallest root; com_out [B][3] = calculateCoM of the +-100 px window around its
+ *   centroid inside that slab (handdetector.py:589-607), status [B] = DPP_DETECT_FOUND; no such component: com (0, 0, 0), status 0.
+ *   Two launches.  The caller feeds com_out to dpp_refine_com_iterative (num_iter 5, :610).
+ * hand_size: after mask_keys + label_components with stats: the largest component (ties: smallest root), estimateHandsize from
+ *   its bounding box and com [B][3] -> cube_out [B][3] = (sz + tol) x 3.  status [B] is read and updated: a frame without
+ *   DPP_DETECT_FOUND keeps cube_in; an empty mask keeps cube_in and sets DPP_DETECT_NO_SIZE.  Two launches.
+ * Limits: H * W < 2^31 - 256, H <= 65535 * 32, B <= 65535 (DPP_E_BADARG beyond; the *_bytes functions then return 0). */
+#define DPP_DETECT_FOUND 1
+#define DPP_DETECT_NO_SIZE 2
+size_t dpp_label_workspace_bytes(int B, int H, int W);
+size_t dpp_component_stats_bytes(int B, int H, int W);
+size_t dpp_detect_state_bytes(int B);
+int dpp_slab_keys(const float* frames, const float* partial, int B, int H, int W, unsigned char* keys, void* state, dpp_stream_t stream);
+int dpp_mask_keys(const float* frames, int B, int H, int W, const float* com, const float* cube, unsigned char* keys, void* state,
+                  dpp_stream_t stream);
+int dpp_label_components(const unsigned char* keys, int B, int H, int W, void* workspace, int* labels, void* stats, dpp_stream_t stream);
+int dpp_detect_seed(const float* frames, const float* partial, const unsigned char* keys, const int* labels, const void* stats, int B, int H,
+                    int W, void* state, float* com_out, int* status, dpp_stream_t stream);
+int dpp_hand_size(const unsigned char* keys, const int* labels, const void* stats, int B, int H, int W, void* state, const float* com,
+                  const float* cube_in, double fx, double fy, double tol, float* cube_out, int* status, dpp_stream_t stream);
 
 /* ---- PCA prior set-up and evaluation on the device --------------------------------------------
  * pose_sample: HandDetector.sampleRandomPoses (/root/reference/src/util/handdetector.py:805-909) for n samples: sample i augments
