@@ -66,17 +66,6 @@ __device__ __forceinline__ void crop_geometry(float mn, float mx, const float c[
     }
 }
 
-// (mn, mx) over the workgroup: wave shuffle, then LDS, then thread 0 -- the only thread that gets `true` and the result.
-__device__ __forceinline__ bool block_minmax(float& mn, float& mx, float* s_mn, float* s_mx) {
-    const int tid = threadIdx.x;
-    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
-    if ((tid & 63) == 0) { s_mn[tid >> 6] = mn; s_mx[tid >> 6] = mx; }
-    __syncthreads();
-    if (tid != 0) return false;
-    for (int w = 1; w < DPP_THREADS / DPP_WAVE; ++w) { mn = fminf(mn, s_mn[w]); mx = fmaxf(mx, s_mx[w]); }
-    return true;
-}
-
 __global__ __launch_bounds__(DPP_THREADS) void crop_prepare_kernel(const float* __restrict__ frames, int H, int W,
                                                                    const float* __restrict__ com, const float* __restrict__ cube,
                                                                    double fx, double fy, int dsz, int stretch,

@@ -1,8 +1,9 @@
 // geom.h -- the camera, crop-bounds and warp-coordinate arithmetic that augment.hip, crop.hip, components.hip and prior.hip share,
-// and the workgroup reductions of the whole-frame kernels (crop.hip, components.hip).
+// and the workgroup reductions of the whole-frame kernels (crop.hip, components.hip, ingest.hip).
 //
 // Everything here restates NumPy / OpenCV 2.4 arithmetic that rounds after every operation and is pinned bit for bit to the reference,
-// so every unit that includes this header is compiled with -ffp-contract=off (csrc/Makefile names them).  One body per rule: a fix
+// so every unit that uses that arithmetic is compiled with -ffp-contract=off (csrc/Makefile names them; ingest.hip takes only the
+// min / max reductions, which do not round).  One body per rule: a fix
 // made here reaches every kernel that applies the rule.
 #pragma once
 #include "dpp_common.h"
@@ -127,6 +128,17 @@ __device__ __forceinline__ bool com_block_sums(double& sx, double& sy, double& s
     __syncthreads();
     if (tid != 0) return false;
     for (int w = 1; w < DPP_THREADS / DPP_WAVE; ++w) { sx += s_red[0][w]; sy += s_red[1][w]; sd += s_red[2][w]; cnt += s_red[3][w]; }
+    return true;
+}
+
+// (mn, mx) over the workgroup: wave shuffle, then LDS, then thread 0 -- the only thread that gets `true` and the result.
+__device__ __forceinline__ bool block_minmax(float& mn, float& mx, float* s_mn, float* s_mx) {
+    const int tid = threadIdx.x;
+    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+    if ((tid & 63) == 0) { s_mn[tid >> 6] = mn; s_mx[tid >> 6] = mx; }
+    __syncthreads();
+    if (tid != 0) return false;
+    for (int w = 1; w < DPP_THREADS / DPP_WAVE; ++w) { mn = fminf(mn, s_mn[w]); mx = fmaxf(mx, s_mx[w]); }
     return true;
 }
 

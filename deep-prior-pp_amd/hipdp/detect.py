@@ -18,6 +18,9 @@ with 8-connected component labelling (csrc/components.hip):
 
 Three deviations from the reference, all forced by leaving cv2 out: pixel count instead of contourArea; raster-first instead of
 cv2's contour order; a depth exactly on a slab boundary belongs to the nearer slab only.
+
+With sensor=dict(dtype=, median=, mirror=) the frames handed to run() are RAW sensor frames: frame_ingest (csrc/ingest.hip) converts,
+mirrors and median-filters them into the float32 frame buffer and writes the depth-range partials, in frame_range's place.
 """
 import numpy as np
 
@@ -27,7 +30,7 @@ NUM_REFINE_ITER = 5                 # handdetector.py:610
 
 
 class FrameDetector(object):
-    def __init__(self, rt, H, W, fx, fy, B=1, frames=None, partial=None, com=None, cube=None, res=None):
+    def __init__(self, rt, H, W, fx, fy, B=1, frames=None, partial=None, com=None, cube=None, res=None, sensor=None, raw=None):
         """
         :param H, W:    frame size
         :param fx, fy:  what the reference hands to HandDetector
@@ -35,11 +38,17 @@ class FrameDetector(object):
         :param frames, partial, com, cube: device buffers of an owner whose state the plan works on (HandTracker: its frame buffer,
                         its depth-range partials, its centre -- the plan's final centre lands there -- and its cube); by default own
         :param res:     8 * B float32 of an owner's result block for seed / cube out / status (so that the owner reads ONE block)
+        :param sensor:  None, or dict(dtype='uint16' | 'float32', median=bool, mirror=bool): run() takes raw frames of that dtype
+        :param raw:     with a sensor: the owner's raw frame buffer (B, H, W) of the sensor's dtype; by default own
         """
         self.rt, self.B, self.H, self.W = rt, int(B), int(H), int(W)
         self.fx, self.fy = abs(float(fx)), abs(float(fy))
         f32 = np.float32
         self.frames = frames if frames is not None else rt.alloc((self.B, self.H, self.W), f32, zero=False)
+        self.sensor = None if sensor is None else ops.sensor_spec(sensor)
+        self.raw = None
+        if self.sensor is not None:
+            self.raw = raw if raw is not None else rt.alloc((self.B, self.H, self.W), self.sensor[0], zero=False)
         self.partial = partial if partial is not None else ops.frame_range_workspace(rt, self.B)
         self.com = com if com is not None else rt.alloc((self.B, 3), f32)
         self.cube = cube if cube is not None else rt.alloc((self.B, 3), f32)
@@ -52,7 +61,7 @@ class FrameDetector(object):
 
     def stage(self, do_hand_size=False, with_range=True):
         """The detector's launches in order (steps a-f of the module docstring); with_range=False when the caller's plan has already
-        run frame_range on these frames."""
+        run frame_range (or frame_ingest) on these frames."""
         rt, B, H, W, fr, ws = self.rt, self.B, self.H, self.W, self.frames, self.ws
         out = [ops.frame_range(rt, fr, B, H, W, self.partial)] if with_range else []
         out += [ops.slab_keys(rt, fr, self.partial, ws),
@@ -87,7 +96,10 @@ class FrameDetector(object):
         key = bool(do_hand_size)
         if key not in self._plans:
             p = ops.Plan('detect')
-            for op in self.stage(key):
+            if self.sensor is not None:             # raw -> frames and the partials, then the stage without its range pass
+                p.add(ops.frame_ingest(self.rt, self.raw, self.B, self.H, self.W, self.frames, self.partial, median=self.sensor[1],
+                                       mirror=self.sensor[2]))
+            for op in self.stage(key, with_range=self.sensor is None):
                 p.add(op)
             self._plans[key] = p
         return self._plans[key]
@@ -106,8 +118,14 @@ class FrameDetector(object):
         return coms, cubes, found, res[:3 * B].reshape(B, 3).copy(), status
 
     def run(self, frames, cubes, do_hand_size=False):
-        """Upload B frames and their cubes, run the plan, download the result (see result())."""
-        self.frames.set(np.ascontiguousarray(frames, np.float32).reshape(self.B, self.H, self.W))
+        """Upload B frames (raw ones of the sensor's dtype, with a sensor) and their cubes, run the plan, download the result (see result())."""
+        if self.sensor is None:
+            self.frames.set(np.ascontiguousarray(frames, np.float32).reshape(self.B, self.H, self.W))
+        else:
+            frames = np.asarray(frames)
+            if frames.dtype != self.sensor[0]:
+                raise ValueError("frame dtype %s, the detector's sensor delivers %s" % (frames.dtype, self.sensor[0]))
+            self.raw.set(np.ascontiguousarray(frames).reshape(self.B, self.H, self.W))
         self.cube.set(np.ascontiguousarray(cubes, np.float32).reshape(self.B, 3))
         self.plan(do_hand_size).run(self.rt)
         self.rt.synchronize()

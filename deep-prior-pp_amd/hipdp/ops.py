@@ -729,6 +729,34 @@ def frame_range(rt, frames, B, H, W, partial, name='frame_range'):
                   dict(kernel='frame_range', flops=2.0 * B * H * W, bytes=4.0 * B * H * W))
 
 
+INGEST_U16, INGEST_F32 = 1, 2                 # DPP_INGEST_*: source types of dpp_frame_ingest
+INGEST_MEDIAN3, INGEST_MIRROR_X = 1, 2        # ... and its flags
+INGEST_TYPES = {'uint16': INGEST_U16, 'float32': INGEST_F32}
+
+
+def sensor_spec(sensor):
+    """A sensor description dict(dtype='uint16' | 'float32', median=bool, mirror=bool) checked and normalised to (numpy dtype, median, mirror)."""
+    unknown = set(sensor) - {'dtype', 'median', 'mirror'}
+    if unknown:
+        raise ValueError("unknown sensor options: %s" % sorted(unknown))
+    dt = np.dtype(sensor.get('dtype', 'uint16'))
+    if dt.name not in INGEST_TYPES:
+        raise ValueError("a sensor delivers uint16 or float32 frames, not %s" % dt.name)
+    return dt, bool(sensor.get('median', False)), bool(sensor.get('mirror', False))
+
+
+def frame_ingest(rt, raw, B, H, W, frames, partial, median=False, mirror=False, name='frame_ingest'):
+    """dpp_frame_ingest: raw sensor frames (uint16 or float32, by raw.dtype) -> float32 frames, optionally mirrored and 3x3-median
+    filtered, and frame_range's partials of the result (partial may be None) -- in a plan it stands where frame_range stood."""
+    if raw.dtype.name not in INGEST_TYPES:
+        raise ValueError("frame_ingest reads uint16 or float32 frames, not %s" % raw.dtype.name)
+    flags = (INGEST_MEDIAN3 if median else 0) | (INGEST_MIRROR_X if mirror else 0)
+    npx = float(B) * H * W
+    # a median output takes 8 compare-exchanges' worth of its columns' sorts (shared by three outputs) + 12 of its own; min / max: 2
+    return Launch(rt.lib.dpp_frame_ingest, (raw.ptr, INGEST_TYPES[raw.dtype.name], B, H, W, flags, frames.ptr, _p(partial)), (raw, frames, partial),
+                  name, dict(kernel='frame_ingest', flops=(22.0 if median else 2.0) * npx, bytes=(raw.dtype.itemsize + 4.0) * npx))
+
+
 def crop_prepare_ranged(rt, partial, B, com, cube, fx, fy, dsz, records, M_out=None, stretch=False, name='crop_prepare_ranged'):
     """dpp_crop_prepare_ranged: crop_prepare's records from frame_range's partials (no pass over the frame)."""
     return Launch(rt.lib.dpp_crop_prepare_ranged, (partial.ptr, B, com.ptr, cube.ptr, float(fx), float(fy), dsz, int(bool(stretch)), records.ptr,

@@ -28,6 +28,12 @@ LOST frames.  Where the refined centre's depth is numpy.isclose to 0 the referen
 (handdetector.py:204-213) and crops the MIDDLE of the frame; no device kernel implements that branch.  track_refine flags such a
 frame instead (status 1), gives it an empty crop window (an all-zero net input, finite outputs), and the tracker refuses further
 frames until reset(com) or a successful acquire(frame).
+
+SENSOR frames.  HandTracker(..., sensor=dict(dtype='uint16' | 'float32', median=bool, mirror=bool)) takes frames as a depth sensor
+delivers them: the host uploads the RAW frame (half the bytes for uint16) and the plan starts with frame_ingest (csrc/ingest.hip:
+mirror, 3x3 median with a replicated border, conversion to float32 -- what the reference's CreativeCameraDevice.getDepth does on the
+host, src/util/cameradevice.py:189-200 of the reference) IN PLACE OF frame_range: it writes the float32 frame buffer everything
+downstream reads and the same depth-range partials, so the launch count does not change.  sensor=None is the plan above, untouched.
 """
 import numpy as np
 
@@ -75,7 +81,7 @@ def refine_stage(rt, frame, H, W, partial, rec, com_in, cube, ceng, cam, fx, fy,
 
 
 class HandTracker(object):
-    def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, hand_right=False, invX=False, invY=False, fx=None, fy=None):
+    def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, hand_right=False, invX=False, invY=False, fx=None, fy=None, sensor=None):
         """
         :param importer:   the dataset importer (camera; NYU / MSRA flip the y axis)
         :param poseNet:    the pose regressor, built for a batch of one; its output is J x 3 normalised joints
@@ -84,6 +90,8 @@ class HandTracker(object):
         :param cube:       metric cube (mm) around the hand
         :param hand_right, invX, invY: estimatePose's mirroring (realtimehandposepipeline.py:347-369)
         :param fx, fy:     what the reference hands to HandDetector (config['fx'], config['fy']); default: the importer's
+        :param sensor:     None: frames are float32 millimetres, prepared by the host.  dict(dtype='uint16' | 'float32', median=bool,
+                           mirror=bool): frames are RAW sensor frames of that dtype, converted (mirrored, median-filtered) on the device
         """
         self.rt, self.H, self.W = rt, int(H), int(W)
         self.importer = importer
@@ -98,6 +106,10 @@ class HandTracker(object):
         f32 = np.float32
         J3 = self.J * 3
         self.frames = [rt.alloc((1, self.H, self.W), f32, zero=False) for _ in range(2)]      # t and t + 1 (process_sequence)
+        self.sensor = None if sensor is None else ops.sensor_spec(sensor)                      # (dtype, median, mirror)
+        # with a sensor the host uploads into `raw`, frame_ingest fills `frames`; without one `frames` IS what the host uploads into
+        self.raw = None if sensor is None else [rt.alloc((1, self.H, self.W), self.sensor[0], zero=False) for _ in range(2)]
+        self.inputs = self.frames if sensor is None else self.raw
         self.partial = ops.frame_range_workspace(rt, 1)
         self.rec = rt.alloc(rt.lib.dpp_crop_record_bytes(), np.uint8)
         self.cube = rt.alloc((1, 3), f32)
@@ -127,20 +139,24 @@ class HandTracker(object):
         self.lost = False
 
     def detector(self):
-        """The whole-frame detector on this tracker's buffers: frame slot 0, the depth-range partials, the centre (its output) and the cube."""
+        """The whole-frame detector on this tracker's buffers: frame slot 0 (and its raw buffer, with a sensor), the depth-range partials,
+        the centre (its output) and the cube."""
         if self._detector is None:
             from .detect import FrameDetector
             self._detector = FrameDetector(self.rt, self.H, self.W, self.fx, self.fy, 1, frames=self.frames[0], partial=self.partial,
-                                           com=self.com, cube=self.cube, res=self.res.view(2 * self.J * 3 + 16, (8,)))
+                                           com=self.com, cube=self.cube, res=self.res.view(2 * self.J * 3 + 16, (8,)),
+                                           sensor=None if self.sensor is None else dict(zip(('dtype', 'median', 'mirror'), self.sensor)),
+                                           raw=None if self.sensor is None else self.raw[0])
         return self._detector
 
     def acquire(self, frame, do_hand_size=False):
-        """Find the hand in `frame` and start (again) from it: one upload, the detector plan, one download of the tracker's result block.  Returns dict(com [3]
+        """Find the hand in `frame` (a raw one with a sensor: frame_ingest then opens the detector plan) and start (again) from it: one
+        upload, the detector plan, one download of the tracker's result block.  Returns dict(com [3]
         image coordinates, cube [3] -- measured with do_hand_size, else the tracker's; the tracker's own cube is not changed --, found).
         Not found: the centre is (0, 0, 0) and the track is lost."""
         frame = self._frame(frame)
         det = self.detector()
-        self.frames[0].set(frame)
+        self.inputs[0].set(frame)
         self._slot = 0
         det.plan(do_hand_size).run(self.rt)
         self.rt.synchronize()
@@ -152,7 +168,8 @@ class HandTracker(object):
 
     def hand_size(self, tol=0.0):
         """The hand's cube around the current centre in the frame last handed to process() or acquire():
-        HandDetector.estimateHandsizeComponents on the device state.  An empty depth range gives the tracker's cube.  After
+        HandDetector.estimateHandsizeComponents on the device state (with a sensor: on the converted, filtered frame the plan left in
+        the float32 frame buffer).  An empty depth range gives the tracker's cube.  After
         process_sequence the last frame may sit in the other frame buffer, which the detector does not see: RuntimeError."""
         if self._slot != 0:
             raise RuntimeError("hand_size measures the frame of the last process() / acquire(); the last frame came through process_sequence")
@@ -180,7 +197,10 @@ class HandTracker(object):
         if key not in self._plans:
             rt, H, W, fr = self.rt, self.H, self.W, self.frames[slot]
             p = ops.Plan('track')
-            p.add(ops.frame_range(rt, fr, 1, H, W, self.partial))
+            if self.sensor is None:
+                p.add(ops.frame_range(rt, fr, 1, H, W, self.partial))
+            else:                                   # raw -> fr and the same partials: in frame_range's place, not in front of it
+                p.add(ops.frame_ingest(rt, self.raw[slot], 1, H, W, fr, self.partial, median=self.sensor[1], mirror=self.sensor[2]))
             # the state buffer is read (prepare, track_refine) and then rewritten by ONE lane of track_refine: in place
             for op, side in refine_stage(rt, fr, H, W, self.partial, self.rec, self.com, self.cube, self.ceng, self.cam, self.fx, self.fy,
                                          self.ds, self.com, self.com3d, self.rec, self.status, self.M):
@@ -208,7 +228,12 @@ class HandTracker(object):
         return self._frame(frame)
 
     def _frame(self, frame):
-        frame = np.asarray(frame, np.float32)
+        if self.sensor is None:
+            frame = np.asarray(frame, np.float32)
+        else:                                       # a raw frame is taken as it is or not at all: no silent conversion
+            frame = np.asarray(frame)
+            if frame.dtype != self.sensor[0]:
+                raise ValueError("frame dtype %s, the tracker's sensor delivers %s" % (frame.dtype, self.sensor[0]))
         if frame.shape != (self.H, self.W):
             raise ValueError("frame shape %s, expected %s" % (frame.shape, (self.H, self.W)))
         return frame
@@ -218,7 +243,7 @@ class HandTracker(object):
         coordinates, com3D [3], M [3][3], status[, crop]) -- `crop` as the pose net saw it (normalised; mirrored for HAND_RIGHT).
         status LOST: see the module docstring; the other entries are finite but meaningless and the tracker needs reset(com)."""
         frame = self._check(frame)
-        self.frames[0].set(frame)
+        self.inputs[0].set(frame)
         self._slot = 0
         self.plan(0).run(self.rt)
         self.runs += 1
@@ -244,9 +269,9 @@ class HandTracker(object):
             frame = self._check(frame)
             k = n & 1
             if staged:
-                rt.wait_event(rt.staged_upload(self.frames[k], frame[None], free[k]))
+                rt.wait_event(rt.staged_upload(self.inputs[k], frame[None], free[k]))
             else:
-                self.frames[k].set(frame)
+                self.inputs[k].set(frame)
             self.plan(k).run(rt)
             self._slot = k
             self.runs += 1

@@ -22,6 +22,12 @@ precedence over seed_com.  A frame in which seed_detect finds no hand (and seed_
 one and the next frame is searched again.  With tracking off, or an all-zero last centre and no seed at all, detect raises the
 NotImplementedError of HandDetector.detect.  calibrateHandsize(device) is the headless counterpart of STATE_INIT (:312-324) on the component hand size.
 
+SENSOR frames: with sensor=dict(dtype='uint16' | 'float32', median=bool, mirror=bool) the frames handed to processFrame /
+processVideo / calibrateHandsize (and to detect) are RAW sensor frames of that dtype; the mirror, the 3x3 median and the conversion
+to float32 of the reference's CreativeCameraDevice.getDepth (cameradevice.py:189-200) run at the head of the frame's device plan
+(hipdp.tracker.HandTracker(sensor=...)), and the per-call paths filter through util.cameradevice.filter_depth first, so that both
+routes see the same frame.
+
 A LOST track (the tracked centre's depth is close to 0: the reference would crop the middle of the frame through comToBounds'
 "CoM ill-defined" branch, which is not built) gives a zero crop, eye(3) and a zero com3D -- the answer of :326-327 -- and clears
 the last centre, so that the next frame needs a seed again.
@@ -63,7 +69,7 @@ class RealtimeHandposePipeline(object):
     # different detectors
     DETECTOR_COM = 0
 
-    def __init__(self, poseNet, config, di, verbose=False, comrefNet=None, init_com=None, seed_com=False, seed_detect=False):
+    def __init__(self, poseNet, config, di, verbose=False, comrefNet=None, init_com=None, seed_com=False, seed_detect=False, sensor=None):
         """
         :param poseNet:   network for pose estimation (a built net, or PoseRegNetParams / ResNetParams, with loadFile or not)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=])
@@ -73,6 +79,8 @@ class RealtimeHandposePipeline(object):
         :param seed_com:  NON-reference seed from the frame's own centre of mass (module docstring)
         :param seed_detect: seed, and re-seed after a lost frame, by connected-component detection on the device (switches tracking on;
                           takes precedence over seed_com)
+        :param sensor:    None (frames are float32 mm), or dict(dtype='uint16' | 'float32', median=bool, mirror=bool): frames are raw
+                          sensor frames, converted / mirrored / median-filtered on the device (module docstring)
         """
         self.importer = di
         self.poseNet = poseNet
@@ -95,6 +103,7 @@ class RealtimeHandposePipeline(object):
         self.show_pose = False
         self.show_crop = False
         self._tracker = None
+        self.sensor = None if sensor is None else dict(sensor)
 
     def initNets(self):
         """Build the nets from their parameters (loading loadFile where set) and compile their forward plans (:118-141)."""
@@ -127,8 +136,22 @@ class RealtimeHandposePipeline(object):
         d0 = dims[0] if isinstance(dims[0], (list, tuple)) else dims
         return (int(d0[2]), int(d0[3]))
 
-    def _seed(self, frame):
-        """The NON-reference seed: whole-frame centre of mass + refineCoMIterative(com, 5, cube)."""
+    def _filtered(self, frame):
+        """The float32 frame the per-call paths work on: a raw sensor frame through filter_depth, anything else as float32."""
+        if self.sensor is None:
+            return numpy.asarray(frame, numpy.float32)
+        from hipdp import ops
+        from util.cameradevice import filter_depth
+        dt, median, mirror = ops.sensor_spec(self.sensor)
+        frame = numpy.asarray(frame)
+        if frame.dtype != dt:
+            raise ValueError("frame dtype %s, the pipeline's sensor delivers %s" % (frame.dtype, dt))
+        return filter_depth(frame, median=median, mirror=mirror)
+
+    def _seed(self, frame, filtered=False):
+        """The NON-reference seed: whole-frame centre of mass + refineCoMIterative(com, 5, cube).  filtered: `frame` has been through
+        _filtered already."""
+        frame = numpy.asarray(frame, numpy.float32) if filtered else self._filtered(frame)
         cfg = self.sync['config']
         hd = HandDetector(numpy.asarray(frame, numpy.float32).copy(), cfg['fx'], cfg['fy'], importer=self.importer)
         com = hd.calculateCoM(hd.dpt)
@@ -137,25 +160,27 @@ class RealtimeHandposePipeline(object):
         cube = numpy.asarray(cfg['cube'], numpy.float32)
         return refine_com_iterative(numpy.asarray(frame, numpy.float32)[None], com[None], cube[None], cfg['fx'], cfg['fy'], 5)[0]
 
-    def _detect_seed(self, frame):
+    def _detect_seed(self, frame, filtered=False):
         """seed_detect for the per-call API: HandDetector.detectComponents' centre (doHandSize=False), zeros where there is no hand."""
         from util.handdetector import find_hands
+        frame = numpy.asarray(frame, numpy.float32) if filtered else self._filtered(frame)
         cfg = self.sync['config']
         coms, _, found = find_hands(numpy.asarray(frame, numpy.float32)[None], numpy.asarray(cfg['cube'], numpy.float32)[None], cfg['fx'], cfg['fy'])
         return coms[0] if found[0] else numpy.zeros(3, numpy.float32)
 
-    def _need_seed(self, frame, detect_tried=False):
-        """The centre to track from, seeding it where there is none; without a seed: HandDetector.detect's NotImplementedError."""
+    def _need_seed(self, frame, detect_tried=False, filtered=False):
+        """The centre to track from, seeding it where there is none; without a seed: HandDetector.detect's NotImplementedError.
+        filtered: `frame` is the float32 frame _filtered returned (detect has it already), not a raw sensor frame."""
         if self.state.value == self.STATE_INIT:
             raise NotImplementedError("hand-size calibration (STATE_INIT: estimateHandsize from cv2.findContours) is not built")
         if self.tracking.value and not numpy.allclose(self.lastcom, 0):
             return numpy.asarray(self.lastcom, numpy.float32)
         if self.tracking.value and self.seed_detect and not detect_tried:
-            com = self._detect_seed(frame)
+            com = self._detect_seed(frame, filtered)
             if not numpy.isclose(com[2], 0.):
                 return com
         if self.tracking.value and self.seed_com:
-            com = self._seed(frame)
+            com = self._seed(frame, filtered)
             if not numpy.isclose(com[2], 0.):
                 return com
         if self.tracking.value and self.seed_detect:
@@ -167,8 +192,10 @@ class RealtimeHandposePipeline(object):
     def detect(self, frame):
         """Follow the hand into `frame` (:296-337, tracking mode): (normalised crop, transformation M, com3D)."""
         cfg = self.sync['config']
+        if self.sensor is not None:                    # filtered ONCE: the seeds below get the same float32 frame
+            frame = self._filtered(frame)
         try:
-            lastcom = self._need_seed(frame)
+            lastcom = self._need_seed(frame, filtered=self.sensor is not None)
         except _NoHand:                                # the answer of :326-327, as for a lost track
             self.lastcom = (0, 0, 0)
             self.handsizes = []
@@ -217,7 +244,7 @@ class RealtimeHandposePipeline(object):
         t = self._tracker
         if t is None or (t.H, t.W) != (H, W) or (t.fx, t.fy) != (abs(float(cfg['fx'])), abs(float(cfg['fy']))):
             t = self._tracker = HandTracker(default_runtime(), self.importer, self.poseNet, self.comrefNet, H, W, cfg['cube'],
-                                            fx=cfg['fx'], fy=cfg['fy'])
+                                            fx=cfg['fx'], fy=cfg['fy'], sensor=self.sensor)
         if tuple(numpy.float32(cfg['cube'])) != tuple(t.cube_host):
             t.set_cube(cfg['cube'])
         t.set_hand(self.hand.value == self.HAND_RIGHT)
@@ -237,7 +264,7 @@ class RealtimeHandposePipeline(object):
 
     def processFrame(self, frame):
         """detect + estimatePose + the de-normalisation of one frame as ONE device plan: the tracker's result dict (pose in mm)."""
-        frame = numpy.asarray(frame, numpy.float32)
+        frame = numpy.asarray(frame, numpy.float32) if self.sensor is None else numpy.asarray(frame)     # (a raw frame: the tracker checks its dtype)
         acquiring = self.seed_detect and self.tracking.value and self.state.value != self.STATE_INIT and numpy.allclose(self.lastcom, 0)
         if acquiring:                                  # the centre goes from the detector plan into the tracker's state on the device
             acq = self.tracker(*frame.shape).acquire(frame)
@@ -303,7 +330,7 @@ class RealtimeHandposePipeline(object):
             ret, frame = device.getDepth()
             if ret is False:
                 raise RuntimeError("Error while reading frame.")
-            frame = numpy.asarray(frame, numpy.float32)
+            frame = numpy.asarray(frame, numpy.float32) if self.sensor is None else numpy.asarray(frame)
             cfg = self.sync['config']
             t = self.tracker(*frame.shape)
             handsz = numpy.asarray(cfg['cube'], numpy.float32)

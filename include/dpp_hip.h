@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 14
+#define DPP_ABI_VERSION 15
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -505,6 +505,27 @@ int dpp_pose_finish(const float* net_out, int B, int J, const float* cube, const
                     int flip_y, int flags, float* pose3d, float* pose_img, dpp_stream_t stream);
 int dpp_refine_com_iterative(const float* frames, const float* partial, int B, int H, int W, const float* com_in, const float* cube,
                              double fx, double fy, int num_iter, float* com_out, int* status, dpp_stream_t stream);
+
+/* ---- sensor frames (ABI v15): uint16 / float32 ingest, mirror, 3x3 median (csrc/ingest.hip) ----------------------------------------
+ * What the reference's live depth source does to every frame (src/util/cameradevice.py:189-200 of the reference): optional mirror,
+ * cv2.medianBlur(depth, 3) with its replicated border, conversion to float32 -- in one launch that also writes frame_range's
+ * partials, so that it REPLACES dpp_frame_range in a plan:
+ *   frames[b][y][x] = float32( median of the nine raw[b][clamp(y + dy, 0, H - 1)][clamp(xs + dx, 0, W - 1)] ),
+ *   xs = W - 1 - x under DPP_INGEST_MIRROR_X, else x; without DPP_INGEST_MEDIAN3 the conversion (and the mirror) alone.
+ * raw [B][H][W] of src_type (DPP_INGEST_U16: uint16, DPP_INGEST_F32: float32); frames [B][H][W] float32, must not overlap raw.  The
+ * median is selected in the source type by comparisons only (uint16 -> float32 is exact), so the result is bit for bit that of
+ * cv2.medianBlur / scipy.ndimage.median_filter(size=3, mode='nearest'); the mirror commutes with it.  A float32 source must be free
+ * of NaN (a NaN makes the comparisons, and so the selection, meaningless); which of -0.0 / +0.0 is selected among equal zeros and
+ * the handling of subnormals are not part of the contract.
+ * partial: NULL, or dpp_frame_range's workspace (dpp_frame_range_bytes(B) bytes): EVERY band's (min, max) over the float32 values
+ * stored to frames is written, an empty band (H below the band count) gets dpp_frame_range's identities (3.4e38f, -3.4e38f).
+ * DPP_E_BADARG (nothing launched): NULL raw / frames, overlapping raw and frames, B / H / W below 1, B above 65535, H * W above
+ * 2^31 - 1, an unknown src_type, unknown flag bits. */
+#define DPP_INGEST_U16 1
+#define DPP_INGEST_F32 2
+#define DPP_INGEST_MEDIAN3 1
+#define DPP_INGEST_MIRROR_X 2
+int dpp_frame_ingest(const void* raw, int src_type, int B, int H, int W, int flags, float* frames, float* partial, dpp_stream_t stream);
 
 /* ---- whole-frame hand detection by connected components (ABI v14) -------------------------------------------------------------
  * What HandDetector.detect / estimateHandsize (handdetector.py:569-632, :911-937) take from cv2.findContours, restated with
