@@ -4,6 +4,7 @@
 //                           applyCrop3D; ABI v12)
 //   realtime tracking       frame_range, crop_prepare_ranged, track_refine, pose_finish, refine_com_iterative (HandDetector.track,
 //                           RealtimeHandposePipeline; ABI v13)
+//   several tracks          the *_ix entry points of the five tracking launches: T tracks over C frames (ABI v16)
 // They share CropRec, crop_geometry and crop_window_value; each section below names the reference lines it restates.  The training-time
 // augmentation of finished crops is augment.hip; finding the hand in a whole frame (connected components) is components.hip; the
 // camera, bounds and warp-coordinate arithmetic and the workgroup reductions these units share are geom.h.
@@ -97,6 +98,17 @@ __global__ __launch_bounds__(DPP_THREADS) void crop_prepare_kernel(const float* 
     crop_geometry(mn, mx, c, cube + b * 3, fx, fy, dsz, stretch, r, M_out ? M_out + (size_t)b * 9 : nullptr);
     rec[b] = r;
 }
+
+// ---- several tracks (ABI v16) -----------------------------------------------------------------------------------------------
+// The tracking launches serve T tracks over C frames: row t of com / cube / records / net outputs is track t, which reads frame
+// src[t] (and that frame's depth-range partials), sits a tick out where gate[t] == 0 and has its own POSE_* bits in tflags[t].
+// The arrays are null in the plain entry points (row b reads frame b, nothing is gated, the flags are a launch argument), so both
+// forms run the same bodies.  The host has checked 0 <= src[t] < C.
+constexpr int POSE_HAND_RIGHT = 1, POSE_INV_X = 2, POSE_INV_Y = 4;     // dpp_pose_finish flags
+constexpr int TRACK_OK = 0, TRACK_LOST = 1, TRACK_IDLE = 2;           // dpp_track_refine status
+
+__device__ __forceinline__ int track_source(const int* __restrict__ src, int b) { return src ? src[b] : b; }
+__device__ __forceinline__ bool track_gated(const int* __restrict__ gate, int b) { return gate && gate[b] == 0; }
 
 constexpr int CW_NORMALIZE = 1, CW_BILINEAR = 2, CW_NO_RANGE = 4, CW_NO_THRESH = 8, CW_FLIP_X = 16;     // dpp_crop_warp_ex flags
 
@@ -294,13 +306,15 @@ __device__ __forceinline__ float bilinear_nd(const Src& src, int sw, int sh, int
 // normalisation to [-1, 1] (dataset.py:98-100) -- with the options of the reference's other callers of the window resize: bilinear mode
 // (cropArea3D / applyCrop3D with resizeMethod = RESIZE_BILINEAR), no detector range test (applyCrop3D crops an arbitrary image),
 // z-threshold off, getCrop's pad value and a fill value outside the paste of their own.  Inlined into both entry points below.
+// src (null: row b reads frame b): the frame of row b, see "several tracks" below.
 __device__ __forceinline__ void crop_warp_body(const float* __restrict__ frames, int H, int W, const CropRec* __restrict__ rec, int dsz, int flags,
-                                               float nd_value, float fill_value, float pad_value, float* __restrict__ out) {
+                                               float nd_value, float fill_value, float pad_value, const int* __restrict__ src,
+                                               float* __restrict__ out) {
     const int b = blockIdx.y;
     const int p = blockIdx.x * DPP_THREADS + threadIdx.x;
     if (p >= dsz * dsz) return;
     const CropRec r = rec[b];
-    const float* f = frames + (size_t)b * H * W;
+    const float* f = frames + (size_t)track_source(src, b) * H * W;
     const int y = p / dsz, xo = p - y * dsz;
     const int x = (flags & CW_FLIP_X) ? dsz - 1 - xo : xo;      // crop[:, ::-1]: output column xo holds column dsz - 1 - xo
     float v = fill_value;
@@ -323,14 +337,17 @@ __device__ __forceinline__ void crop_warp_body(const float* __restrict__ frames,
 // The training path's crop_frames: nearest neighbour, range test and z-threshold on, nd_value outside the paste.  Its flags are
 // compile-time constants apart from the normalise bit, so the bilinear, flip and no-range branches of the body are compiled out.
 __global__ __launch_bounds__(DPP_THREADS) void crop_warp_kernel(const float* __restrict__ frames, int H, int W, const CropRec* __restrict__ rec,
-                                                                int dsz, int normalize, float nd_value, float* __restrict__ out) {
-    crop_warp_body(frames, H, W, rec, dsz, normalize ? CW_NORMALIZE : 0, nd_value, nd_value, 0.0f, out);
+                                                                int dsz, int normalize, float nd_value, const int* __restrict__ src,
+                                                                float* __restrict__ out) {
+    crop_warp_body(frames, H, W, rec, dsz, normalize ? CW_NORMALIZE : 0, nd_value, nd_value, 0.0f, src, out);
 }
 
 __global__ __launch_bounds__(DPP_THREADS) void crop_warp_ex_kernel(const float* __restrict__ frames, int H, int W, const CropRec* __restrict__ rec,
                                                                    int dsz, int flags, float nd_value, float fill_value, float pad_value,
+                                                                   const int* __restrict__ src, const int* __restrict__ tflags,
                                                                    float* __restrict__ out) {
-    crop_warp_body(frames, H, W, rec, dsz, flags, nd_value, fill_value, pad_value, out);
+    if (tflags && (tflags[blockIdx.y] & POSE_HAND_RIGHT)) flags |= CW_FLIP_X;      // the row's own hand side
+    crop_warp_body(frames, H, W, rec, dsz, flags, nd_value, fill_value, pad_value, src, out);
 }
 
 // resizeCrop on B same-size crops: cv2 2.4 resizeNN (source index min(floor(x * ifx), sw - 1)) or bilinearResize
@@ -463,18 +480,20 @@ __device__ __forceinline__ void crop_empty_record(float min_depth, float max_dep
 }
 
 // crop_prepare_kernel without its pass over the frame: one wave per frame reduces the partials, lane 0 writes the record.  An
-// ill-defined centre (a lost track whose next frame is already queued) gets the empty window instead of a division by zero.
+// ill-defined centre (a lost track whose next frame is already queued) gets the empty window instead of a division by zero, and so
+// does a gated track.
 __global__ __launch_bounds__(DPP_WAVE) void crop_prepare_ranged_kernel(const float* __restrict__ partial, const float* __restrict__ com,
                                                                        const float* __restrict__ cube, double fx, double fy, int dsz, int stretch,
+                                                                       const int* __restrict__ src, const int* __restrict__ gate,
                                                                        CropRec* __restrict__ rec, float* __restrict__ M_out) {
     const int b = blockIdx.x;
     float mn, mx;
-    frame_range_reduce(partial, b, threadIdx.x, mn, mx);
+    frame_range_reduce(partial, track_source(src, b), threadIdx.x, mn, mx);
     if (threadIdx.x != 0) return;
     CropRec r;
     const float c[3] = {com[b * 3], com[b * 3 + 1], com[b * 3 + 2]};
     float* M = M_out ? M_out + (size_t)b * 9 : nullptr;
-    if (com_ill_defined(c)) crop_empty_record(fmaxf(10.0f, mn), fminf(1500.0f, mx), r, M);
+    if (com_ill_defined(c) || track_gated(gate, b)) crop_empty_record(fmaxf(10.0f, mn), fminf(1500.0f, mx), r, M);
     else crop_geometry(mn, mx, c, cube + b * 3, fx, fy, dsz, stretch, r, M);
     rec[b] = r;
 }
@@ -485,24 +504,27 @@ __global__ __launch_bounds__(DPP_WAVE) void crop_prepare_ranged_kernel(const flo
 // centre is a case of it) or not finite, or when com_in already was.  A lost frame gets an EMPTY window (crop_warp then writes zeros, nothing divides by zero or
 // leaves the frame), M = identity and com3D = 0.  One lane per frame does all of it, reads before writes: com_out may be com_in (the
 // tracker's state buffer, updated in place -- the next reader is the next frame's first prepare, a later launch) and rec_out may be rec_in.
+// A gated track is never lost: status 2 (idle), the empty window, M = identity, com3D = 0, and its centre's bits are left as they are.
 __global__ __launch_bounds__(DPP_WAVE) void track_refine_kernel(const float* __restrict__ frames, int H, int W, const CropRec* rec_in,
                                                                 const float* com_in, const float* __restrict__ cube,
                                                                 const float* __restrict__ net_out, AugCam cam, double fx, double fy, int dsz,
+                                                                const int* __restrict__ src, const int* __restrict__ gate,
                                                                 float* com_out, float* __restrict__ com3d_out, CropRec* rec_out,
                                                                 float* __restrict__ M_out, int* __restrict__ status) {
     const int b = blockIdx.x;
     if (threadIdx.x != 0) return;
     const CropRec r0 = rec_in[b];
-    float c2[3];
-    refined_centre(cam, com_in + b * 3, net_out + b * 3, cube + b * 3, frames + (size_t)b * H * W, H, W, r0, c2);
+    const bool idle = track_gated(gate, b);
     const float c1[3] = {com_in[b * 3], com_in[b * 3 + 1], com_in[b * 3 + 2]};
-    const bool lost = com_ill_defined(c2) || com_ill_defined(c1);            // (a frame queued behind a lost one stays lost)
-    for (int d = 0; d < 3; ++d) com_out[b * 3 + d] = c2[d];
-    status[b] = lost ? 1 : 0;
+    float c2[3] = {c1[0], c1[1], c1[2]};                                     // a gated track keeps its centre
+    if (!idle) refined_centre(cam, com_in + b * 3, net_out + b * 3, cube + b * 3, frames + (size_t)track_source(src, b) * H * W, H, W, r0, c2);
+    const bool lost = !idle && (com_ill_defined(c2) || com_ill_defined(c1));  // (a frame queued behind a lost one stays lost)
+    if (!idle || com_out != com_in) { for (int d = 0; d < 3; ++d) com_out[b * 3 + d] = c2[d]; }
+    status[b] = idle ? TRACK_IDLE : lost ? TRACK_LOST : TRACK_OK;
     float* M = M_out ? M_out + (size_t)b * 9 : nullptr;
     CropRec r;
     float q3[3] = {0.f, 0.f, 0.f};
-    if (lost) {
+    if (lost || idle) {
         crop_empty_record(r0.min_depth, r0.max_depth, r, M);
     } else {
         crop_geometry(r0.min_depth, r0.max_depth, c2, cube + b * 3, fx, fy, dsz, 0, r, M);
@@ -517,14 +539,16 @@ __global__ __launch_bounds__(DPP_WAVE) void track_refine_kernel(const float* __r
 // negated), bit 1 config['invX'] (column 1, as the reference has it), bit 2 config['invY'] (column 0).  One thread per joint.
 __global__ __launch_bounds__(DPP_THREADS) void pose_finish_kernel(const float* __restrict__ net_out, int B, int J, const float* __restrict__ cube,
                                                                   const float* __restrict__ com3d, AugCam cam, int flags,
-                                                                  float* __restrict__ pose3d, float* __restrict__ pose_img) {
+                                                                  const int* __restrict__ tflags, float* __restrict__ pose3d,
+                                                                  float* __restrict__ pose_img) {
     const int i = blockIdx.x * DPP_THREADS + threadIdx.x;
     if (i >= B * J) return;
     const int b = i / J;
+    if (tflags) flags = tflags[b];                                     // the row's own sign rules
     float p[3] = {net_out[(size_t)i * 3], net_out[(size_t)i * 3 + 1], net_out[(size_t)i * 3 + 2]};
-    if (flags & 2) p[1] = -p[1];
-    if (flags & 4) p[0] = -p[0];
-    if (flags & 1) p[0] = -p[0];
+    if (flags & POSE_INV_X) p[1] = -p[1];
+    if (flags & POSE_INV_Y) p[0] = -p[0];
+    if (flags & POSE_HAND_RIGHT) p[0] = -p[0];
     const float cz = cube[b * 3 + 2];
     float q[3];
     for (int d = 0; d < 3; ++d) {
@@ -616,7 +640,7 @@ extern "C" int dpp_crop_warp(const float* frames, const void* records, int B, in
     if (!frames || !records || !out || B < 1 || H < 1 || W < 1 || dsz < 1) return DPP_E_BADARG;
     dim3 grid(dpp_cdiv(dsz * dsz, DPP_THREADS), B);
     DPP_LAUNCH(crop_warp_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
-                       static_cast<const CropRec*>(records), dsz, normalize, nd_value, out);
+                       static_cast<const CropRec*>(records), dsz, normalize, nd_value, static_cast<const int*>(nullptr), out);
     return dpp_launch_status();
 }
 
@@ -649,13 +673,18 @@ extern "C" int dpp_crop_refine(const float* frames, const void* records, int B, 
     return dpp_launch_status();
 }
 
+static int launch_crop_warp_ex(const float* frames, const void* records, int B, int H, int W, int dsz, int flags, float nd_value,
+                               float fill_value, float pad_value, const int* src, const int* tflags, float* out, dpp_stream_t stream) {
+    dim3 grid(dpp_cdiv(dsz * dsz, DPP_THREADS), B);
+    DPP_LAUNCH(crop_warp_ex_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
+               static_cast<const CropRec*>(records), dsz, flags, nd_value, fill_value, pad_value, src, tflags, out);
+    return dpp_launch_status();
+}
+
 extern "C" int dpp_crop_warp_ex(const float* frames, const void* records, int B, int H, int W, int dsz, int flags, float nd_value,
                                 float fill_value, float pad_value, float* out, dpp_stream_t stream) {
     if (!frames || !records || !out || B < 1 || H < 1 || W < 1 || dsz < 1 || (flags & ~31)) return DPP_E_BADARG;
-    dim3 grid(dpp_cdiv(dsz * dsz, DPP_THREADS), B);
-    DPP_LAUNCH(crop_warp_ex_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
-               static_cast<const CropRec*>(records), dsz, flags, nd_value, fill_value, pad_value, out);
-    return dpp_launch_status();
+    return launch_crop_warp_ex(frames, records, B, H, W, dsz, flags, nd_value, fill_value, pad_value, nullptr, nullptr, out, stream);
 }
 
 extern "C" int dpp_resize_crops(const float* src, int B, int sh, int sw, int dh, int dw, int bilinear, float nd_value, float* out,
@@ -698,11 +727,31 @@ extern "C" int dpp_frame_range(const float* frames, int B, int H, int W, float* 
     return dpp_launch_status();
 }
 
-extern "C" int dpp_crop_prepare_ranged(const float* partial, int B, const float* com, const float* cube, double fx, double fy, int dsz,
-                                       int stretch, void* records, float* M_out, dpp_stream_t stream) {
+static int launch_crop_prepare_ranged(const float* partial, int B, const float* com, const float* cube, double fx, double fy, int dsz,
+                                      int stretch, const int* src, const int* gate, void* records, float* M_out, dpp_stream_t stream) {
     if (!partial || !com || !cube || !records || B < 1 || dsz < 1 || fx == 0.0 || fy == 0.0) return DPP_E_BADARG;
     DPP_LAUNCH(crop_prepare_ranged_kernel, dim3(B), dim3(DPP_WAVE), 0, static_cast<hipStream_t>(stream), partial, com, cube, fabs(fx), fabs(fy),
-               dsz, stretch, static_cast<CropRec*>(records), M_out);
+               dsz, stretch, src, gate, static_cast<CropRec*>(records), M_out);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_crop_prepare_ranged(const float* partial, int B, const float* com, const float* cube, double fx, double fy, int dsz,
+                                       int stretch, void* records, float* M_out, dpp_stream_t stream) {
+    return launch_crop_prepare_ranged(partial, B, com, cube, fx, fy, dsz, stretch, nullptr, nullptr, records, M_out, stream);
+}
+
+static int launch_track_refine(const float* frames, const void* records_in, int B, int H, int W, const float* com_in, const float* cube,
+                               const float* net_out, double fx, double fy, double ux, double uy, int flip_y, double crop_fx, double crop_fy,
+                               int dsz, const int* src, const int* gate, float* com_out, float* com3d_out, void* records_out, float* M_out,
+                               int* status, dpp_stream_t stream) {
+    if (!frames || !records_in || !com_in || !cube || !net_out || !com_out || !com3d_out || !records_out || !status || B < 1 || H < 1 ||
+        W < 1 || dsz < 1 || fx == 0.0 || fy == 0.0 || crop_fx == 0.0 || crop_fy == 0.0)
+        return DPP_E_BADARG;
+    AugCam cam;
+    cam.fx = fx; cam.fy = fy; cam.ux = ux; cam.uy = uy; cam.flip_y = flip_y;
+    DPP_LAUNCH(track_refine_kernel, dim3(B), dim3(DPP_WAVE), 0, static_cast<hipStream_t>(stream), frames, H, W,
+               static_cast<const CropRec*>(records_in), com_in, cube, net_out, cam, fabs(crop_fx), fabs(crop_fy), dsz, src, gate, com_out,
+               com3d_out, static_cast<CropRec*>(records_out), M_out, status);
     return dpp_launch_status();
 }
 
@@ -710,25 +759,23 @@ extern "C" int dpp_track_refine(const float* frames, const void* records_in, int
                                 const float* net_out, double fx, double fy, double ux, double uy, int flip_y, double crop_fx, double crop_fy,
                                 int dsz, float* com_out, float* com3d_out, void* records_out, float* M_out, int* status,
                                 dpp_stream_t stream) {
-    if (!frames || !records_in || !com_in || !cube || !net_out || !com_out || !com3d_out || !records_out || !status || B < 1 || H < 1 ||
-        W < 1 || dsz < 1 || fx == 0.0 || fy == 0.0 || crop_fx == 0.0 || crop_fy == 0.0)
-        return DPP_E_BADARG;
+    return launch_track_refine(frames, records_in, B, H, W, com_in, cube, net_out, fx, fy, ux, uy, flip_y, crop_fx, crop_fy, dsz, nullptr,
+                               nullptr, com_out, com3d_out, records_out, M_out, status, stream);
+}
+
+static int launch_pose_finish(const float* net_out, int B, int J, const float* cube, const float* com3d, double fx, double fy, double ux,
+                              double uy, int flip_y, int flags, const int* tflags, float* pose3d, float* pose_img, dpp_stream_t stream) {
+    if (!net_out || !cube || !com3d || !pose3d || !pose_img || B < 1 || J < 1 || fx == 0.0 || fy == 0.0 || (flags & ~7)) return DPP_E_BADARG;
     AugCam cam;
     cam.fx = fx; cam.fy = fy; cam.ux = ux; cam.uy = uy; cam.flip_y = flip_y;
-    DPP_LAUNCH(track_refine_kernel, dim3(B), dim3(DPP_WAVE), 0, static_cast<hipStream_t>(stream), frames, H, W,
-               static_cast<const CropRec*>(records_in), com_in, cube, net_out, cam, fabs(crop_fx), fabs(crop_fy), dsz, com_out, com3d_out,
-               static_cast<CropRec*>(records_out), M_out, status);
+    DPP_LAUNCH(pose_finish_kernel, dim3(dpp_cdiv(B * J, DPP_THREADS)), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), net_out, B, J,
+               cube, com3d, cam, flags, tflags, pose3d, pose_img);
     return dpp_launch_status();
 }
 
 extern "C" int dpp_pose_finish(const float* net_out, int B, int J, const float* cube, const float* com3d, double fx, double fy, double ux,
                                double uy, int flip_y, int flags, float* pose3d, float* pose_img, dpp_stream_t stream) {
-    if (!net_out || !cube || !com3d || !pose3d || !pose_img || B < 1 || J < 1 || fx == 0.0 || fy == 0.0 || (flags & ~7)) return DPP_E_BADARG;
-    AugCam cam;
-    cam.fx = fx; cam.fy = fy; cam.ux = ux; cam.uy = uy; cam.flip_y = flip_y;
-    DPP_LAUNCH(pose_finish_kernel, dim3(dpp_cdiv(B * J, DPP_THREADS)), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), net_out, B, J,
-               cube, com3d, cam, flags, pose3d, pose_img);
-    return dpp_launch_status();
+    return launch_pose_finish(net_out, B, J, cube, com3d, fx, fy, ux, uy, flip_y, flags, nullptr, pose3d, pose_img, stream);
 }
 
 extern "C" int dpp_refine_com_iterative(const float* frames, const float* partial, int B, int H, int W, const float* com_in, const float* cube,
@@ -738,4 +785,41 @@ extern "C" int dpp_refine_com_iterative(const float* frames, const float* partia
     DPP_LAUNCH(refine_com_iterative_kernel, dim3(B), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W, partial, com_in, cube,
                fabs(fx), fabs(fy), num_iter, com_out, status);
     return dpp_launch_status();
+}
+
+// ---- several tracks over several frames (ABI v16): the five tracking launches with one (src, gate, tflags) entry per track ----------
+extern "C" int dpp_crop_prepare_ranged_ix(const float* partial, int T, const int* src, const int* gate, const float* com, const float* cube,
+                                          double fx, double fy, int dsz, int stretch, void* records, float* M_out, dpp_stream_t stream) {
+    if (!src || !gate) return DPP_E_BADARG;
+    return launch_crop_prepare_ranged(partial, T, com, cube, fx, fy, dsz, stretch, src, gate, records, M_out, stream);
+}
+
+extern "C" int dpp_crop_warp_ix(const float* frames, const void* records, int T, const int* src, int H, int W, int dsz, int normalize,
+                                float nd_value, float* out, dpp_stream_t stream) {
+    if (!frames || !records || !src || !out || T < 1 || H < 1 || W < 1 || dsz < 1) return DPP_E_BADARG;
+    dim3 grid(dpp_cdiv(dsz * dsz, DPP_THREADS), T);
+    DPP_LAUNCH(crop_warp_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
+               static_cast<const CropRec*>(records), dsz, normalize, nd_value, src, out);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_track_refine_ix(const float* frames, const void* records_in, int T, const int* src, const int* gate, int H, int W,
+                                   const float* com_in, const float* cube, const float* net_out, double fx, double fy, double ux, double uy,
+                                   int flip_y, double crop_fx, double crop_fy, int dsz, float* com_out, float* com3d_out, void* records_out,
+                                   float* M_out, int* status, dpp_stream_t stream) {
+    if (!src || !gate) return DPP_E_BADARG;
+    return launch_track_refine(frames, records_in, T, H, W, com_in, cube, net_out, fx, fy, ux, uy, flip_y, crop_fx, crop_fy, dsz, src, gate,
+                               com_out, com3d_out, records_out, M_out, status, stream);
+}
+
+extern "C" int dpp_crop_warp_ex_ix(const float* frames, const void* records, int T, const int* src, const int* tflags, int H, int W, int dsz,
+                                   int flags, float nd_value, float fill_value, float pad_value, float* out, dpp_stream_t stream) {
+    if (!frames || !records || !src || !tflags || !out || T < 1 || H < 1 || W < 1 || dsz < 1 || (flags & ~15)) return DPP_E_BADARG;
+    return launch_crop_warp_ex(frames, records, T, H, W, dsz, flags, nd_value, fill_value, pad_value, src, tflags, out, stream);
+}
+
+extern "C" int dpp_pose_finish_ix(const float* net_out, int T, int J, const int* tflags, const float* cube, const float* com3d, double fx,
+                                  double fy, double ux, double uy, int flip_y, float* pose3d, float* pose_img, dpp_stream_t stream) {
+    if (!tflags) return DPP_E_BADARG;
+    return launch_pose_finish(net_out, T, J, cube, com3d, fx, fy, ux, uy, flip_y, 0, tflags, pose3d, pose_img, stream);
 }

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(os.path.dirname(_HERE), 'lib', 'libdpp_hip.so')
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 ST_A, ST_B, ST_C, ST_BNX = 1, 2, 4, 8      # DPP_ST_*: which pointers of a call address bf16-stored activation tensors
 c_float_p = C.c_void_p      # device pointers travel as integers
 stream_t = C.c_void_p
@@ -190,6 +190,16 @@ SIGNATURES = {
                          [C.c_int, C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 5 + [stream_t]),
     'dpp_pose_finish': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_double] * 4 + [C.c_int, C.c_int, C.c_void_p,
                                                                                                               C.c_void_p, stream_t]),
+    'dpp_crop_prepare_ranged_ix': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int,
+                                             C.c_int, C.c_void_p, C.c_void_p, stream_t]),
+    'dpp_crop_warp_ix': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                   stream_t]),
+    'dpp_track_refine_ix': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 5 + [stream_t]),
+    'dpp_crop_warp_ex_ix': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                      C.c_float, C.c_float, C.c_void_p, stream_t]),
+    'dpp_pose_finish_ix': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_double] * 4 +
+                           [C.c_int, C.c_void_p, C.c_void_p, stream_t]),
     'dpp_refine_com_iterative': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                            C.c_int, C.c_void_p, C.c_void_p, stream_t]),
     'dpp_frame_ingest': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, stream_t]),

@@ -1,0 +1,239 @@
+"""
+Realtime tracking of several hands over several cameras: T tracks over C frame sources, ONE launch plan per tick.
+
+hipdp/tracker.py's plan follows one hand in one camera's frames.  At a batch of one the two nets are bound by their launches, not
+by arithmetic, so a second hand (or a second camera) served by a second HandTracker pays the whole plan, an upload and a download
+again.  Here every launch of that plan runs once per tick for all tracks:
+
+    frame_range (or frame_ingest)   at B = C       every source's depth range, the one pass over each frame
+    crop_prepare_ranged_ix          at B = T       track t's window in frame src[t], from that frame's partials
+    crop_warp_ix -> crop_center x2  at B = T       the refinement net's inputs
+    the refinement net's forward plan, built for a batch of T
+    track_refine_ix                 at B = T       centre update, final record, M, com3D, status; the T centres stay on the device
+    crop_warp_ex_ix                 at B = T       the final crop, mirrored where tflags[t] has POSE_HAND_RIGHT
+    the pose net's forward plan, built for a batch of T
+    pose_finish_ix                  at B = T       the sign rules per track from tflags[t]
+
+so the launch count is HandTracker's whatever T and C are.  A track names its source (`src`), its hand side and invX / invY
+(`tflags`) and whether it takes part in this tick (`gate`) in three small int32 device arrays; the hand side is data, not a launch
+argument, so there is one plan, not one per flag combination.  C cameras with one hand each is tracks = [(c, False) for c in
+range(C)]; both hands of one camera is tracks = [(0, False), (0, True)]; mixtures are allowed.
+
+GATING.  A track sits a tick out (gate 0) when it is lost, was never started, or its source delivered no frame.  Its row still runs
+through the nets (on an all-zero crop), its centre's bits stay as they are, and it is reported IDLE -- or LOST, when that is why it
+was gated.  A lost track does not stop the others; it stays gated until reset(t, com) or a successful acquire(t, frame).
+
+One importer (camera) serves all sources: the camera is a launch argument.  Per-source intrinsics are out of scope here, and so are
+the overlapped process_sequence form for several sources and a detector that returns two hands (DESIGN.md names them as follow-ups).
+"""
+import numpy as np
+
+from . import ops
+from .augmenter import camera_tuple
+from .tracker import IDLE, LOST, OK, _engine, refine_stage
+
+
+class MultiTracker(object):
+    def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, tracks, sources=None, invX=False, invY=False, fx=None, fy=None,
+                 sensor=None):
+        """
+        :param importer:   the dataset importer: ONE camera for all sources (per-source intrinsics are out of scope)
+        :param poseNet, comrefNet: as for HandTracker, but built for a batch of len(tracks): row t is track t
+        :param H, W:       frame size, the same for all sources
+        :param cube:       metric cube (mm) every track starts with (set_cube(t, cube) changes one)
+        :param tracks:     list of (source, hand_right): track t follows one hand in the frames of source `source`
+        :param sources:    number of frame sources C (default: the largest source named, plus one); C <= T, every track reads one source
+        :param invX, invY: estimatePose's mirroring, for all tracks
+        :param fx, fy:     what the reference hands to HandDetector; default: the importer's
+        :param sensor:     as for HandTracker, for ALL sources: frames are raw sensor frames and frame_ingest runs at B = C
+        """
+        self.rt, self.H, self.W = rt, int(H), int(W)
+        tracks = [(int(s), bool(r)) for s, r in tracks]
+        if not tracks:
+            raise ValueError("MultiTracker needs at least one track")
+        self.T = T = len(tracks)
+        self.C = C = int(max(s for s, _ in tracks) + 1 if sources is None else sources)
+        self.src_host = ops.track_index([s for s, _ in tracks], C)           # the kernels trust it: checked here
+        if C > T:
+            raise ValueError("%d sources for %d tracks: every source needs a track that reads it" % (C, T))
+        self.importer = importer
+        self.cam = camera_tuple(importer)
+        self.fx = abs(float(importer.fx if fx is None else fx))
+        self.fy = abs(float(importer.fy if fy is None else fy))
+        self.ceng = _engine(comrefNet, rt, 'comrefNet', T, "one row per track")
+        self.peng = _engine(poseNet, rt, 'poseNet', T, "one row per track")
+        if len(self.peng.x_ins) != 1 or self.peng.out_dim % 3:
+            raise ValueError("the pose net takes one crop and regresses J x 3 coordinates")
+        self.rs, self.ds, self.J = int(self.ceng.x_ins[0].shape[1]), int(self.peng.x_in.shape[1]), self.peng.out_dim // 3
+        f32, i32 = np.float32, np.int32
+        J3 = self.J * 3
+        self.frames = rt.alloc((C, self.H, self.W), f32, zero=False)
+        self.sensor = None if sensor is None else ops.sensor_spec(sensor)
+        self.raw = None if sensor is None else rt.alloc((C, self.H, self.W), self.sensor[0], zero=False)
+        self.inputs = self.frames if sensor is None else self.raw                 # what the host uploads into
+        self.partial = ops.frame_range_workspace(rt, C)
+        self._pstride = self.partial.size // C
+        self.rec = rt.alloc(T * rt.lib.dpp_crop_record_bytes(), np.uint8)
+        self.cube = rt.alloc((T, 3), f32)
+        ix = rt.alloc((3, T), i32)                                                 # src, gate (all zero: nobody has started), tflags
+        self.src, self.gate, self.tflags = ix.view(0, (T,)), ix.view(T, (T,)), ix.view(2 * T, (T,))
+        self.src.set(self.src_host)
+        # everything the host reads per tick is ONE block, every entry an array over the tracks (the launches write [T][...] arrays):
+        # pose (mm), pose in image coordinates, centres (= the state), com3D, M, status (+ one detector's 8 words: acquire)
+        self._off = off = dict(pose=0, pose_img=T * J3, com=2 * T * J3, com3D=2 * T * J3 + 3 * T, M=2 * T * J3 + 6 * T,
+                               status=2 * T * J3 + 15 * T, det=2 * T * J3 + 16 * T)
+        self.res = rt.alloc(off['det'] + 8, f32)
+        self.pose3d, self.pose_img = self.res.view(off['pose'], (T, self.J, 3)), self.res.view(off['pose_img'], (T, self.J, 3))
+        self.com, self.com3d = self.res.view(off['com'], (T, 3)), self.res.view(off['com3D'], (T, 3))
+        self.M, self.status = self.res.view(off['M'], (T, 9)), self.res.view(off['status'], (T,), i32)
+        self.crop = self.peng.x_in.buf.reshape(T, self.ds, self.ds)             # the pose net's input IS the final crops
+        self.flags_host = np.zeros(T, i32)
+        self.flags_host[:] = (ops.POSE_INV_X if invX else 0) | (ops.POSE_INV_Y if invY else 0)
+        for t, (_, right) in enumerate(tracks):
+            if right:
+                self.flags_host[t] |= ops.POSE_HAND_RIGHT
+        self.tflags.set(self.flags_host)
+        self.gate_host = np.zeros(T, i32)                                          # what the device holds
+        self.lost = np.ones(T, bool)                                               # no centre yet
+        self.cube_host = np.zeros((T, 3), f32)
+        for t in range(T):
+            self.set_cube(t, cube)
+        self._plan = None
+        self._detectors = {}
+        self.runs = 0
+
+    # ---- device state -----------------------------------------------------------------------------------------------------
+    def _track(self, t):
+        t = int(t)
+        if not 0 <= t < self.T:
+            raise IndexError("track %d of %d" % (t, self.T))
+        return t
+
+    def reset(self, t, com):
+        """Start track t (again) from the centre `com` (image coordinates of its source, z in mm)."""
+        t = self._track(t)
+        com = np.asarray(com, np.float32).reshape(3)
+        if not np.all(np.isfinite(com)) or np.isclose(com[2], 0.):
+            raise ValueError("reset needs a centre with a depth: %r" % (com,))
+        self.com.view(3 * t, (1, 3)).set(com)
+        self.lost[t] = False
+
+    def set_cube(self, t, cube):
+        t = self._track(t)
+        cube = np.asarray(cube, np.float32).reshape(3)
+        if not (cube > 0).all():
+            raise ValueError("the cube must have a positive size: %r" % (cube,))
+        self.cube.view(3 * t, (1, 3)).set(cube)
+        self.cube_host[t] = cube
+
+    def set_hand(self, t, right):
+        """HAND_RIGHT mirrors track t's pose-net input and the x coordinate of its output: a rewrite of tflags[t], not a new plan."""
+        t = self._track(t)
+        self.flags_host[t] = (self.flags_host[t] & ~ops.POSE_HAND_RIGHT) | (ops.POSE_HAND_RIGHT if right else 0)
+        self.tflags.set(self.flags_host)
+
+    def detector(self, t):
+        """The whole-frame detector at B = 1 on views of track t's buffers: its source's frame (and raw frame), that frame's
+        depth-range partials, the track's centre (the detector's output) and cube."""
+        t = self._track(t)
+        if t not in self._detectors:
+            from .detect import FrameDetector
+            c, px = int(self.src_host[t]), self.H * self.W
+            self._detectors[t] = FrameDetector(
+                self.rt, self.H, self.W, self.fx, self.fy, 1, frames=self.frames.view(c * px, (1, self.H, self.W)),
+                partial=self.partial.view(c * self._pstride, (self._pstride,)), com=self.com.view(3 * t, (1, 3)),
+                cube=self.cube.view(3 * t, (1, 3)), res=self.res.view(self._off['det'], (8,)),
+                sensor=None if self.sensor is None else dict(zip(('dtype', 'median', 'mirror'), self.sensor)),
+                raw=None if self.sensor is None else self.raw.view(c * px, (1, self.H, self.W)))
+        return self._detectors[t]
+
+    def acquire(self, t, frame, do_hand_size=False):
+        """Find a hand in `frame` of track t's source and start track t (again) from it, as HandTracker.acquire does: one upload, the
+        detector plan, one download of the result block.  The detector finds the NEAREST object of the frame: of two hands on one
+        source it finds the same one for both tracks, so the second hand of a source is seeded with reset(t, com).  Returns
+        dict(com, cube, found); not found: the centre is (0, 0, 0) and the track stays lost."""
+        t = self._track(t)
+        frame = self._frame(frame)
+        det = self.detector(t)
+        c = int(self.src_host[t])
+        self.inputs.view(c * self.H * self.W, (1, self.H, self.W)).set(frame)
+        det.plan(do_hand_size).run(self.rt)
+        self.rt.synchronize()
+        res, o = self.res.get(), self._off
+        coms, cubes, found, _, _ = det.parse(res[o['det']:], res[o['com'] + 3 * t:o['com'] + 3 * t + 3], None if do_hand_size else self.cube_host[t])
+        ok = bool(found[0]) and bool(np.all(np.isfinite(coms[0]))) and not np.isclose(coms[0][2], 0.)
+        self.lost[t] = not ok
+        return dict(com=coms[0], cube=cubes[0], found=ok)
+
+    # ---- the per-tick plan --------------------------------------------------------------------------------------------------
+    def plan(self):
+        if self._plan is None:
+            rt, H, W, T, C, fr = self.rt, self.H, self.W, self.T, self.C, self.frames
+            p = ops.Plan('multitrack')
+            if self.sensor is None:
+                p.add(ops.frame_range(rt, fr, C, H, W, self.partial))
+            else:
+                p.add(ops.frame_ingest(rt, self.raw, C, H, W, fr, self.partial, median=self.sensor[1], mirror=self.sensor[2]))
+            # the T centres are read (prepare, track_refine) and then rewritten by one lane per track of track_refine: in place
+            for op, side in refine_stage(rt, fr, H, W, self.partial, self.rec, self.com, self.cube, self.ceng, self.cam, self.fx, self.fy,
+                                         self.ds, self.com, self.com3d, self.rec, self.status, self.M, tracks=(T, self.src, self.gate)):
+                p.add(op, side)
+            p.add(ops.crop_warp_ex_ix(rt, fr, self.rec, T, self.src, self.tflags, H, W, self.ds, self.crop, flags=ops.CROP_NORMALIZE,
+                                      nd_value=0.0, name='track_crop'))
+            for op, side in self.peng.fwd.ops:
+                p.add(op, side)
+            p.add(ops.pose_finish_ix(rt, self.peng.out.buf, T, self.J, self.tflags, self.cube, self.com3d, self.cam, self.pose3d, self.pose_img))
+            self._plan = p
+        return self._plan
+
+    def _frame(self, frame):
+        if self.sensor is None:
+            frame = np.asarray(frame, np.float32)
+        else:                                       # a raw frame is taken as it is or not at all: no silent conversion
+            frame = np.asarray(frame)
+            if frame.dtype != self.sensor[0]:
+                raise ValueError("frame dtype %s, the tracker's sensor delivers %s" % (frame.dtype, self.sensor[0]))
+        if frame.shape != (self.H, self.W):
+            raise ValueError("frame shape %s, expected %s" % (frame.shape, (self.H, self.W)))
+        return frame
+
+    def _results(self, res, gate, crops=None):
+        o, T, J = self._off, self.T, self.J
+        st = res[o['status']:o['status'] + T].view(np.int32)
+        pose, pimg = res[:o['pose_img']].reshape(T, J, 3), res[o['pose_img']:o['com']].reshape(T, J, 3)
+        com, com3d = res[o['com']:o['com3D']].reshape(T, 3), res[o['com3D']:o['M']].reshape(T, 3)
+        M = res[o['M']:o['status']].reshape(T, 3, 3)
+        out = []
+        for t in range(T):
+            status = int(st[t])
+            if not gate[t]:                          # gated because it is lost (or never started): LOST; because its source idles: IDLE
+                status = LOST if self.lost[t] else IDLE
+            else:
+                self.lost[t] = status != OK
+            d = dict(pose=pose[t], pose_img=pimg[t], com=com[t], com3D=com3d[t], M=M[t], status=status)
+            if crops is not None:
+                d['crop'] = crops[t]
+            out.append(d)
+        return out
+
+    def process(self, frames, return_crop=False):
+        """One tick: `frames` has one entry per source, None where that source has no new frame.  The fresh frames are uploaded (one
+        upload each; `gate` too, only when it differs from the last tick's), ONE plan runs, ONE block is downloaded.  Returns one
+        dict per track with HandTracker.process's keys.  status OK: the track was followed.  IDLE: its source had no frame, its
+        centre is unchanged.  LOST: it lost the hand in this tick, or is refused (lost before, or never started) until reset(t,
+        com) / acquire(t, frame).  For IDLE and LOST the other entries are finite but meaningless."""
+        if len(frames) != self.C:
+            raise ValueError("%d frames for %d sources" % (len(frames), self.C))
+        fresh = [None if f is None else self._frame(f) for f in frames]
+        gate = np.array([int(not self.lost[t] and fresh[self.src_host[t]] is not None) for t in range(self.T)], np.int32)
+        px = self.H * self.W
+        for c, f in enumerate(fresh):
+            if f is not None:
+                self.inputs.view(c * px, (1, self.H, self.W)).set(f)
+        if not np.array_equal(gate, self.gate_host):
+            self.gate.set(gate)
+            self.gate_host = gate
+        self.plan().run(self.rt)
+        self.runs += 1
+        self.rt.synchronize()
+        return self._results(self.res.get(), gate, self.crop.get() if return_crop else None)

@@ -785,6 +785,57 @@ def pose_finish(rt, net_out, B, J, cube, com3d, cam, flags, pose3d, pose_img, na
                   (net_out, cube, com3d, pose3d, pose_img), name)
 
 
+TRACK_OK, TRACK_LOST, TRACK_IDLE = 0, 1, 2           # DPP_TRACK_*: dpp_track_refine's status word
+
+
+def track_index(src, C):
+    """The host's check of a `src` array (the kernels trust it): int32, every entry a frame of [0, C)."""
+    src = np.ascontiguousarray(src, np.int32).reshape(-1)
+    if src.size < 1 or src.min() < 0 or src.max() >= int(C):
+        raise ValueError("every track reads one of the %d frame sources: %r" % (C, src.tolist()))
+    return src
+
+
+# The five tracking launches for T tracks over C frames: src / gate / tflags are int32 device arrays with one entry per track
+# (include/dpp_hip.h, ABI v16).  The caller has checked `src` with track_index before uploading it.
+def crop_prepare_ranged_ix(rt, partial, T, src, gate, com, cube, fx, fy, dsz, records, M_out=None, stretch=False, name='crop_prepare_ranged'):
+    return Launch(rt.lib.dpp_crop_prepare_ranged_ix, (partial.ptr, T, src.ptr, gate.ptr, com.ptr, cube.ptr, float(fx), float(fy), dsz,
+                                                      int(bool(stretch)), records.ptr, _p(M_out)),
+                  (partial, src, gate, com, cube, records, M_out), name)
+
+
+def crop_warp_ix(rt, frames, records, T, src, H, W, dsz, out, normalize=True, nd_value=0.0, name='crop_warp'):
+    return Launch(rt.lib.dpp_crop_warp_ix, (frames.ptr, records.ptr, T, src.ptr, H, W, dsz, int(bool(normalize)), float(nd_value), out.ptr),
+                  (frames, records, src, out), name, dict(kernel='crop_warp', flops=10.0 * T * dsz * dsz, bytes=8.0 * T * dsz * dsz))
+
+
+def track_refine_ix(rt, frames, records_in, T, src, gate, H, W, com_in, cube, net_out, cam, crop_fx, crop_fy, dsz, com_out, com3d_out,
+                    records_out, status, M_out=None, name='track_refine'):
+    fx, fy, ux, uy, flip = cam
+    return Launch(rt.lib.dpp_track_refine_ix,
+                  (frames.ptr, records_in.ptr, T, src.ptr, gate.ptr, H, W, com_in.ptr, cube.ptr, net_out.ptr, float(fx), float(fy), float(ux),
+                   float(uy), int(flip), float(crop_fx), float(crop_fy), dsz, com_out.ptr, com3d_out.ptr, records_out.ptr, _p(M_out), status.ptr),
+                  (frames, records_in, src, gate, com_in, cube, net_out, com_out, com3d_out, records_out, M_out, status), name)
+
+
+def crop_warp_ex_ix(rt, frames, records, T, src, tflags, H, W, dsz, out, flags=0, nd_value=0.0, fill_value=None, pad_value=0.0,
+                    name='crop_warp_ex'):
+    """dpp_crop_warp_ex_ix: CROP_FLIP_X comes per track from tflags[t] & POSE_HAND_RIGHT, the other flags hold for all tracks."""
+    fill = float(nd_value) if fill_value is None else float(fill_value)
+    taps = 4 if flags & CROP_BILINEAR else 1
+    return Launch(rt.lib.dpp_crop_warp_ex_ix, (frames.ptr, records.ptr, T, src.ptr, tflags.ptr, H, W, dsz, int(flags), float(nd_value), fill,
+                                               float(pad_value), out.ptr),
+                  (frames, records, src, tflags, out), name,
+                  dict(kernel='crop_warp', flops=(30.0 if taps == 4 else 10.0) * T * dsz * dsz, bytes=(4.0 * taps + 4.0) * T * dsz * dsz))
+
+
+def pose_finish_ix(rt, net_out, T, J, tflags, cube, com3d, cam, pose3d, pose_img, name='pose_finish'):
+    fx, fy, ux, uy, flip = cam
+    return Launch(rt.lib.dpp_pose_finish_ix, (net_out.ptr, T, J, tflags.ptr, cube.ptr, com3d.ptr, float(fx), float(fy), float(ux), float(uy),
+                                              int(flip), pose3d.ptr, pose_img.ptr),
+                  (net_out, tflags, cube, com3d, pose3d, pose_img), name)
+
+
 def refine_com_iterative(rt, frames, partial, B, H, W, com_in, cube, fx, fy, num_iter, com_out, status, name='refine_com_iterative'):
     """dpp_refine_com_iterative: refineCoMIterative of B frames, all iterations in one launch."""
     return Launch(rt.lib.dpp_refine_com_iterative, (frames.ptr, partial.ptr, B, H, W, com_in.ptr, cube.ptr, float(fx), float(fy), int(num_iter),

@@ -40,7 +40,7 @@ import numpy as np
 from . import ops
 from .augmenter import camera_tuple
 
-OK, LOST = 0, 1
+OK, LOST, IDLE = ops.TRACK_OK, ops.TRACK_LOST, ops.TRACK_IDLE
 
 
 def _net_side(net):
@@ -49,34 +49,50 @@ def _net_side(net):
     return int(d0[2])
 
 
-def _engine_b1(net, rt, what):
+def _engine(net, rt, what, batch, why):
     net.setDeterministic()
     eng = net._engine(rt)
-    if eng.N != 1:
-        raise ValueError("%s must be built for a batch of one (batchSize=%d): one frame is one plan" % (what, eng.N))
+    if eng.N != batch:
+        raise ValueError("%s must be built for a batch of %s (batchSize=%d): %s" % (what, 'one' if batch == 1 else batch, eng.N, why))
     if any(t.shape[3] != 1 for t in eng.x_ins):
         raise ValueError("%s must take single-channel depth crops" % what)
     return eng
 
 
-def refine_stage(rt, frame, H, W, partial, rec, com_in, cube, ceng, cam, fx, fy, dsz_final, com_out, com3d, rec_out, status, M=None):
+def _engine_b1(net, rt, what):
+    return _engine(net, rt, what, 1, "one frame is one plan")
+
+
+def refine_stage(rt, frame, H, W, partial, rec, com_in, cube, ceng, cam, fx, fy, dsz_final, com_out, com3d, rec_out, status, M=None, tracks=None):
     """The (op, side) list of HandDetector.track for ONE frame whose depth-range partials are in `partial`: window around com_in,
-    the refinement net's inputs, its forward plan, track_refine.  Shared by HandTracker's plan and HandDetector.track."""
+    the refinement net's inputs, its forward plan, track_refine.  Shared by HandTracker's plan and HandDetector.track -- and, with
+    tracks = (T, src, gate) (int32 device arrays, one entry per track: hipdp/multitrack.py), by MultiTracker's plan: the same steps
+    for T tracks that each read frame src[t] of `frame` and its partials, through the indexed siblings of the three crop launches."""
     nin = len(ceng.x_ins)
     if nin not in (1, 3):
         raise NotImplementedError("Number of inputs is {}".format(nin))
     if ceng.out_dim != 3:
         raise ValueError("the refinement net must regress one 3-D offset")
     rs = int(ceng.x_ins[0].shape[1])
-    in0 = ceng.x_ins[0].buf.reshape(1, rs, rs)
-    out = [(ops.crop_prepare_ranged(rt, partial, 1, com_in, cube, fx, fy, rs, rec, None, stretch=True), False),
-           (ops.crop_warp(rt, frame, rec, 1, H, W, rs, in0, normalize=True, nd_value=0.0, name='track_in0'), False)]
+    B = 1 if tracks is None else int(tracks[0])
+    in0 = ceng.x_ins[0].buf.reshape(B, rs, rs)
+    if tracks is None:
+        out = [(ops.crop_prepare_ranged(rt, partial, 1, com_in, cube, fx, fy, rs, rec, None, stretch=True), False),
+               (ops.crop_warp(rt, frame, rec, 1, H, W, rs, in0, normalize=True, nd_value=0.0, name='track_in0'), False)]
+    else:
+        _, src, gate = tracks
+        out = [(ops.crop_prepare_ranged_ix(rt, partial, B, src, gate, com_in, cube, fx, fy, rs, rec, None, stretch=True), False),
+               (ops.crop_warp_ix(rt, frame, rec, B, src, H, W, rs, in0, normalize=True, nd_value=0.0, name='track_in0'), False)]
     for k in range(1, nin):                        # 1/2 and 1/4 CENTRE crops, handdetector.py:657-669
         f = 2 ** k
-        out.append((ops.crop_center(rt, in0, 1, rs, rs, ceng.x_ins[k].buf, rs // f, rs // f, name='track_in%d' % k), False))
+        out.append((ops.crop_center(rt, in0, B, rs, rs, ceng.x_ins[k].buf, rs // f, rs // f, name='track_in%d' % k), False))
     out.extend(ceng.fwd.ops)
-    out.append((ops.track_refine(rt, frame, rec, 1, H, W, com_in, cube, ceng.out.buf, cam, fx, fy, dsz_final, com_out, com3d, rec_out, status,
-                                 M_out=M), False))
+    if tracks is None:
+        out.append((ops.track_refine(rt, frame, rec, 1, H, W, com_in, cube, ceng.out.buf, cam, fx, fy, dsz_final, com_out, com3d, rec_out,
+                                     status, M_out=M), False))
+    else:
+        out.append((ops.track_refine_ix(rt, frame, rec, B, src, gate, H, W, com_in, cube, ceng.out.buf, cam, fx, fy, dsz_final, com_out,
+                                        com3d, rec_out, status, M_out=M), False))
     return out
 
 

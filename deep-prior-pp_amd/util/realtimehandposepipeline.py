@@ -31,6 +31,9 @@ routes see the same frame.
 A LOST track (the tracked centre's depth is close to 0: the reference would crop the middle of the frame through comToBounds'
 "CoM ill-defined" branch, which is not built) gives a zero crop, eye(3) and a zero com3D -- the answer of :326-327 -- and clears
 the last centre, so that the next frame needs a seed again.
+
+SEVERAL cameras and hands: MultiStreamPipeline (below) plays a list of devices through hipdp.multitrack.MultiTracker -- one device
+plan per tick for all tracks, with the same seeding rules per track.
 """
 import copy
 import time
@@ -384,3 +387,122 @@ class RealtimeHandposePipeline(object):
         self.sync.update(config=copy.deepcopy(self.initialconfig))
         self.detection.value = self.DETECTOR_COM
         self.lastcom = (0, 0, 0) if self.init_com is None else self.init_com.copy()
+
+
+class MultiStreamPipeline(object):
+    """Several cameras and hands through ONE device plan per tick (hipdp.multitrack.MultiTracker): the headless processVideo of
+    RealtimeHandposePipeline for a list of CameraDevices.  `hands` names the tracks, one (device index, hand) each with hand
+    HAND_LEFT / HAND_RIGHT: N cameras with one hand each, both hands of one camera, or a mixture.  Both nets are built for a batch
+    of len(hands).  All devices share the importer's camera and the frame size.
+
+    Seeds: init_com= one centre per track (image coordinates of its device, z in mm; None for a track without one), and / or
+    seed_detect=True: a track without a centre -- never seeded, or lost -- is searched for in its device's next frame by the
+    component detector (MultiTracker.acquire), as RealtimeHandposePipeline's _need_seed does after a lost frame.  The detector finds
+    the nearest object, so of two tracks on one device only the first is acquired that way; the other needs its init_com."""
+
+    HAND_LEFT, HAND_RIGHT = RealtimeHandposePipeline.HAND_LEFT, RealtimeHandposePipeline.HAND_RIGHT
+
+    def __init__(self, poseNet, config, di, devices, hands, comrefNet, init_com=None, seed_detect=False, sensor=None, verbose=False):
+        """
+        :param poseNet, comrefNet: built nets or their parameters (as for RealtimeHandposePipeline), with batchSize == len(hands)
+        :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=])
+        :param di:        depth importer (the one camera of all devices)
+        :param devices:   list of CameraDevice
+        :param hands:     list of (device index, HAND_LEFT | HAND_RIGHT), one per track
+        :param init_com:  None, or one centre (or None) per track
+        :param seed_detect: acquire tracks without a centre by detection, again after they are lost
+        :param sensor:    as for RealtimeHandposePipeline, for all devices
+        """
+        self.poseNet, self.comrefNet, self.importer = poseNet, comrefNet, di
+        self.config = copy.deepcopy(config)
+        self.devices = list(devices)
+        self.hands = [(int(d), int(h)) for d, h in hands]
+        if not self.hands or not self.devices:
+            raise ValueError("MultiStreamPipeline needs at least one device and one track")
+        if sorted(set(d for d, _ in self.hands)) != list(range(len(self.devices))):
+            raise ValueError("every device needs a track, every track a device: %d devices, tracks on %r"
+                             % (len(self.devices), sorted(set(d for d, _ in self.hands))))
+        init_com = [None] * len(self.hands) if init_com is None else list(init_com)
+        if len(init_com) != len(self.hands):
+            raise ValueError("init_com has one entry per track")
+        self.init_com = [None if c is None else numpy.asarray(c, numpy.float32).copy() for c in init_com]
+        self.seed_detect = bool(seed_detect)
+        if not self.seed_detect and any(c is None for c in self.init_com):
+            raise ValueError("a track without init_com needs seed_detect=True")
+        self.sensor = None if sensor is None else dict(sensor)
+        self.verbose = verbose
+        self.stop = _Value(False)
+        self._tracker = None
+        self._seeded = [False] * len(self.hands)
+
+    def initNets(self):
+        """Build the nets from their parameters and compile their forward plans: RealtimeHandposePipeline.initNets, at batch len(hands)."""
+        one = RealtimeHandposePipeline(self.poseNet, self.config, self.importer, comrefNet=self.comrefNet)
+        one.initNets()
+        self.poseNet, self.comrefNet = one.poseNet, one.comrefNet
+
+    def tracker(self, H, W):
+        from hipdp.multitrack import MultiTracker
+        from hipdp.runtime import default_runtime
+        if self._tracker is None or (self._tracker.H, self._tracker.W) != (H, W):
+            cfg = self.config
+            self._tracker = MultiTracker(default_runtime(), self.importer, self.poseNet, self.comrefNet, H, W, cfg['cube'],
+                                         [(d, h == self.HAND_RIGHT) for d, h in self.hands], sources=len(self.devices),
+                                         invX=cfg.get('invX') is True, invY=cfg.get('invY') is True, fx=cfg['fx'], fy=cfg['fy'],
+                                         sensor=self.sensor)
+            self._seeded = [False] * len(self.hands)
+        return self._tracker
+
+    def processFrames(self, frames):
+        """One tick: one frame (or None) per device -> one result dict per track (MultiTracker.process).  Tracks without a centre are
+        seeded first: from init_com once, else (seed_detect) by detection in their device's frame."""
+        shape = next(numpy.asarray(f).shape for f in frames if f is not None)
+        mt = self.tracker(*shape)
+        for t, (d, _) in enumerate(self.hands):
+            if not mt.lost[t] or frames[d] is None:
+                continue
+            if not self._seeded[t] and self.init_com[t] is not None:
+                mt.reset(t, self.init_com[t])
+            elif self.seed_detect:
+                mt.acquire(t, frames[d])
+            self._seeded[t] = True
+        return mt.process(frames)
+
+    def processVideos(self, max_frames=None):
+        """Every tick one frame of every device through one plan, until a FileDevice ends, max_frames ticks, `stop`, or -- without
+        seed_detect -- every track is lost.  Returns one (ticks followed, J, 3) float32 array of poses in mm per track: a tick in
+        which a track is lost or idle is left out of that track's list."""
+        self.initNets()
+        for dev in self.devices:
+            dev.start()
+        poses = [[] for _ in self.hands]
+        times, ticks = [], 0
+        while not self.stop.value and (max_frames is None or ticks < max_frames):
+            frames = []
+            try:
+                for dev in self.devices:
+                    ret, frame = dev.getDepth()
+                    frames.append(frame if ret is not False else None)
+            except IndexError:
+                break
+            if all(f is None for f in frames):
+                print("Error while reading frames.")
+                break
+            start = time.time()
+            res = self.processFrames(frames)
+            times.append(time.time() - start)
+            ticks += 1
+            for t, r in enumerate(res):
+                if r['status'] == 0:
+                    poses[t].append(r['pose'].copy())
+                elif r['status'] == 1:
+                    print("Track {} lost (or no hand) in tick {}.".format(t, ticks - 1))
+            if not self.seed_detect and all(self._tracker.lost):
+                break
+            if self.verbose is True:
+                print("{}ms tick".format(times[-1] * 1000.))
+        for dev in self.devices:
+            dev.stop()
+        self.frame_times = times
+        J = self.poseNet.cfgParams.outputDim[1] // 3
+        return [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in poses]

@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""
+Several hands and cameras through ONE device plan per tick, headless: two recorded sequences are played through two FileDevices as two
+cameras, and three hands are followed at once -- the left- and the right-hand view of the first camera and the left-hand view of the
+second (util.realtimehandposepipeline.MultiStreamPipeline on hipdp/multitrack.py).  The nets are built for a batch of three; a tick
+costs the launches of ONE single-hand tracker (examples/test_realtimepipeline.py), whatever the number of hands.
+
+Every track is seeded with its sequence's annotated centre of the first frame (both views of the first camera with the same one; a
+detector that tells two hands of one frame apart is not built), or, with --seed detect, the tracks that are alone on their camera by
+connected-component detection.  Prints the time per tick and, where the annotations match the pose net's joints, the mean joint error
+of every left-hand track.  Checkpoints are optional: without them the nets have random weights (a dry run of the machinery).
+
+    python examples/realtime_multi.py --dataset icvl --data ../data/ICVL/ --seqs test_seq_1 test_seq_2
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'deep-prior-pp_amd'))
+
+import numpy  # noqa: E402
+
+from data.importers import ICVLImporter, MSRA15Importer, NYUImporter  # noqa: E402
+from net.poseregnet import PoseRegNetParams  # noqa: E402
+from net.resnet import ResNetParams  # noqa: E402
+from net.scalenet import ScaleNetParams  # noqa: E402
+from util.cameradevice import FileDevice  # noqa: E402
+from util.handpose_evaluation import HandposeEvaluation  # noqa: E402
+from util.realtimehandposepipeline import MultiStreamPipeline  # noqa: E402
+
+DATASETS = {'icvl': (ICVLImporter, ('test_seq_1', 'test_seq_2'), {'fx': 241.42, 'fy': 241.42, 'cube': (250, 250, 250)}),
+            'nyu': (NYUImporter, ('test_1', 'test_2'), {'fx': 588., 'fy': 587., 'cube': (300, 300, 300)}),
+            'msra': (MSRA15Importer, ('P0', 'P1'), {'fx': 241.42, 'fy': 241.42, 'cube': (200, 200, 200)})}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--dataset', choices=sorted(DATASETS), default='nyu')
+    ap.add_argument('--data', default=None, help='dataset directory (default: ../data/<NAME>/)')
+    ap.add_argument('--seqs', nargs=2, default=None, help='the two sequences played as camera 0 and camera 1')
+    ap.add_argument('--net', choices=['resnet', 'poseregnet'], default='resnet', help='pose net: ResNet type 1 (the reference) or PoseRegNet type 0')
+    ap.add_argument('--joints', type=int, default=None, help="the pose net's joints (default: the sequences')")
+    ap.add_argument('--pose-net', default=None, help='checkpoint of the pose net')
+    ap.add_argument('--comref-net', default=None, help='checkpoint of the ScaleNet centre refinement')
+    ap.add_argument('--seed', choices=['gt', 'detect'], default='gt', help="first centres: the annotations, or detection where a camera has one track")
+    ap.add_argument('--max-frames', type=int, default=None)
+    ap.add_argument('--cache', default='./cache/')
+    args = ap.parse_args(argv)
+    Importer, seq_names, config = DATASETS[args.dataset]
+    base = args.data or {'icvl': '../data/ICVL/', 'nyu': '../data/NYU/', 'msra': '../data/MSRA15/'}[args.dataset]
+    di = Importer(base, useCache=False, cacheDir=args.cache)
+    seqs = [di.loadSequence(name, Nmax=args.max_frames if args.max_frames else float('inf')) for name in (args.seqs or seq_names)]
+    if not all(s.data for s in seqs):
+        raise SystemExit("no frames in one of %s" % (args.seqs or seq_names,))
+    L, R = MultiStreamPipeline.HAND_LEFT, MultiStreamPipeline.HAND_RIGHT
+    hands = [(0, L), (0, R), (1, L)]                                   # both hands of camera 0, one hand of camera 1
+    T = len(hands)
+    J = args.joints or int(seqs[0].data[0].gt3Dorig.shape[0])
+    if args.net == 'resnet':
+        poseNetParams = ResNetParams(type=1, nChan=1, wIn=128, hIn=128, batchSize=T, numJoints=J, nDims=3)
+    else:
+        poseNetParams = PoseRegNetParams(type=0, nChan=1, wIn=128, hIn=128, batchSize=T, numJoints=J, nDims=3)
+    poseNetParams.loadFile = args.pose_net
+    comrefNetParams = ScaleNetParams(type=1, nChan=1, wIn=128, hIn=128, batchSize=T, resizeFactor=2, numJoints=1, nDims=3)
+    comrefNetParams.loadFile = args.comref_net
+    config = dict(config, cube=tuple(seqs[0].config['cube']))
+    init = [seqs[d].data[0].gtorig[di.crop_joint_idx] for d, _ in hands]
+    if args.seed == 'detect':
+        init[2] = None                                                 # alone on its camera: found by the detector
+    devices = [FileDevice([f.fileName for f in s.data], di) for s in seqs]
+    msp = MultiStreamPipeline(poseNetParams, config, di, devices, hands, comrefNetParams, init_com=init, seed_detect=args.seed == 'detect')
+    poses = msp.processVideos(max_frames=args.max_frames)
+    t = numpy.asarray(msp.frame_times[1:] or msp.frame_times)         # the first tick records the plan
+    print("{} ticks, {} tracks, {:.3f} ms per tick (median; {:.3f} ms mean)".format(len(msp.frame_times), T, numpy.median(t) * 1000., t.mean() * 1000.))
+    errs = []
+    for (d, hand), p in zip(hands, poses):
+        err = None
+        if hand == L and len(p) and p.shape[1] == seqs[d].data[0].gt3Dorig.shape[0]:
+            err = HandposeEvaluation([f.gt3Dorig for f in seqs[d].data[:len(p)]], list(p)).getMeanError()
+            print("camera {} left hand, mean error: {}mm".format(d, err))
+        errs.append(err)
+    return poses, errs
+
+
+if __name__ == '__main__':
+    main()

@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 15
+#define DPP_ABI_VERSION 16
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -505,6 +505,36 @@ int dpp_pose_finish(const float* net_out, int B, int J, const float* cube, const
                     int flip_y, int flags, float* pose3d, float* pose_img, dpp_stream_t stream);
 int dpp_refine_com_iterative(const float* frames, const float* partial, int B, int H, int W, const float* com_in, const float* cube,
                              double fx, double fy, int num_iter, float* com_out, int* status, dpp_stream_t stream);
+
+/* ---- several tracks over several frames (ABI v16) -------------------------------------------------------------------------------
+ * The five tracking launches for T tracks over C frames (hipdp/multitrack.py): every row t of com / cube / records / net_out /
+ * the outputs is one track, and three int32 device arrays with one entry per track say
+ *   src[t]     which frame of `frames` [C][H][W] (and which frame's partials of dpp_frame_range at B = C) track t reads; the
+ *              caller guarantees 0 <= src[t] < C, the kernels do not check it;
+ *   gate[t]    0: the track sits this launch out;
+ *   tflags[t]  the track's own dpp_pose_finish flags (1 HAND_RIGHT, 2 invX, 4 invY).
+ * With src[t] = t, gate[t] = 1 and tflags[t] = flags every entry point gives the bytes of its plain sibling (the same kernel bodies).
+ * crop_prepare_ranged_ix: a gated track gets the empty window, like an ill-defined centre.
+ * crop_warp_ix / crop_warp_ex_ix: row t is cropped from frame src[t]; crop_warp_ex_ix sets DPP_CROP_FLIP_X per row from
+ *   tflags[t] & 1 (the bit is refused in `flags`), the remaining flags hold for all rows.
+ * track_refine_ix: a gated track keeps com_out[t] = com_in[t] bit for bit and gets status DPP_TRACK_IDLE, the empty window,
+ *   M = identity and com3D = 0; it is never reported lost.
+ * pose_finish_ix: the sign rules of row t come from tflags[t]. */
+#define DPP_TRACK_OK 0
+#define DPP_TRACK_LOST 1
+#define DPP_TRACK_IDLE 2
+int dpp_crop_prepare_ranged_ix(const float* partial, int T, const int* src, const int* gate, const float* com, const float* cube, double fx,
+                               double fy, int dsz, int stretch, void* records, float* M_out, dpp_stream_t stream);
+int dpp_crop_warp_ix(const float* frames, const void* records, int T, const int* src, int H, int W, int dsz, int normalize, float nd_value,
+                     float* out, dpp_stream_t stream);
+int dpp_track_refine_ix(const float* frames, const void* records_in, int T, const int* src, const int* gate, int H, int W,
+                        const float* com_in, const float* cube, const float* net_out, double fx, double fy, double ux, double uy, int flip_y,
+                        double crop_fx, double crop_fy, int dsz, float* com_out, float* com3d_out, void* records_out, float* M_out,
+                        int* status, dpp_stream_t stream);
+int dpp_crop_warp_ex_ix(const float* frames, const void* records, int T, const int* src, const int* tflags, int H, int W, int dsz, int flags,
+                        float nd_value, float fill_value, float pad_value, float* out, dpp_stream_t stream);
+int dpp_pose_finish_ix(const float* net_out, int T, int J, const int* tflags, const float* cube, const float* com3d, double fx, double fy,
+                       double ux, double uy, int flip_y, float* pose3d, float* pose_img, dpp_stream_t stream);
 
 /* ---- sensor frames (ABI v15): uint16 / float32 ingest, mirror, 3x3 median (csrc/ingest.hip) ----------------------------------------
  * What the reference's live depth source does to every frame (src/util/cameradevice.py:189-200 of the reference): optional mirror,
