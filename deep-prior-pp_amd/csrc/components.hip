@@ -1,9 +1,10 @@
-// components.hip -- finding the hand in a whole depth frame by 8-connected component labelling, for gfx950 (ABI v14):
+// components.hip -- finding the hand in a whole depth frame by 8-connected component labelling, for gfx950 (ABI v14, several hands: v17):
 //   slab keys        slab_keys: the 20 depth slabs of HandDetector.detect (handdetector.py:576-582) as one uint8 key per pixel
 //   labelling        cc_local / cc_border / cc_compress: labels[p] = smallest linear index of p's 8-connected component of equal key
 //   statistics       cc_stats: per component pixel count, bounding box and coordinate sums (integer atomics only)
 //   the seed         comp_select + detect_seed: the nearest slab's raster-first component of more than 200 px, the centre of mass of
 //                    the +-100 px window around its centroid within that slab (handdetector.py:586-607) -> refine_com_iterative
+//   several hands    comp_candidates + detect_select + detect_seeds: up to K seeds of one frame from the same labelling
 //   hand size        mask_keys -> labelling -> comp_select -> hand_size: estimateHandsize (handdetector.py:911-937) from the bounding
 //                    box of the largest component of the hand's depth range (:616-627)
 // Where the reference walks cv2.findContours' contour list, this unit labels components: pixel count for contourArea, raster order
@@ -222,30 +223,22 @@ __global__ __launch_bounds__(DPP_THREADS) void comp_select_kernel(const int* __r
 
 __device__ __forceinline__ int select_root(unsigned long long v) { return (int)(0xffffffffull - (v & 0xffffffffull)); }
 
-// detect's seed for frame b (handdetector.py:589-607), one workgroup: the centroid of the selected component (rint of the float64
+// detect's seed from one component (handdetector.py:589-607), one workgroup: the centroid of the component (rint of the float64
 // quotient), the window [max(cx - 100, 0), min(cx + 100, W - 1)) x [max(cy - 100, 0), min(cy + 100, H - 1)), calculateCoM of the
-// window's pixels inside the selected slab's inclusive bounds (float64 sums of integers and of float32 millimetres: exact, the order
-// is free; the mean as NumPy forms it: sum / num * num / num), the centre-pixel fallback, the window origin added.  No component:
-// com = (0, 0, 0) (:632) and status 0.
-__global__ __launch_bounds__(DPP_THREADS) void detect_seed_kernel(const float* __restrict__ frames, int H, int W, const float* __restrict__ partial,
-                                                                  const CompStat* __restrict__ stats, const unsigned long long* __restrict__ best,
-                                                                  float* __restrict__ com_out, int* __restrict__ status) {
-    __shared__ double s_red[4][DPP_THREADS / DPP_WAVE];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* f = frames + (size_t)b * H * W;
-    float mn, mx;
-    frame_range_reduce(partial, b, lane, mn, mx);
-    const float min_depth = fmaxf(10.0f, mn), max_depth = fminf(1500.0f, mx);
-    const unsigned long long v = best[b * 2];
-    if (v == 0ull) {
-        if (tid == 0) { com_out[b * 3] = 0.f; com_out[b * 3 + 1] = 0.f; com_out[b * 3 + 2] = 0.f; status[b] = 0; }
-        return;
-    }
-    const int key = 255 - (int)(v >> 32);
-    const CompStat st = stats[(size_t)b * H * W + select_root(v)];
-    const int cx = (int)rint((double)st.sx / (double)st.cnt), cy = (int)rint((double)st.sy / (double)st.cnt);
-    const int xs = cx - 100 > 0 ? cx - 100 : 0, xe = cx + 100 < W - 1 ? cx + 100 : W - 1;
-    const int ys = cy - 100 > 0 ? cy - 100 : 0, ye = cy + 100 < H - 1 ? cy + 100 : H - 1;
+// window's pixels inside the component's slab's inclusive bounds (float64 sums of integers and of float32 millimetres: exact, the
+// order is free; the mean as NumPy forms it: sum / num * num / num), the centre-pixel fallback, the window origin added.  Thread 0
+// stores com_out[0..2] and *status.  The ONE body of detect_seed_kernel (one winner per frame) and detect_seeds_kernel (K per frame).
+__device__ __forceinline__ int seed_centroid(unsigned long long sum, int cnt) { return (int)rint((double)sum / (double)cnt); }
+__device__ __forceinline__ int seed_window_lo(int c) { return c - 100 > 0 ? c - 100 : 0; }
+__device__ __forceinline__ int seed_window_hi(int c, int n) { return c + 100 < n - 1 ? c + 100 : n - 1; }
+
+__device__ __forceinline__ void detect_seed_body(const float* __restrict__ f, int H, int W, float min_depth, float max_depth, int key,
+                                                 const CompStat& st, double (*s_red)[DPP_THREADS / DPP_WAVE], float* __restrict__ com_out,
+                                                 int* __restrict__ status) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cx = seed_centroid(st.sx, st.cnt), cy = seed_centroid(st.sy, st.cnt);
+    const int xs = seed_window_lo(cx), xe = seed_window_hi(cx, W);
+    const int ys = seed_window_lo(cy), ye = seed_window_hi(cy, H);
     const double lo = slab_bound(min_depth, max_depth, key), hi = slab_bound(min_depth, max_depth, key + 1);
     // the window's value at frame pixel (x, y): the detector's range, then the slab
     auto value = [&](int x, int y) {
@@ -266,10 +259,173 @@ __global__ __launch_bounds__(DPP_THREADS) void detect_seed_kernel(const float* _
     if (cnt > 0.0) { c0 = sx / cnt * cnt / cnt; c1 = sy / cnt * cnt / cnt; c2 = sd / cnt; }
     if (fabs(c0) <= 1e-8 && fabs(c1) <= 1e-8 && fabs(c2) <= 1e-8 && xe > xs && ye > ys)       // numpy.allclose(com, 0.)
         c2 = (double)value(xs + (xe - xs) / 2, ys + (ye - ys) / 2);
-    com_out[b * 3] = (float)(c0 + (double)xs);
-    com_out[b * 3 + 1] = (float)(c1 + (double)ys);
-    com_out[b * 3 + 2] = (float)c2;
-    status[b] = DET_FOUND;
+    com_out[0] = (float)(c0 + (double)xs);
+    com_out[1] = (float)(c1 + (double)ys);
+    com_out[2] = (float)c2;
+    *status = DET_FOUND;
+}
+
+// detect's seed for frame b from the component comp_select (mode 0) chose.  No component: com = (0, 0, 0) (:632) and status 0.
+__global__ __launch_bounds__(DPP_THREADS) void detect_seed_kernel(const float* __restrict__ frames, int H, int W, const float* __restrict__ partial,
+                                                                  const CompStat* __restrict__ stats, const unsigned long long* __restrict__ best,
+                                                                  float* __restrict__ com_out, int* __restrict__ status) {
+    __shared__ double s_red[4][DPP_THREADS / DPP_WAVE];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float mn, mx;
+    frame_range_reduce(partial, b, tid & 63, mn, mx);
+    const unsigned long long v = best[b * 2];
+    if (v == 0ull) {
+        if (tid == 0) { com_out[b * 3] = 0.f; com_out[b * 3 + 1] = 0.f; com_out[b * 3 + 2] = 0.f; status[b] = 0; }
+        return;
+    }
+    const CompStat st = stats[(size_t)b * H * W + select_root(v)];
+    detect_seed_body(frames + (size_t)b * H * W, H, W, fmaxf(10.0f, mn), fminf(1500.0f, mx), 255 - (int)(v >> 32), st, s_red, com_out + b * 3,
+                     status + b);
+}
+
+// ---- several hands of one frame (ABI v17) ----------------------------------------------------------------------------------------
+// comp_candidates -> detect_select -> detect_seeds: up to K seeds per frame from the labelling that detect_seed takes one from.
+//   candidates   every root of more than 200 px (that passes the extent filter), in (key, root) order
+//   selection    greedy: a candidate whose centroid lies in the seed window of an ACCEPTED one is suppressed; K acceptances
+// The extent filter and the window suppression are this project's own rules.
+constexpr int DET_MAX_HANDS = 16;
+constexpr unsigned long long DET_NONE = ~0ull;
+
+// candidates per frame: components of more than 200 px are disjoint, so there are at most H * W / 201 of them
+__host__ __device__ __forceinline__ int cand_capacity(int H, int W) { return (int)((long long)H * W / (CC_MIN_AREA + 1)); }
+// a frame's part of the candidate workspace, in 64-bit words: the list, the centroids of its entries, the selection
+__host__ __device__ __forceinline__ size_t cand_stride(int H, int W) { return 2 * (size_t)cand_capacity(H, W) + DET_MAX_HANDS; }
+
+// One word key << 32 | root per candidate root, and its centroid cy << 32 | cx beside it, appended through the frame's counter
+// (best[b][0], which slab_keys cleared): the wave counts its candidates (an inclusive scan over the lanes) and its last lane
+// draws the wave's range with ONE atomic.  The list's order is that of arrival; detect_select's result does not depend on it.
+// Extent filter (max_extent > 0): a component whose box is wider or higher than max_extent mm at its slab's far bound is no
+// candidate: (xmax - xmin + 1) * b_{key+1} / fx > max_extent, float64 in that order, likewise in y.
+__global__ __launch_bounds__(DPP_THREADS) void comp_candidates_kernel(const int* __restrict__ labels, const unsigned char* __restrict__ keys,
+                                                                      const CompStat* __restrict__ stats, int H, int W,
+                                                                      const float* __restrict__ partial, double max_extent, double fx, double fy,
+                                                                      unsigned long long* __restrict__ best, unsigned long long* __restrict__ cand) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int p = blockIdx.x * DPP_THREADS + threadIdx.x;
+    const int cap = cand_capacity(H, W);
+    float min_depth = 0.0f, max_depth = 0.0f;
+    if (max_extent > 0.0) {                                                    // uniform: the whole wave reduces the range
+        float mn, mx;
+        frame_range_reduce(partial, b, lane, mn, mx);
+        min_depth = fmaxf(10.0f, mn); max_depth = fminf(1500.0f, mx);
+    }
+    unsigned long long word = 0ull, cen = 0ull;
+    int is_cand = 0;
+    if (p < H * W && labels[(size_t)b * H * W + p] == p) {
+        const CompStat st = stats[(size_t)b * H * W + p];
+        if (st.cnt > CC_MIN_AREA) {
+            const int key = keys[(size_t)b * H * W + p];
+            is_cand = 1;
+            if (max_extent > 0.0) {
+                const double hi = slab_bound(min_depth, max_depth, key + 1);
+                const double ex = (double)(st.xmax - ~st.ixmin + 1) * hi / fx, ey = (double)(st.ymax - ~st.iymin + 1) * hi / fy;
+                if (ex > max_extent || ey > max_extent) is_cand = 0;
+            }
+            word = ((unsigned long long)key << 32) | (unsigned long long)p;
+            cen = ((unsigned long long)seed_centroid(st.sy, st.cnt) << 32) | (unsigned long long)seed_centroid(st.sx, st.cnt);
+        }
+    }
+    int scan = is_cand;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(scan, o);
+        if (lane >= o) scan += t;
+    }
+    const int total = __shfl(scan, 63);
+    if (total == 0) return;
+    int base = 0;
+    if (lane == 63) base = (int)atomicAdd(&best[b * 2], (unsigned long long)total);
+    base = __shfl(base, 63);
+    const int i = base + scan - 1;
+    if (is_cand && i < cap) {                                                  // (i < cap always: see cand_capacity)
+        unsigned long long* c = cand + (size_t)b * cand_stride(H, W);
+        c[i] = word;
+        c[cap + i] = cen;
+    }
+}
+
+// Greedy selection for frame b, one workgroup, K rounds: the smallest word above the last accepted one whose centroid lies in no
+// accepted window (a block minimum over the list, in whatever order it is; threads stride over it) is accepted and its window
+// recorded.  Walking by a lower bound needs no marks: everything below the bound was accepted or suppressed, and suppressed
+// candidates suppress nothing.  sel[k] = the k-th accepted word, DET_NONE from the first round that finds none.
+__global__ __launch_bounds__(DPP_THREADS) void detect_select_kernel(const unsigned long long* __restrict__ best, int H, int W, int K,
+                                                                    unsigned long long* __restrict__ cand) {
+    __shared__ unsigned long long s_w[DPP_THREADS / DPP_WAVE], s_c[DPP_THREADS / DPP_WAVE];
+    __shared__ int s_win[DET_MAX_HANDS][4];
+    __shared__ unsigned long long s_bound;                                     // words below it are done; DET_NONE: no candidate left
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cap = cand_capacity(H, W);
+    const unsigned long long count = best[b * 2];
+    const int n = count < (unsigned long long)cap ? (int)count : cap;
+    const unsigned long long* list = cand + (size_t)b * cand_stride(H, W);
+    const unsigned long long* cens = list + cap;
+    unsigned long long* sel = cand + (size_t)b * cand_stride(H, W) + 2 * (size_t)cap;
+    unsigned long long bound = 0ull;
+    for (int k = 0; k < K; ++k) {
+        unsigned long long m = DET_NONE, mc = 0ull;
+        if (bound != DET_NONE) {
+            for (int i = tid; i < n; i += DPP_THREADS) {
+                const unsigned long long w = list[i];
+                if (w < bound || w >= m) continue;
+                const unsigned long long c = cens[i];
+                const int cx = (int)(c & 0xffffffffull), cy = (int)(c >> 32);
+                bool free_ = true;
+                for (int a = 0; a < k; ++a)
+                    if (s_win[a][0] <= cx && cx < s_win[a][1] && s_win[a][2] <= cy && cy < s_win[a][3]) free_ = false;
+                if (free_) { m = w; mc = c; }
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long tw = __shfl_xor(m, o), tc = __shfl_xor(mc, o);
+            if (tw < m) { m = tw; mc = tc; }
+        }
+        if (lane == 0) { s_w[wave] = m; s_c[wave] = mc; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < DPP_THREADS / DPP_WAVE; ++w)
+                if (s_w[w] < m) { m = s_w[w]; mc = s_c[w]; }
+            sel[k] = m;
+            if (m != DET_NONE) {
+                const int cx = (int)(mc & 0xffffffffull), cy = (int)(mc >> 32);
+                s_win[k][0] = seed_window_lo(cx); s_win[k][1] = seed_window_hi(cx, W);
+                s_win[k][2] = seed_window_lo(cy); s_win[k][3] = seed_window_hi(cy, H);
+            }
+            s_bound = m == DET_NONE ? DET_NONE : m + 1ull;
+        }
+        __syncthreads();
+        bound = s_bound;
+    }
+}
+
+// The seed of slot k of frame b (row b * K + k) from its accepted component, and the slot's report: key, pixel count, xmin, xmax,
+// ymin, ymax.  An empty slot: seed (0, 0, 0), status 0, an all-zero report.
+__global__ __launch_bounds__(DPP_THREADS) void detect_seeds_kernel(const float* __restrict__ frames, int H, int W, const float* __restrict__ partial,
+                                                                   const CompStat* __restrict__ stats, const unsigned long long* __restrict__ cand,
+                                                                   int K, float* __restrict__ com_out, int* __restrict__ status,
+                                                                   int* __restrict__ report) {
+    __shared__ double s_red[4][DPP_THREADS / DPP_WAVE];
+    const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, row = b * K + k;
+    float mn, mx;
+    frame_range_reduce(partial, b, tid & 63, mn, mx);
+    const unsigned long long v = cand[(size_t)b * cand_stride(H, W) + 2 * (size_t)cand_capacity(H, W) + k];
+    if (v == DET_NONE) {
+        if (tid == 0) {
+            com_out[row * 3] = 0.f; com_out[row * 3 + 1] = 0.f; com_out[row * 3 + 2] = 0.f; status[row] = 0;
+            for (int j = 0; j < 6; ++j) report[row * 6 + j] = 0;
+        }
+        return;
+    }
+    const int key = (int)(v >> 32);
+    const CompStat st = stats[(size_t)b * H * W + (int)(v & 0xffffffffull)];
+    if (tid == 0) {
+        int* r = report + row * 6;
+        r[0] = key; r[1] = st.cnt; r[2] = ~st.ixmin; r[3] = st.xmax; r[4] = ~st.iymin; r[5] = st.ymax;
+    }
+    detect_seed_body(frames + (size_t)b * H * W, H, W, fmaxf(10.0f, mn), fminf(1500.0f, mx), key, st, s_red, com_out + row * 3, status + row);
 }
 
 // estimateHandsize (handdetector.py:920-935) from the bounding box of the selected (largest) component: w = xmax - xmin + 1 and
@@ -351,6 +507,27 @@ extern "C" int dpp_detect_seed(const float* frames, const float* partial, const 
                H, W, 0, static_cast<unsigned long long*>(state));
     DPP_LAUNCH(detect_seed_kernel, dim3(B), dim3(DPP_THREADS), 0, st, frames, H, W, partial, static_cast<const CompStat*>(stats),
                static_cast<const unsigned long long*>(state), com_out, status);
+    return dpp_launch_status();
+}
+
+extern "C" size_t dpp_detect_candidates_bytes(int B, int H, int W) {
+    return cc_dims_ok(B, H, W) ? (size_t)B * cand_stride(H, W) * sizeof(unsigned long long) : 0;
+}
+
+extern "C" int dpp_detect_seeds(const float* frames, const float* partial, const unsigned char* keys, const int* labels, const void* stats, int B,
+                                int H, int W, void* state, void* candidates, int K, double max_extent, double fx, double fy, float* seed_out,
+                                int* status, int* report, dpp_stream_t stream) {
+    if (!frames || !partial || !keys || !labels || !stats || !state || !candidates || !seed_out || !status || !report || !cc_dims_ok(B, H, W))
+        return DPP_E_BADARG;
+    if (K < 1 || K > DET_MAX_HANDS || !(max_extent >= 0.0) || !(max_extent <= 1.7976931348623157e308)) return DPP_E_BADARG;
+    if (max_extent > 0.0 && !(fabs(fx) > 0.0 && fabs(fy) > 0.0)) return DPP_E_BADARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned long long* cand = static_cast<unsigned long long*>(candidates);
+    DPP_LAUNCH(comp_candidates_kernel, dim3(dpp_cdiv(H * W, DPP_THREADS), B), dim3(DPP_THREADS), 0, st, labels, keys,
+               static_cast<const CompStat*>(stats), H, W, partial, max_extent, fabs(fx), fabs(fy), static_cast<unsigned long long*>(state), cand);
+    DPP_LAUNCH(detect_select_kernel, dim3(B), dim3(DPP_THREADS), 0, st, static_cast<const unsigned long long*>(state), H, W, K, cand);
+    DPP_LAUNCH(detect_seeds_kernel, dim3(K, B), dim3(DPP_THREADS), 0, st, frames, H, W, partial, static_cast<const CompStat*>(stats),
+               static_cast<const unsigned long long*>(cand), K, seed_out, status, report);
     return dpp_launch_status();
 }
 

@@ -5,6 +5,7 @@
 //   realtime tracking       frame_range, crop_prepare_ranged, track_refine, pose_finish, refine_com_iterative (HandDetector.track,
 //                           RealtimeHandposePipeline; ABI v13)
 //   several tracks          the *_ix entry points of the five tracking launches: T tracks over C frames (ABI v16)
+//   several hands           refine_com_iterative_ix: several centres of one frame refined in one launch (ABI v17)
 // They share CropRec, crop_geometry and crop_window_value; each section below names the reference lines it restates.  The training-time
 // augmentation of finished crops is augment.hip; finding the hand in a whole frame (connected components) is components.hip; the
 // camera, bounds and warp-coordinate arithmetic and the workgroup reductions these units share are geom.h.
@@ -567,19 +568,22 @@ __global__ __launch_bounds__(DPP_THREADS) void pose_finish_kernel(const float* _
 // float64 between them as on the host.  Window sums in float64 (column / row sums are integers, a sum of float32 depths of
 // 10..1500 mm over at most a frame is exact: the order is free); the mean as NumPy forms it: sum / num, * num, / num.
 // A centre whose depth is isclose to 0 ("CoM ill-defined") stops the frame with status 1 (com_out: the centre so far).
+// src (ABI v17; NULL: row r works on frame r): row r refines com_in[r] in frame src[r], with that frame's partials and cube.
 __global__ __launch_bounds__(DPP_THREADS) void refine_com_iterative_kernel(const float* __restrict__ frames, int H, int W,
-                                                                           const float* __restrict__ partial, const float* __restrict__ com_in,
-                                                                           const float* __restrict__ cube, double fx, double fy, int num_iter,
-                                                                           float* __restrict__ com_out, int* __restrict__ status) {
+                                                                           const float* __restrict__ partial, const int* __restrict__ src,
+                                                                           const float* __restrict__ com_in, const float* __restrict__ cube,
+                                                                           double fx, double fy, int num_iter, float* __restrict__ com_out,
+                                                                           int* __restrict__ status) {
     __shared__ double s_red[4][DPP_THREADS / DPP_WAVE];
     __shared__ CropRec s_r;
     __shared__ double s_com[3];
     __shared__ int s_stop;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float* f = frames + (size_t)b * H * W;
+    const int fb = src ? src[b] : b;                                   // the row's frame
+    const float* f = frames + (size_t)fb * H * W;
     float mn, mx;
-    frame_range_reduce(partial, b, tid & 63, mn, mx);
-    const double size[3] = {(double)cube[b * 3], (double)cube[b * 3 + 1], (double)cube[b * 3 + 2]};
+    frame_range_reduce(partial, fb, tid & 63, mn, mx);
+    const double size[3] = {(double)cube[fb * 3], (double)cube[fb * 3 + 1], (double)cube[fb * 3 + 2]};
     if (tid == 0) {
         for (int d = 0; d < 3; ++d) s_com[d] = (double)com_in[b * 3 + d];
         s_stop = 0;
@@ -778,13 +782,27 @@ extern "C" int dpp_pose_finish(const float* net_out, int B, int J, const float* 
     return launch_pose_finish(net_out, B, J, cube, com3d, fx, fy, ux, uy, flip_y, flags, nullptr, pose3d, pose_img, stream);
 }
 
-extern "C" int dpp_refine_com_iterative(const float* frames, const float* partial, int B, int H, int W, const float* com_in, const float* cube,
-                                        double fx, double fy, int num_iter, float* com_out, int* status, dpp_stream_t stream) {
+static int launch_refine_com_iterative(const float* frames, const float* partial, int B, const int* src, int H, int W, const float* com_in,
+                                       const float* cube, double fx, double fy, int num_iter, float* com_out, int* status,
+                                       dpp_stream_t stream) {
     if (!frames || !partial || !com_in || !cube || !com_out || !status || B < 1 || H < 1 || W < 1 || num_iter < 0 || fx == 0.0 || fy == 0.0)
         return DPP_E_BADARG;
-    DPP_LAUNCH(refine_com_iterative_kernel, dim3(B), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W, partial, com_in, cube,
-               fabs(fx), fabs(fy), num_iter, com_out, status);
+    DPP_LAUNCH(refine_com_iterative_kernel, dim3(B), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W, partial, src, com_in,
+               cube, fabs(fx), fabs(fy), num_iter, com_out, status);
     return dpp_launch_status();
+}
+
+extern "C" int dpp_refine_com_iterative(const float* frames, const float* partial, int B, int H, int W, const float* com_in, const float* cube,
+                                        double fx, double fy, int num_iter, float* com_out, int* status, dpp_stream_t stream) {
+    return launch_refine_com_iterative(frames, partial, B, nullptr, H, W, com_in, cube, fx, fy, num_iter, com_out, status, stream);
+}
+
+// R rows over the frames src names (ABI v17): several centres of one frame, as the several-hands detector refines them; a NULL
+// src is the plain entry point.  The caller guarantees that src[r] is a frame of `frames`; rows of a frame share its cube.
+extern "C" int dpp_refine_com_iterative_ix(const float* frames, const float* partial, int R, const int* src, int H, int W, const float* com_in,
+                                           const float* cube, double fx, double fy, int num_iter, float* com_out, int* status,
+                                           dpp_stream_t stream) {
+    return launch_refine_com_iterative(frames, partial, R, src, H, W, com_in, cube, fx, fy, num_iter, com_out, status, stream);
 }
 
 // ---- several tracks over several frames (ABI v16): the five tracking launches with one (src, gate, tflags) entry per track ----------

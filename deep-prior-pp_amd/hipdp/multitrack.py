@@ -23,8 +23,9 @@ GATING.  A track sits a tick out (gate 0) when it is lost, was never started, or
 through the nets (on an all-zero crop), its centre's bits stay as they are, and it is reported IDLE -- or LOST, when that is why it
 was gated.  A lost track does not stop the others; it stays gated until reset(t, com) or a successful acquire(t, frame).
 
-One importer (camera) serves all sources: the camera is a launch argument.  Per-source intrinsics are out of scope here, and so are
-the overlapped process_sequence form for several sources and a detector that returns two hands (DESIGN.md names them as follow-ups).
+One importer (camera) serves all sources: the camera is a launch argument.  Per-source intrinsics are out of scope here, and so is
+the overlapped process_sequence form for several sources (DESIGN.md names both as follow-ups).  acquire_source(c, frame) finds ALL
+hands of a source in one detector plan and starts the source's tracks from them.
 """
 import numpy as np
 
@@ -96,6 +97,7 @@ class MultiTracker(object):
         self.gate_host = np.zeros(T, i32)                                          # what the device holds
         self.lost = np.ones(T, bool)                                               # no centre yet
         self.cube_host = np.zeros((T, 3), f32)
+        self.com_host = np.zeros((T, 3), f32)                                      # the centres as last downloaded (or reset)
         for t in range(T):
             self.set_cube(t, cube)
         self._plan = None
@@ -116,6 +118,7 @@ class MultiTracker(object):
         if not np.all(np.isfinite(com)) or np.isclose(com[2], 0.):
             raise ValueError("reset needs a centre with a depth: %r" % (com,))
         self.com.view(3 * t, (1, 3)).set(com)
+        self.com_host[t] = com
         self.lost[t] = False
 
     def set_cube(self, t, cube):
@@ -150,7 +153,7 @@ class MultiTracker(object):
     def acquire(self, t, frame, do_hand_size=False):
         """Find a hand in `frame` of track t's source and start track t (again) from it, as HandTracker.acquire does: one upload, the
         detector plan, one download of the result block.  The detector finds the NEAREST object of the frame: of two hands on one
-        source it finds the same one for both tracks, so the second hand of a source is seeded with reset(t, com).  Returns
+        source it finds the same one for both tracks; acquire_source(c, frame) finds both and shares them out.  Returns
         dict(com, cube, found); not found: the centre is (0, 0, 0) and the track stays lost."""
         t = self._track(t)
         frame = self._frame(frame)
@@ -163,7 +166,79 @@ class MultiTracker(object):
         coms, cubes, found, _, _ = det.parse(res[o['det']:], res[o['com'] + 3 * t:o['com'] + 3 * t + 3], None if do_hand_size else self.cube_host[t])
         ok = bool(found[0]) and bool(np.all(np.isfinite(coms[0]))) and not np.isclose(coms[0][2], 0.)
         self.lost[t] = not ok
+        self.com_host[t] = coms[0]
         return dict(com=coms[0], cube=cubes[0], found=ok)
+
+    def source_detector(self, c, max_extent=None):
+        """(detector, tracks of source c).  The several-hands detector of source c at B = 1, hands = the number of tracks that read c: on views of the source's frame
+        (and raw frame) and partials, with a result block of its own that also holds the K centres -- they go to the tracks through
+        reset(t, com), not through the plan.  The K detections share ONE cube, that of the source's first track."""
+        c = int(c)
+        ts = [t for t in range(self.T) if self.src_host[t] == c]
+        if not 0 <= c < self.C or not ts:
+            raise IndexError("source %d of %d" % (c, self.C))
+        key = ('source', c, float(max_extent) if max_extent else 0.0)
+        if len(ts) == 1 and not max_extent:                                   # nothing to share out: track ts[0]'s own detector
+            return self.detector(ts[0]), ts
+        if key not in self._detectors:
+            from .detect import FrameDetector
+            px = self.H * self.W
+            self._detectors[key] = FrameDetector(
+                self.rt, self.H, self.W, self.fx, self.fy, 1, frames=self.frames.view(c * px, (1, self.H, self.W)),
+                partial=self.partial.view(c * self._pstride, (self._pstride,)), cube=self.cube.view(3 * ts[0], (1, 3)),
+                sensor=None if self.sensor is None else dict(zip(('dtype', 'median', 'mirror'), self.sensor)),
+                raw=None if self.sensor is None else self.raw.view(c * px, (1, self.H, self.W)), hands=len(ts), max_extent=max_extent)
+        return self._detectors[key], ts
+
+    def acquire_source(self, c, frame, max_extent=None, order='near'):
+        """Find the hands of source c in `frame` and start its tracks from them: one upload, ONE detector plan at K = the number of
+        tracks that read c, one download.  The detections (hipdp.detect, hands=K: nearest slab first, then raster-first; max_extent
+        as there) are refined with the cube of the source's first track and handed out on the host:
+          - a track that is being followed keeps its centre and claims the found detection nearest to its last downloaded centre in
+            image (x, y) (Euclidean, float64, ties to the lower slot), so that its hand is not given to another track;
+          - the lost tracks, in ascending t, take the remaining found detections in slot order (order='near') or in ascending
+            refined-centre x (order='x': left to right); each is started with reset(t, com);
+          - a track left without a detection stays lost.
+        Returns one dict(com, cube, found) per track of the source, in ascending t (a followed track: its own centre, found True)."""
+        if order not in ('near', 'x'):
+            raise ValueError("order is 'near' or 'x', not %r" % (order,))
+        frame = self._frame(frame)
+        det, ts = self.source_detector(c, max_extent)
+        c = int(c)
+        if not det.multi:                                                     # one track, no extent filter: acquire's plan, acquire's bits
+            t = ts[0]
+            if self.lost[t]:
+                return [self.acquire(t, frame)]
+            self.inputs.view(c * self.H * self.W, (1, self.H, self.W)).set(frame)
+            return [dict(com=self.com_host[t].copy(), cube=self.cube_host[t].copy(), found=True)]
+        self.inputs.view(c * self.H * self.W, (1, self.H, self.W)).set(frame)
+        det.plan(False).run(self.rt)
+        self.rt.synchronize()
+        coms, _, found = det.parse(det.res.get(), None, self.cube_host[ts[0]])[:3]
+        coms, found = coms[0], found[0]
+        ok = [bool(found[k]) and bool(np.all(np.isfinite(coms[k]))) and not np.isclose(coms[k][2], 0.) for k in range(len(ts))]
+        free = [k for k in range(len(ts)) if ok[k]]
+        out = {}
+        followed = [t for t in ts if not self.lost[t]]
+        if followed:
+            last = self.com_host.astype(np.float64)
+            for t in followed:
+                if free:
+                    d = [np.hypot(np.float64(coms[k][0]) - last[t][0], np.float64(coms[k][1]) - last[t][1]) for k in free]
+                    free.pop(int(np.argmin(d)))                               # argmin: the first (lowest slot) of equal distances
+                out[t] = dict(com=last[t].astype(np.float32), cube=self.cube_host[t].copy(), found=True)
+        if order == 'x':
+            free.sort(key=lambda k: (float(coms[k][0]), k))
+        for t in ts:
+            if t in out:
+                continue
+            if free:
+                k = free.pop(0)
+                self.reset(t, coms[k])
+                out[t] = dict(com=coms[k].copy(), cube=self.cube_host[t].copy(), found=True)
+            else:
+                out[t] = dict(com=np.zeros(3, np.float32), cube=self.cube_host[t].copy(), found=False)
+        return [out[t] for t in ts]
 
     # ---- the per-tick plan --------------------------------------------------------------------------------------------------
     def plan(self):
@@ -203,6 +278,7 @@ class MultiTracker(object):
         pose, pimg = res[:o['pose_img']].reshape(T, J, 3), res[o['pose_img']:o['com']].reshape(T, J, 3)
         com, com3d = res[o['com']:o['com3D']].reshape(T, 3), res[o['com3D']:o['M']].reshape(T, 3)
         M = res[o['M']:o['status']].reshape(T, 3, 3)
+        self.com_host[:] = com
         out = []
         for t in range(T):
             status = int(st[t])

@@ -843,7 +843,17 @@ def refine_com_iterative(rt, frames, partial, B, H, W, com_in, cube, fx, fy, num
                   (frames, partial, com_in, cube, com_out, status), name)
 
 
+def refine_com_iterative_ix(rt, frames, partial, R, src, H, W, com_in, cube, fx, fy, num_iter, com_out, status, name='refine_com_iterative'):
+    """dpp_refine_com_iterative_ix: R rows, row r in frame src[r] with that frame's cube (src: an int32 device array the caller has
+    checked with track_index, or None: row r reads frame r)."""
+    return Launch(rt.lib.dpp_refine_com_iterative_ix, (frames.ptr, partial.ptr, R, _p(src), H, W, com_in.ptr, cube.ptr, float(fx), float(fy),
+                                                       int(num_iter), com_out.ptr, status.ptr),
+                  (frames, partial, src, com_in, cube, com_out, status), name)
+
+
 DETECT_FOUND, DETECT_NO_SIZE = 1, 2          # DPP_DETECT_*: status bits of detect_seed / hand_size
+DETECT_MAX_HANDS = 16                        # DPP_DETECT_MAX_HANDS
+DETECT_REPORT = ('key', 'count', 'xmin', 'xmax', 'ymin', 'ymax')      # one slot of dpp_detect_seeds' report, int32 each
 KEY_BACKGROUND = 255
 # one record of dpp_label_components' statistics (include/dpp_hip.h), meaningful at roots
 COMPONENT_STAT = np.dtype([('count', np.int32), ('ixmin', np.int32), ('xmax', np.int32), ('iymin', np.int32), ('ymax', np.int32),
@@ -852,9 +862,10 @@ COMPONENT_STAT = np.dtype([('count', np.int32), ('ixmin', np.int32), ('xmax', np
 
 class ComponentWorkspace(object):
     """What labelling B frames of H x W needs on the device, allocated once: keys, the union-find parents, labels, the per-root
-    statistics and the selection words (cleared by slab_keys / mask_keys inside the plan)."""
+    statistics and the selection words (cleared by slab_keys / mask_keys inside the plan); with candidates=True also the
+    candidate list of detect_seeds (several hands of one frame)."""
 
-    def __init__(self, rt, B, H, W, stats=True):
+    def __init__(self, rt, B, H, W, stats=True, candidates=False):
         lib = rt.lib
         nb = int(lib.dpp_label_workspace_bytes(B, H, W))
         if nb == 0 or int(lib.dpp_component_stats_bytes(1, 1, 1)) != COMPONENT_STAT.itemsize:
@@ -865,6 +876,7 @@ class ComponentWorkspace(object):
         self.labels = rt.alloc((B, H, W), np.int32, zero=False)
         self.stats = rt.alloc(int(lib.dpp_component_stats_bytes(B, H, W)), np.uint8, zero=False) if stats else None
         self.state = rt.alloc(int(lib.dpp_detect_state_bytes(B)) // 8, np.int64)
+        self.candidates = rt.alloc(int(lib.dpp_detect_candidates_bytes(B, H, W)) // 8, np.int64, zero=False) if candidates else None
 
 
 def slab_keys(rt, frames, partial, ws, name='slab_keys'):
@@ -894,6 +906,18 @@ def detect_seed(rt, frames, partial, ws, com_out, status, name='detect_seed'):
     return Launch(rt.lib.dpp_detect_seed, (frames.ptr, partial.ptr, ws.keys.ptr, ws.labels.ptr, ws.stats.ptr, B, H, W, ws.state.ptr, com_out.ptr,
                                            status.ptr),
                   (frames, partial, ws, com_out, status), name, kernels=2)
+
+
+def detect_seeds(rt, frames, partial, ws, K, seed_out, status, report, max_extent=None, fx=1.0, fy=1.0, name='detect_seeds'):
+    """dpp_detect_seeds: up to K seeds per frame (rows b * K + k) -- the candidates of more than 200 px in (key, root) order, minus
+    those wider or higher than max_extent mm (None / 0: off), greedily selected under window suppression -- and the per-slot report."""
+    B, H, W = ws.B, ws.H, ws.W
+    if ws.candidates is None:
+        raise ValueError("detect_seeds needs a ComponentWorkspace(candidates=True)")
+    return Launch(rt.lib.dpp_detect_seeds, (frames.ptr, partial.ptr, ws.keys.ptr, ws.labels.ptr, ws.stats.ptr, B, H, W, ws.state.ptr,
+                                            ws.candidates.ptr, int(K), float(max_extent or 0.0), float(fx), float(fy), seed_out.ptr, status.ptr,
+                                            report.ptr),
+                  (frames, partial, ws, seed_out, status, report), name, kernels=3)
 
 
 def hand_size(rt, ws, com, cube_in, fx, fy, cube_out, status, tol=0.0, name='hand_size'):

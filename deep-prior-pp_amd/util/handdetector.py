@@ -459,15 +459,25 @@ class HandDetector(object):
           2. among the components of the winning slab the raster-first one (smallest y * W + x) wins, not cv2's contour order;
           3. a depth exactly on a slab boundary belongs to the nearer slab only (the reference keeps it in both)."""
 
-    def detectComponents(self, size=(250, 250, 250), doHandSize=True):
+    def detectComponents(self, size=(250, 250, 250), doHandSize=True, max_hands=1, max_extent=None):
         """Detect the hand as the closest object to the camera, by connected components on the device: the depth range in 20 slabs,
         nearest first; the first slab with an 8-connected component of more than 200 px; the centre of mass of the +-100 px window
         around that component's centroid inside the slab; refineCoMIterative(com, 5, size); with doHandSize the cube from the bounding
         box of the largest component of the depth range com_z -+ size_z / 2 (estimateHandsizeComponents).  Returns (com, size) with
         detect's convention (handdetector.py:569-632): no hand gives ((0, 0, 0), size).
+
+        max_hands=K > 1 returns up to K hands of the frame (find_hands): (coms (K, 3) float64, size), an empty slot being (0, 0, 0);
+        max_extent (mm) keeps components wider or higher than that out.  Hand size is a one-hand procedure: with K > 1 doHandSize
+        must not be True (ValueError).
         """
+        if int(max_hands) > 1:
+            if doHandSize is True:
+                raise ValueError("hand size is measured for one hand per frame: doHandSize needs max_hands=1")
+            coms, _, found = find_hands(numpy.asarray(self.dpt, numpy.float32)[None], numpy.asarray(size, numpy.float32)[None], self.fx,
+                                        self.fy, max_hands=max_hands, max_extent=max_extent)
+            return numpy.where(found[0][:, None], coms[0], 0).astype(numpy.float64), size
         coms, cubes, found = find_hands(numpy.asarray(self.dpt, numpy.float32)[None], numpy.asarray(size, numpy.float32)[None], self.fx,
-                                        self.fy, do_hand_size=doHandSize is True)
+                                        self.fy, do_hand_size=doHandSize is True, max_extent=max_extent)
         if not found[0]:
             return numpy.array((0, 0, 0), numpy.float64), size
         if doHandSize is True:
@@ -761,17 +771,26 @@ def label_components(keys, runtime=None, return_stats=False):
     return labels, stats
 
 
-def _detector(rt, H, W, fx, fy, B):
+def _detector(rt, H, W, fx, fy, B, hands=1, max_extent=None):
     from hipdp import detect
-    return _cached(('detector', rt, B, H, W, abs(float(fx)), abs(float(fy))), lambda: detect.FrameDetector(rt, H, W, fx, fy, B))
+    ext = float(max_extent) if max_extent else 0.0
+    return _cached(('detector', rt, B, H, W, abs(float(fx)), abs(float(fy)), int(hands), ext),
+                   lambda: detect.FrameDetector(rt, H, W, fx, fy, B, hands=hands, max_extent=max_extent))
 
 
-def find_hands(frames, cubes, fx, fy, do_hand_size=False, runtime=None, return_seed=False, chunk=8):
+def find_hands(frames, cubes, fx, fy, do_hand_size=False, runtime=None, return_seed=False, chunk=8, max_hands=1, max_extent=None):
     """Batched HandDetector.detectComponents: frames (B, H, W) raw depth in mm, cubes (B, 3) -> (coms (B, 3) float32 in image
     coordinates, cubes (B, 3) float32, found (B,) bool).  One device plan per chunk of frames (hipdp.detect.FrameDetector, kept
     per frame shape and used again by later calls): depth
     range, slab keys, labelling, seed, refineCoMIterative(5) and, with do_hand_size, the hand's cube; a frame without a hand gets
-    com (0, 0, 0) and its input cube.  return_seed adds the centres before the refinement."""
+    com (0, 0, 0) and its input cube.  return_seed adds the centres before the refinement.
+
+    max_hands=K > 1 finds up to K hands per frame in the same plan (one launch more): coms (B, K, 3), cubes (B, K, 3) (the frame's
+    cube in every slot), found (B, K), seeds likewise; slot k is the k-th accepted component in (slab, raster) order, empty slots are
+    all zero.  The candidates are the components of more than 200 px; one whose centroid lies in the +-100 px seed window of an
+    accepted one is suppressed (a hand across a slab boundary is two components), and with max_extent (mm) one wider or higher than
+    that at its slab's far bound is no candidate at all (a wall is no hand).  Both rules are this project's, not the reference's.
+    max_hands=1 returns today's shapes.  Hand size is a one-hand procedure: do_hand_size with max_hands > 1 raises ValueError."""
     from hipdp.runtime import default_runtime
     rt = runtime or default_runtime()
     frames = numpy.ascontiguousarray(frames, numpy.float32)
@@ -779,11 +798,24 @@ def find_hands(frames, cubes, fx, fy, do_hand_size=False, runtime=None, return_s
         raise ValueError("frames must be (B, H, W)")
     B, H, W = frames.shape
     cubes = numpy.ascontiguousarray(cubes, numpy.float32).reshape(B, 3)
-    coms, sizes, found, seeds = (numpy.zeros((B, 3), numpy.float32), cubes.copy(), numpy.zeros(B, bool), numpy.zeros((B, 3), numpy.float32))
+    K = int(max_hands)
+    if do_hand_size and K > 1:
+        raise ValueError("hand size is measured for one hand per frame: do_hand_size needs max_hands=1")
+    if K == 1 and not max_extent:
+        coms, sizes, found, seeds = (numpy.zeros((B, 3), numpy.float32), cubes.copy(), numpy.zeros(B, bool), numpy.zeros((B, 3), numpy.float32))
+        for i0 in range(0, B, chunk):
+            n = min(chunk, B - i0)
+            det = _detector(rt, H, W, fx, fy, n)
+            coms[i0:i0 + n], sizes[i0:i0 + n], found[i0:i0 + n], seeds[i0:i0 + n], _ = det.run(frames[i0:i0 + n], cubes[i0:i0 + n], do_hand_size)
+        return (coms, sizes, found, seeds) if return_seed else (coms, sizes, found)
+    coms, sizes, found, seeds = (numpy.zeros((B, K, 3), numpy.float32), numpy.zeros((B, K, 3), numpy.float32), numpy.zeros((B, K), bool),
+                                 numpy.zeros((B, K, 3), numpy.float32))
     for i0 in range(0, B, chunk):
         n = min(chunk, B - i0)
-        det = _detector(rt, H, W, fx, fy, n)
-        coms[i0:i0 + n], sizes[i0:i0 + n], found[i0:i0 + n], seeds[i0:i0 + n], _ = det.run(frames[i0:i0 + n], cubes[i0:i0 + n], do_hand_size)
+        det = _detector(rt, H, W, fx, fy, n, K, max_extent)
+        coms[i0:i0 + n], sizes[i0:i0 + n], found[i0:i0 + n], seeds[i0:i0 + n] = det.run(frames[i0:i0 + n], cubes[i0:i0 + n], do_hand_size)[:4]
+    if K == 1:                                       # one hand under the extent filter: today's shapes
+        coms, sizes, found, seeds = coms[:, 0], sizes[:, 0], found[:, 0], seeds[:, 0]
     return (coms, sizes, found, seeds) if return_seed else (coms, sizes, found)
 
 

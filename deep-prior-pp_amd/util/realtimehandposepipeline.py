@@ -397,12 +397,15 @@ class MultiStreamPipeline(object):
 
     Seeds: init_com= one centre per track (image coordinates of its device, z in mm; None for a track without one), and / or
     seed_detect=True: a track without a centre -- never seeded, or lost -- is searched for in its device's next frame by the
-    component detector (MultiTracker.acquire), as RealtimeHandposePipeline's _need_seed does after a lost frame.  The detector finds
-    the nearest object, so of two tracks on one device only the first is acquired that way; the other needs its init_com."""
+    component detector, as RealtimeHandposePipeline's _need_seed does after a lost frame: ONE detector plan per device with lost
+    tracks (MultiTracker.acquire_source) finds as many hands as the device has tracks and shares them out -- followed tracks keep
+    theirs, the lost ones take the rest, nearest first -- so both hands of one camera start, and come back, without an init_com.
+    max_extent (mm) keeps things larger than a hand (a wall behind one hand) from being taken for the second."""
 
     HAND_LEFT, HAND_RIGHT = RealtimeHandposePipeline.HAND_LEFT, RealtimeHandposePipeline.HAND_RIGHT
 
-    def __init__(self, poseNet, config, di, devices, hands, comrefNet, init_com=None, seed_detect=False, sensor=None, verbose=False):
+    def __init__(self, poseNet, config, di, devices, hands, comrefNet, init_com=None, seed_detect=False, sensor=None, verbose=False,
+                 max_extent=None):
         """
         :param poseNet, comrefNet: built nets or their parameters (as for RealtimeHandposePipeline), with batchSize == len(hands)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=])
@@ -412,7 +415,9 @@ class MultiStreamPipeline(object):
         :param init_com:  None, or one centre (or None) per track
         :param seed_detect: acquire tracks without a centre by detection, again after they are lost
         :param sensor:    as for RealtimeHandposePipeline, for all devices
+        :param max_extent: None, or the largest metric width / height (mm) of a component that seed_detect may take for a hand
         """
+        self.max_extent = max_extent
         self.poseNet, self.comrefNet, self.importer = poseNet, comrefNet, di
         self.config = copy.deepcopy(config)
         self.devices = list(devices)
@@ -455,17 +460,21 @@ class MultiStreamPipeline(object):
 
     def processFrames(self, frames):
         """One tick: one frame (or None) per device -> one result dict per track (MultiTracker.process).  Tracks without a centre are
-        seeded first: from init_com once, else (seed_detect) by detection in their device's frame."""
+        seeded first: from init_com once, else (seed_detect) by detection in their device's frame -- one detector plan per device
+        for all its lost tracks."""
         shape = next(numpy.asarray(f).shape for f in frames if f is not None)
         mt = self.tracker(*shape)
+        search = set()
         for t, (d, _) in enumerate(self.hands):
             if not mt.lost[t] or frames[d] is None:
                 continue
             if not self._seeded[t] and self.init_com[t] is not None:
                 mt.reset(t, self.init_com[t])
             elif self.seed_detect:
-                mt.acquire(t, frames[d])
+                search.add(d)
             self._seeded[t] = True
+        for d in sorted(search):
+            mt.acquire_source(d, frames[d], max_extent=self.max_extent)
         return mt.process(frames)
 
     def processVideos(self, max_frames=None):

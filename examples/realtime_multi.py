@@ -5,9 +5,11 @@ cameras, and three hands are followed at once -- the left- and the right-hand vi
 second (util.realtimehandposepipeline.MultiStreamPipeline on hipdp/multitrack.py).  The nets are built for a batch of three; a tick
 costs the launches of ONE single-hand tracker (examples/test_realtimepipeline.py), whatever the number of hands.
 
-Every track is seeded with its sequence's annotated centre of the first frame (both views of the first camera with the same one; a
-detector that tells two hands of one frame apart is not built), or, with --seed detect, the tracks that are alone on their camera by
-connected-component detection.  Prints the time per tick and, where the annotations match the pose net's joints, the mean joint error
+Every track is seeded with its sequence's annotated centre of the first frame (both views of the first camera with the same one),
+or, with --seed detect, the tracks that are alone on their camera by connected-component detection.  With --seed detect-all no
+annotation is used at all: both tracks of the first camera are started by ONE detector plan that returns two hands of a frame
+(nearest first; --max-extent MM keeps a wall behind a single hand from being taken for the second -- without a second hand in view
+the second track then stays lost).  Prints the time per tick and, where the annotations match the pose net's joints, the mean joint error
 of every left-hand track.  Checkpoints are optional: without them the nets have random weights (a dry run of the machinery).
 
     python examples/realtime_multi.py --dataset icvl --data ../data/ICVL/ --seqs test_seq_1 test_seq_2
@@ -43,7 +45,9 @@ def main(argv=None):
     ap.add_argument('--joints', type=int, default=None, help="the pose net's joints (default: the sequences')")
     ap.add_argument('--pose-net', default=None, help='checkpoint of the pose net')
     ap.add_argument('--comref-net', default=None, help='checkpoint of the ScaleNet centre refinement')
-    ap.add_argument('--seed', choices=['gt', 'detect'], default='gt', help="first centres: the annotations, or detection where a camera has one track")
+    ap.add_argument('--seed', choices=['gt', 'detect', 'detect-all'], default='gt',
+                    help="first centres: the annotations, detection where a camera has one track, or detection for every track")
+    ap.add_argument('--max-extent', type=float, default=None, help='with detection: the largest width / height (mm) of a hand candidate')
     ap.add_argument('--max-frames', type=int, default=None)
     ap.add_argument('--cache', default='./cache/')
     args = ap.parse_args(argv)
@@ -68,8 +72,11 @@ def main(argv=None):
     init = [seqs[d].data[0].gtorig[di.crop_joint_idx] for d, _ in hands]
     if args.seed == 'detect':
         init[2] = None                                                 # alone on its camera: found by the detector
+    elif args.seed == 'detect-all':
+        init = [None] * T                                              # both hands of camera 0 from one detector plan
     devices = [FileDevice([f.fileName for f in s.data], di) for s in seqs]
-    msp = MultiStreamPipeline(poseNetParams, config, di, devices, hands, comrefNetParams, init_com=init, seed_detect=args.seed == 'detect')
+    msp = MultiStreamPipeline(poseNetParams, config, di, devices, hands, comrefNetParams, init_com=init, seed_detect=args.seed != 'gt',
+                              max_extent=args.max_extent)
     poses = msp.processVideos(max_frames=args.max_frames)
     t = numpy.asarray(msp.frame_times[1:] or msp.frame_times)         # the first tick records the plan
     print("{} ticks, {} tracks, {:.3f} ms per tick (median; {:.3f} ms mean)".format(len(msp.frame_times), T, numpy.median(t) * 1000., t.mean() * 1000.))

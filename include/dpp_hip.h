@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 16
+#define DPP_ABI_VERSION 17
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -589,6 +589,31 @@ int dpp_detect_seed(const float* frames, const float* partial, const unsigned ch
                     int W, void* state, float* com_out, int* status, dpp_stream_t stream);
 int dpp_hand_size(const unsigned char* keys, const int* labels, const void* stats, int B, int H, int W, void* state, const float* com,
                   const float* cube_in, double fx, double fy, double tol, float* cube_out, int* status, dpp_stream_t stream);
+
+/* ---- several hands of one frame (ABI v17) ------------------------------------------------------------------------------------------
+ * detect_seeds: up to K seeds per frame from the labelling of slab_keys + label_components (with stats), in detect_seed's place.
+ *   Candidates: the components of more than 200 px, ordered by (key, root): nearest slab first, then raster-first.  With
+ *   max_extent > 0 (mm; 0: off) a candidate is dropped when (xmax - xmin + 1) * b_{key+1} / |fx| > max_extent or the same in y with
+ *   |fy| (float64, in that order): a far wall is no hand.  A dropped candidate suppresses nothing.
+ *   Selection: the candidates are walked in order; one whose centroid (rint of sum / count, float64) lies inside the seed window
+ *   [xs, xe) x [ys, ye) of an ACCEPTED candidate is suppressed (one hand across a slab boundary is two components), any other is
+ *   accepted, until K are.  Suppressed candidates suppress nothing.
+ *   Row b * K + k of seed_out [B * K][3] / status [B * K] is detect_seed's result for the k-th accepted component of frame b;
+ *   report [B * K][6] int32 = its key, pixel count, xmin, xmax, ymin, ymax.  A slot without a component: seed (0, 0, 0), status
+ *   0, report all zero.  K = 1 with max_extent 0 gives detect_seed's bytes.
+ *   state: as for detect_seed; word 0 of a frame (which slab_keys cleared) counts the frame's candidates.  candidates:
+ *   dpp_detect_candidates_bytes(B, H, W) bytes, (2 * (H * W / 201) + 16) 64-bit words per frame: the list cannot overflow, since
+ *   components of more than 200 px are disjoint.  Three launches.  DPP_E_BADARG (nothing launched): a NULL pointer, the
+ *   labelling's limits, K outside [1, 16], max_extent negative or not finite, max_extent > 0 with fx or fy 0.
+ * refine_com_iterative_ix: R rows; row r refines com_in[r] in frame src[r] with that frame's partials and cube [C][3] (the rows of
+ *   a frame share its cube); the caller guarantees 0 <= src[r] < C.  src NULL: row r reads frame r, the plain entry point. */
+#define DPP_DETECT_MAX_HANDS 16
+size_t dpp_detect_candidates_bytes(int B, int H, int W);
+int dpp_detect_seeds(const float* frames, const float* partial, const unsigned char* keys, const int* labels, const void* stats, int B, int H,
+                     int W, void* state, void* candidates, int K, double max_extent, double fx, double fy, float* seed_out, int* status,
+                     int* report, dpp_stream_t stream);
+int dpp_refine_com_iterative_ix(const float* frames, const float* partial, int R, const int* src, int H, int W, const float* com_in,
+                                const float* cube, double fx, double fy, int num_iter, float* com_out, int* status, dpp_stream_t stream);
 
 /* ---- PCA prior set-up and evaluation on the device --------------------------------------------
  * pose_sample: HandDetector.sampleRandomPoses (/root/reference/src/util/handdetector.py:805-909) for n samples: sample i augments
