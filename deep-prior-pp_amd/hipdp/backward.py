@@ -229,6 +229,7 @@ class BackwardMixin(object):
                 if hz.TAIL_REDUCE and self.reduce_jobs.jobs:
                     # the partials collected so far are reduced on the gradient branch BESIDE the stem's filter gradient (the last
                     # launch of the main stream, which otherwise idles at the join while reduce_multi waits behind it)
+                    ops.one_side_stream_only("DPP_TAIL_REDUCE (reduce_multi_side sums the partials of every earlier filter-gradient group)")
                     self.bwd.fork()
                     self.bwd.add(self.reduce_jobs.flush('reduce_multi_side'), side=True)
                 self._bwd_stem(layer, io, dY)
@@ -242,6 +243,7 @@ class BackwardMixin(object):
             else:
                 raise NotImplementedError(kind)
             if hz.EARLY_REDUCE_BYTES > 0 and self.reduce_jobs.pending_bytes() >= hz.EARLY_REDUCE_BYTES:
+                ops.one_side_stream_only("DPP_EARLY_REDUCE_MB (reduce_multi_early sums the partials of the filter-gradient groups before it)")
                 self.bwd.fork()
                 self.bwd.add(self.reduce_jobs.flush('reduce_multi_early'), side=True)
         self._defer_fc1_wgrad()

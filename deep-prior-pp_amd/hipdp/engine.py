@@ -752,6 +752,9 @@ class CompiledNet(BackwardMixin):
             return self.bwd, self.upd
         if '_early_adam_cache' in self.__dict__:
             return self._early_adam_cache
+        # (adam_fc1 sits in a fork group of its own -- it has to wait for FC1's data gradient on the main stream -- behind the group
+        #  whose fc_wgrad launch writes the gradient it reads)
+        ops.one_side_stream_only("DPP_EARLY_ADAM (the early FC1 update)")
         rt, st = self.rt, self.store
         lo, hi, n = ea['lo'], ea['hi'], st.n_w
         sl = lambda b, a, z: b.view(a, (z - a,))          # noqa: E731

@@ -47,6 +47,27 @@ class Join(object):
 LAUNCH_MODE = os.environ.get('DPP_LAUNCH_MODE', 'native')
 
 
+def _side_streams():
+    try:
+        return max(1, min(8, int(os.environ.get('DPP_SIDE_STREAMS', '1'))))
+    except ValueError:
+        return 1
+
+
+# Side streams of the native runner (csrc/plan.hip reads the same variable).  With S > 1 the launches between two forks are a group,
+# groups are dealt round-robin to S streams that are NOT ordered against each other: a plan is only valid there if no side launch
+# depends on a side launch of an earlier group.  The engine checks this number where it builds a plan that has such a dependency.
+SIDE_STREAMS = _side_streams()
+
+
+def one_side_stream_only(what):
+    """Called where a plan is built whose gradient-branch groups depend on each other: refuse it for DPP_SIDE_STREAMS > 1."""
+    if SIDE_STREAMS > 1:
+        raise NotImplementedError("%s puts launches on the gradient branch that read what an EARLIER fork group of the branch wrote; with "
+                                  "DPP_SIDE_STREAMS=%d the groups run on streams that are not ordered against each other.  Use one side "
+                                  "stream (DPP_SIDE_STREAMS=1) or turn the knob off." % (what, SIDE_STREAMS))
+
+
 class NativePlan(object):
     """A run of launches / fork / join markers recorded into a dpp_plan.  Recording calls every prepared op once with the
     library in recording mode: the C side keeps the resolved kernel, grid and a private copy of the arguments."""
