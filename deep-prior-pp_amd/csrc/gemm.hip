@@ -187,11 +187,14 @@ extern "C" int dpp_gemm_variant_rows(const dpp_gemm_desc* dp) {
     return 0;
 }
 
-extern "C" int dpp_gemm(const dpp_gemm_desc* dp, dpp_stream_t stream) {
+// dpp_gemm for a checked descriptor; walk_grid != nullptr (dpp_gemm_walk_grid): nothing is launched, the variant-0 dispatch only reports
+// the grid its walking form would take
+static int gemm_run(const dpp_gemm_desc* dp, dpp_stream_t stream, int* walk_grid) {
     GemmArgs ga;
     const int prep = gemm_prepare(dp, ga);
     if (prep != DPP_OK) return prep;
     dpp_gemm_desc& d = ga.d;
+    if (walk_grid != nullptr && d.variant != 0) return DPP_OK;
     const bool red_layout = !d.a_kc && !d.b_kc;
     static const int bk64_min_k = []() { const char* e = getenv("DPP_GEMM_BK64_MINK"); return e ? atoi(e) : 128; }();
     ga.bk = (d.K > 16) ? 32 : 16;
@@ -220,9 +223,21 @@ extern "C" int dpp_gemm(const dpp_gemm_desc* dp, dpp_stream_t stream) {
     if (d.precision == 1) {
         // 8 k-values per lane and chunk: chunks of 32 / 64 (K > 16), or the K = 16 stream kernel (zero upper half)
         if (d.variant == 0 && !red_layout && ga.bk < 32) return DPP_E_UNSUPPORTED;
-        return dpp_gemm_dispatch_pb(ga, bm, bn, wm, st);
+        return dpp_gemm_dispatch_pb(ga, bm, bn, wm, st, walk_grid);
     }
-    return d.store ? dpp_gemm_dispatch_st(ga, bm, bn, wm, st) : gemm_dispatch<false>(ga, bm, bn, wm, st);
+    return d.store ? dpp_gemm_dispatch_st(ga, bm, bn, wm, st, walk_grid) : gemm_dispatch<false>(ga, bm, bn, wm, st, walk_grid);
+}
+
+extern "C" int dpp_gemm(const dpp_gemm_desc* dp, dpp_stream_t stream) { return gemm_run(dp, stream, nullptr); }
+
+extern "C" int dpp_gemm_walk_grid(const dpp_gemm_desc* dp, int* gx, int* gy) {
+    int grid[2] = {0, 0};
+    if (!gx || !gy) return 0;
+    *gx = *gy = 0;
+    if (gemm_run(dp, nullptr, grid) != DPP_OK) return 0;
+    *gx = grid[0];
+    *gy = grid[1];
+    return grid[0] > 0 ? 1 : 0;
 }
 
 extern "C" size_t dpp_reduce_job_bytes(void) { return sizeof(ReduceJob); }

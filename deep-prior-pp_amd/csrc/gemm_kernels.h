@@ -200,6 +200,81 @@ struct Stager {
     static constexpr int LD = KC ? (BKT + 4) : (ROWS + 4);
 };
 
+// The products of ONE K chunk of gemm_walk_kernel (As / Bs: the chunk images in Stager's layout, A K-contiguous): gemm_kernel's chunk body
+// instruction for instruction -- the order of the MFMAs is what fixes the bits of the result -- kept apart from it so that the one-tile kernels
+// compile to exactly what they were (called from there, the register allocation of a third of gemm_kernel's instantiations moved by 4 - 28).
+// Lane (i, kq) owns k = kq * KL + e of the chunk on both sides.
+template <int BM, int BN, int WM, int BKT, bool BKC, bool PB, int RM, int CN>
+__device__ __forceinline__ void gemm_walk_products(f32x4 (&acc)[RM][CN], const float* As, const float* Bs, int wm, int wn, int l15, int kq) {
+    constexpr int WN = 4 / WM;
+    constexpr int LDA_ = Stager<BM, BKT, true>::LD, LDB_ = Stager<BN, BKT, BKC>::LD;
+    constexpr int KL = BKT / 4;
+    if constexpr (PB) {
+#pragma unroll
+        for (int e8 = 0; e8 < KL; e8 += 8) {
+            dpp_bf16x8 af[RM], bf[CN];
+#pragma unroll
+            for (int rt = 0; rt < RM; ++rt) {
+                const int r = wm * (BM / WM) + rt * 16 + l15;
+                float f[8];
+                const float4 v0 = *reinterpret_cast<const float4*>(&As[r * LDA_ + kq * KL + e8]);
+                const float4 v1 = *reinterpret_cast<const float4*>(&As[r * LDA_ + kq * KL + e8 + 4]);
+                f[0] = v0.x; f[1] = v0.y; f[2] = v0.z; f[3] = v0.w; f[4] = v1.x; f[5] = v1.y; f[6] = v1.z; f[7] = v1.w;
+#pragma unroll
+                for (int t = 0; t < 8; ++t) af[rt][t] = (dpp_bf16)f[t];
+            }
+#pragma unroll
+            for (int ct = 0; ct < CN; ++ct) {
+                const int cc = wn * (BN / WN) + ct * 16 + l15;
+                float f[8];
+                if (BKC) {
+                    const float4 v0 = *reinterpret_cast<const float4*>(&Bs[cc * LDB_ + kq * KL + e8]);
+                    const float4 v1 = *reinterpret_cast<const float4*>(&Bs[cc * LDB_ + kq * KL + e8 + 4]);
+                    f[0] = v0.x; f[1] = v0.y; f[2] = v0.z; f[3] = v0.w; f[4] = v1.x; f[5] = v1.y; f[6] = v1.z; f[7] = v1.w;
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) f[t] = Bs[(kq * KL + e8 + t) * LDB_ + cc];
+                }
+#pragma unroll
+                for (int t = 0; t < 8; ++t) bf[ct][t] = (dpp_bf16)f[t];
+            }
+#pragma unroll
+            for (int rt = 0; rt < RM; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < CN; ++ct)
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[rt], bf[ct], acc[rt][ct], 0, 0, 0);
+        }
+    } else
+#pragma unroll
+    for (int e4 = 0; e4 < KL; e4 += 4) {
+        float af[RM][4], bf[CN][4];
+#pragma unroll
+        for (int rt = 0; rt < RM; ++rt) {
+            int r = wm * (BM / WM) + rt * 16 + l15;
+            float4 v = *reinterpret_cast<const float4*>(&As[r * LDA_ + kq * KL + e4]);
+            af[rt][0] = v.x; af[rt][1] = v.y; af[rt][2] = v.z; af[rt][3] = v.w;
+        }
+#pragma unroll
+        for (int ct = 0; ct < CN; ++ct) {
+            int cc = wn * (BN / WN) + ct * 16 + l15;
+            if (BKC) {
+                float4 v = *reinterpret_cast<const float4*>(&Bs[cc * LDB_ + kq * KL + e4]);
+                bf[ct][0] = v.x; bf[ct][1] = v.y; bf[ct][2] = v.z; bf[ct][3] = v.w;
+            } else {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) bf[ct][t] = Bs[(kq * KL + e4 + t) * LDB_ + cc];
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int rt = 0; rt < RM; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < CN; ++ct)
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[rt][t], bf[ct][t], acc[rt][ct], 0, 0, 0);
+    }
+}
+
 // ST: the instantiation may meet bf16-stored operands / outputs (DPP_ST_*); the float32 instantiations carry none of that code
 // PB (dpp_gemm_desc.precision = 1, BASELINE config 5, round 6): both operands are rounded to bfloat16 (RNE; the activation after its
 // prologue) when the fragments are read from the float32 LDS images, eight k-values of a lane become ONE v_mfma_f32_16x16x32_bf16
@@ -572,6 +647,163 @@ __global__ __launch_bounds__(DPP_THREADS) void gemm_kernel(GemmArgs ga) {
         }, 0, d.store);
     }
     else gemm_epilogue<RM, CN, WM, WN, BM, BN>(acc, d, row0, col0, wm, wn, l15, kq, As);
+    dpp_stamp(ga.prof, 4);
+}
+
+// ---- the LDS-tiled kernel WALKING its row tiles (variant 0 launches of more workgroups than are resident at once) ------------------------
+// gemm_kernel is allocated 130-220 registers: two or three workgroups fit a CU, so the 1 024 - 2 048 tile launches of the stride-2 stage
+// entries, the projection shortcuts and their data gradients ran as 1.3 - 2.7 rounds, each round paying the entry code (kernarg lines,
+// coefficient vectors, a cold B tile) again and the last one leaving most CUs idle.  Here the launch is what is resident, workgroup b takes row
+// tiles b, b + gridDim.x, ...: the WHOLE K x BN panel of B (K <= 128; one image per K chunk, in gemm_kernel's chunk layout, behind the A chunk /
+// epilogue image) and the per-column vectors of the epilogue are staged once, and the A rows of the next tile are requested -- unconditionally,
+// rows clamped to the last one -- as soon as the barrier has published the current tile's last chunk, so they travel under its products and
+// epilogue: gemm_kernel's register prefetch carried across tiles.  Per tile the arithmetic is gemm_kernel's (same chunks, same MFMA order, the same
+// dpp_epilogue_wide with the TILE's index in the statistics partials): the results are bit-identical to one workgroup per tile.
+// The host only sends problems here that are gemm_kernel's fast path but for ragged last rows: K-contiguous A with 16-byte quads and a mode 0-3
+// prologue in channel quads, plain B with 16-byte quads, whole column tiles, whole K chunks, the 16-byte epilogue (walk_eligible).
+// The loop bound comes from the kernel arguments alone; workgroups do not talk to each other.
+template <int BM, int BN, int WM, int BKT, bool BKC, bool ST = false, bool PB = false>
+__global__ __launch_bounds__(DPP_THREADS) void gemm_walk_kernel(GemmArgs ga) {
+    static_assert(!PB || BKT % 32 == 0, "bf16 MFMA operands: 8 k-values per lane and chunk");
+    dpp_kernarg_warm<sizeof(GemmArgs)>();
+    const dpp_gemm_desc& d = ga.d;
+    HIP_DYNAMIC_SHARED(float4, smem4)
+    float* const smem = reinterpret_cast<float*>(smem4);
+    constexpr int WN = 4 / WM;
+    constexpr int RM = BM / (16 * WM);
+    constexpr int CN = BN / (16 * WN);
+    using SA = Stager<BM, BKT, true>;
+    using SB = Stager<BN, BKT, BKC>;
+    constexpr int LDA_ = SA::LD, LDB_ = SB::LD;
+    constexpr int QA = SA::QK;                               // float4 per staged A row
+    constexpr int RSTEP = DPP_THREADS / QA;                  // A rows between two staging slots of a thread
+    static_assert((BM * QA) % DPP_THREADS == 0 && DPP_THREADS % QA == 0, "whole staging slots");
+    constexpr int SZA = BM * LDA_;
+    constexpr int SZB = BKC ? BN * LDB_ : BKT * LDB_;
+    constexpr int SZE = BM * (BN + 4) + 16 * BN;             // tile image + reduction scratch of the wide epilogue
+    constexpr int A_REGION = SZA > SZE ? SZA : SZE;          // (the launcher sizes the LDS with the same expressions: walk_lds_bytes)
+    float* const As = smem;
+    float* const Bs = smem + A_REGION;                       // K / BKT chunk images, resident for the whole walk
+
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int wm = wave / WN, wn = wave % WN;
+    const int l15 = lane & 15, kq = lane >> 4;
+    const int col0 = blockIdx.y * BN;
+    const int M = d.M, N = d.N, K = d.K;
+    const int nchunks = K / BKT, ntiles = (M + BM - 1) / BM;
+    const int shA = ST ? ga.shA : 0, shB = ST ? ga.shB : 0;
+    const int modeA = d.actA.mode;
+    dpp_stamp(ga.prof, 0);
+
+    // ---- B panel: every load of it up front, then the first tile's first A chunk behind them ----
+    constexpr int BSLOTS = (128 / 4 * BN + DPP_THREADS - 1) / DPP_THREADS;      // K <= 128
+    const int nquads = (K >> 2) * BN;
+    float4 rbp[BSLOTS];
+#pragma unroll
+    for (int s = 0; s < BSLOTS; ++s) {
+        const int idx = tid + s * DPP_THREADS;
+        rbp[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (idx < nquads) {
+            size_t e;                                        // element offset of the quad in B
+            if (BKC) { const int j = idx / (K >> 2), k = (idx - j * (K >> 2)) * 4; e = (size_t)(col0 + j) * d.ldb + k; }
+            else { const int k = idx / (BN / 4), j4 = idx % (BN / 4); e = (size_t)k * d.ldb + col0 + j4 * 4; }
+            rbp[s] = shB ? dpp_raw8(d.B + (e >> 1)) : *reinterpret_cast<const float4*>(d.B + e);
+        }
+    }
+
+    // ---- A staging: slot s of a thread is row (tid / QA + s * RSTEP) of the tile, k-quad qa of the chunk ----
+    const int qa = (tid % QA) * 4, ar = tid / QA;
+    const int ldsA0 = ar * LDA_ + qa;
+    struct Co4 { float4 mu, sc, be; };
+    Co4 co;
+    co.mu = co.sc = co.be = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float* a_base[SA::SLOTS];
+    float4 ra[SA::SLOTS];
+    // rows of a tile (any tile index: rows at or beyond M read row M - 1 and are zeroed at the commit)
+    auto set_rows = [&](int tile) {
+#pragma unroll
+        for (int s = 0; s < SA::SLOTS; ++s) {
+            const int gi = tile * BM + ar + s * RSTEP;
+            a_base[s] = d.A + (((size_t)dpp_map_row(d.mapA, gi < M ? gi : M - 1) * d.lda) >> shA);
+        }
+    };
+    auto fetch = [&](int kc) {
+        if (modeA & 2) {
+            const int c0 = kc + qa, c = c0 < d.actA.cmod ? c0 : c0 % d.actA.cmod;
+            co.mu = *reinterpret_cast<const float4*>(d.actA.mean + c);
+            co.sc = *reinterpret_cast<const float4*>(d.actA.scale + c);
+            co.be = *reinterpret_cast<const float4*>(d.actA.beta + c);
+        }
+        if (shA) {
+#pragma unroll
+            for (int s = 0; s < SA::SLOTS; ++s) ra[s] = dpp_raw8(a_base[s] + ((kc + qa) >> 1));
+        } else {
+#pragma unroll
+            for (int s = 0; s < SA::SLOTS; ++s) ra[s] = *reinterpret_cast<const float4*>(a_base[s] + kc + qa);
+        }
+    };
+    // the BN + ReLU prologue is applied HERE, when the chunk is written to LDS (see gemm_kernel's commit)
+    auto commit = [&](int tile) {
+#pragma unroll
+        for (int s = 0; s < SA::SLOTS; ++s) {
+            float4 v = shA ? dpp_widen4(ra[s]) : ra[s];
+            if (modeA & 2) {
+                v.x = dpp_fma(v.x - co.mu.x, co.sc.x, co.be.x);
+                v.y = dpp_fma(v.y - co.mu.y, co.sc.y, co.be.y);
+                v.z = dpp_fma(v.z - co.mu.z, co.sc.z, co.be.z);
+                v.w = dpp_fma(v.w - co.mu.w, co.sc.w, co.be.w);
+            }
+            if (modeA & 1) { v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f); }
+            if (tile * BM + ar + s * RSTEP >= M) v = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(&As[ldsA0 + s * RSTEP * LDA_]) = v;
+        }
+    };
+
+    int tile = blockIdx.x;
+    set_rows(tile);
+    fetch(0);
+    dpp_wide_coef wco;
+    wco.load<BN>(col0, N, d.bias, d.epi, d.C);
+    dpp_stamp(ga.prof, 1);
+#pragma unroll
+    for (int s = 0; s < BSLOTS; ++s) {
+        const int idx = tid + s * DPP_THREADS;
+        if (idx < nquads) {
+            const float4 v = shB ? dpp_widen4(rbp[s]) : rbp[s];
+            int k, o;                                        // k of the quad, its place in the chunk image
+            if (BKC) { const int j = idx / (K >> 2); k = (idx - j * (K >> 2)) * 4; o = j * LDB_ + k % BKT; }
+            else { k = idx / (BN / 4); o = (k % BKT) * LDB_ + (idx % (BN / 4)) * 4; }
+            *reinterpret_cast<float4*>(&Bs[(k / BKT) * SZB + o]) = v;
+        }
+    }
+
+    for (; tile < ntiles; tile += gridDim.x) {
+        const int row0 = tile * BM;
+        f32x4 acc[RM][CN];
+#pragma unroll
+        for (int i = 0; i < RM; ++i)
+#pragma unroll
+            for (int j = 0; j < CN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (tile != (int)blockIdx.x) __syncthreads();        // the previous tile's epilogue is done with the image that shares A's place
+        for (int c = 0; c < nchunks; ++c) {
+            commit(tile);
+            __syncthreads();
+            if (c == 0 && tile == (int)blockIdx.x) dpp_stamp(ga.prof, 2);
+            // the next chunk -- of this tile, or the first one of the workgroup's next tile (past the last tile: the clamped rows, unused)
+            if (c + 1 < nchunks) fetch((c + 1) * BKT);
+            else { set_rows(tile + (int)gridDim.x); fetch(0); }
+            DPP_SCHED_FENCE();
+            gemm_walk_products<BM, BN, WM, BKT, BKC, PB>(acc, As, Bs + c * SZB, wm, wn, l15, kq);
+            __syncthreads();
+        }
+        if (tile == (int)blockIdx.x) dpp_stamp(ga.prof, 3);
+        const int nvalid = (M - row0 < BM) ? (M - row0) : BM;
+        dpp_epilogue_wide<RM, CN, WM, WN, BM, BN, 1, ST>(acc, smem, col0, N, wco, d.residual, d.C, d.epi, nvalid, wm, wn, l15, kq, [&](int rl) {
+            const int row = row0 + rl;
+            return row < M ? (long)dpp_map_row(d.mapC, row) * d.ldc : -1L;
+        }, 0, d.store, tile, ntiles);
+    }
     dpp_stamp(ga.prof, 4);
 }
 
@@ -1374,11 +1606,123 @@ int launch_layout(const GemmArgs& ga, hipStream_t st) {
 }
 
 
+// ---- gemm_walk_kernel: which launches take it, and with which grid ----------------------------------------------------------------------
+// What the kernel assumes of a problem (see its header) -- none of it depends on the batch size: a batch of 8 and a batch of 128 of the same
+// layer get the same kernel family and tile, and the walk only ever changes the grid.
+static bool walk_eligible(const dpp_gemm_desc& d, const GemmArgs& ga, int bn) {
+    if (d.variant != 0 || d.splitk != 1 || !ga.wide || !d.a_kc || !d.C) return false;
+    if ((d.actA.mode & ~3) || d.actB.mode != 0 || (!d.b_kc && d.mapB.s != 1)) return false;       // not the two-tensor (LAZY) operand
+    if (d.actA.mode != 0 && (d.actA.cmod & 3)) return false;
+    if (!ga.vecA || !ga.vecB || d.K > 128 || d.K % ga.bk || d.N % bn) return false;
+    return true;
+}
+
+static constexpr size_t walk_lds_bytes(int bm, int bn, int bk, bool bkc, int K) {
+    const int sza = bm * (bk + 4), sze = bm * (bn + 4) + 16 * bn, szb = bkc ? bn * (bk + 4) : bk * (bn + 4);
+    return sizeof(float) * (size_t)((sza > sze ? sza : sze) + (K / bk) * szb);
+}
+
+// Workgroups of kernel `kern` that the device holds at once with `lds` bytes of dynamic LDS each: CUs x what the occupancy calculator gives
+// for the kernel's registers and LDS.  0: not known (no device) -- the launch then does not walk.  (The callers keep the answer.)
+static int walk_resident(void (*kern)(GemmArgs), size_t lds, size_t lds_static) {
+#ifdef DPP_HIP_EMU
+    // the emulator has no device: an MI355X's 256 CUs, workgroups per CU as the 160 KB of LDS allow (at most 4)
+    const int per_cu = (int)(160 * 1024 / (lds + lds_static));
+    return 256 * (per_cu > 4 ? 4 : per_cu);
+#else
+    int dev = 0, cus = 0, per_cu = 0;
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, DPP_THREADS, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return cus * per_cu;
+#endif
+}
+
+// Row-tile workgroups of a walking launch, 0: one workgroup per tile.  A launch walks when its one-tile grid is MORE than gemm_kernel holds at
+// once (`resident_tile`: the one-round launches of the 128 x 128 step measured 0.3 - 1.5 us SLOWER walking) and the walking form fits no fewer
+// workgroups on a CU than gemm_kernel does (the 128 x 16 tile is allocated 140 registers walking against 124: three per CU instead of four,
+// and its 4 096-tile launch of the 256 x 256 net went from 34.6 to 37.0 us); its grid is then what gemm_walk_kernel holds at once (`resident_walk`), shared among the column tiles -- and as few workgroups as still finish
+// in the same number of rounds (1 024 tiles on 768 places: 512 workgroups of two tiles each, not 256 of two beside 512 of one).
+// DPP_GEMM_WALK (read per call: the tests switch it) = 0: never walk; N > 0: N workgroups per column tile wherever there are more row tiles.
+static int walk_grid_x(int ntiles, int ncol, int resident_tile, int resident_walk) {
+    const char* e = getenv("DPP_GEMM_WALK");
+    int cap = resident_walk / ncol;
+    if (e) {
+        const int v = atoi(e);
+        if (v <= 0) return 0;
+        cap = v;
+    } else if (resident_tile <= 0 || (long)ntiles * ncol <= resident_tile || resident_walk < resident_tile) return 0;
+    if (cap < 1 || ntiles <= cap) return 0;
+    const int rounds = (ntiles + cap - 1) / cap;
+    return (ntiles + rounds - 1) / rounds;
+}
+
+// One instantiation of the walk: says with which grid (gx x gy workgroups) the problem walks and, with launch = true, launches it
+// (*status = the launch status).  Returns 1 when the problem walks, 0 when it keeps gemm_kernel's one-tile grid.
+template <int BM, int BN, int WM, int BK, bool BKC, bool ST, bool PB>
+static int walk_launch(const GemmArgs& ga, hipStream_t st, bool launch, int* gx, int* gy, int* status) {
+    const dpp_gemm_desc& d = ga.d;
+    const auto walk = &gemm_walk_kernel<BM, BN, WM, BK, BKC, ST, PB>;
+    const auto tile = &gemm_kernel<BM, BN, WM, BK, true, BKC, 1, false, true, ST, PB>;      // what launch_layout runs the problem on
+    const int nchunks = d.K / BK, ntiles = dpp_cdiv(d.M, BM), ncol = d.N / BN;
+    const size_t lds = walk_lds_bytes(BM, BN, BK, BKC, d.K);
+    if (nchunks < 1 || nchunks > 8 || lds > 160 * 1024) return 0;
+    // what the device holds of the two kernels: asked once per instantiation (and chunk count: the walk's LDS grows with K) and kept
+    static int resident_tile = -1, resident_walk[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
+    if (resident_tile < 0) resident_tile = walk_resident(tile, 0, walk_lds_bytes(BM, BN, BK, BKC, BK));
+    if (resident_walk[nchunks] < 0) resident_walk[nchunks] = walk_resident(walk, lds, 0);
+    const int wx = walk_grid_x(ntiles, ncol, resident_tile, resident_walk[nchunks]);
+    if (wx <= 0) return 0;
+    *gx = wx;
+    *gy = ncol;
+    if (launch) {
+        if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(walk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        DPP_LAUNCH(walk, dim3(wx, ncol), dim3(DPP_THREADS), lds, st, ga);
+        *status = dpp_launch_status();
+    }
+    return 1;
+}
+
+template <int BM, int BN, int WM, bool ST, bool PB>
+static int walk_layout(const GemmArgs& ga, hipStream_t st, bool launch, int* gx, int* gy, int* status) {
+    const dpp_gemm_desc& d = ga.d;
+    if (!walk_eligible(d, ga, BN)) return 0;
+    if (ga.bk == 64) return d.b_kc ? walk_launch<BM, BN, WM, 64, true, ST, PB>(ga, st, launch, gx, gy, status) : walk_launch<BM, BN, WM, 64, false, ST, PB>(ga, st, launch, gx, gy, status);
+    if (ga.bk == 32) return d.b_kc ? walk_launch<BM, BN, WM, 32, true, ST, PB>(ga, st, launch, gx, gy, status) : walk_launch<BM, BN, WM, 32, false, ST, PB>(ga, st, launch, gx, gy, status);
+    if constexpr (!PB) {
+        if (ga.bk == 16) return d.b_kc ? walk_launch<BM, BN, WM, 16, true, ST, false>(ga, st, launch, gx, gy, status) : walk_launch<BM, BN, WM, 16, false, ST, false>(ga, st, launch, gx, gy, status);
+    }
+    return 0;
+}
+
+// the tiles of variant 0 that have a walking form (four waves along M; the short tiles of the FC layers never have more row tiles than fit)
+template <bool ST, bool PB>
+static int gemm_walk(const GemmArgs& ga, int bm, int bn, int wm, hipStream_t st, bool launch, int* gx, int* gy, int* status) {
+#define DPP_WTILE(BM_, BN_) if (bm == BM_ && bn == BN_ && wm == 4) return walk_layout<BM_, BN_, 4, ST, PB>(ga, st, launch, gx, gy, status);
+    DPP_WTILE(128, 32)
+    DPP_WTILE(128, 16)
+    DPP_WTILE(64, 64)
+    DPP_WTILE(64, 32)
+    DPP_WTILE(64, 16)
+#undef DPP_WTILE
+    return 0;
+}
+
 // variants 3 / 2 / 1 / 0 of dpp_gemm for a prepared problem.  ST = false: every tensor float32 (gemm.hip); ST = true: some operand /
 // output is bf16-stored (gemm_st.hip, its own translation unit: the two sets of instantiations compile side by side)
+// walk_grid != nullptr: launch nothing, only report the grid gemm_walk_kernel would run the problem on ({0, 0}: it would not walk)
 template <bool ST, bool PB = false>
-int gemm_dispatch(GemmArgs& ga, int bm, int bn, int wm, hipStream_t st) {
+int gemm_dispatch(GemmArgs& ga, int bm, int bn, int wm, hipStream_t st, int* walk_grid = nullptr) {
     dpp_gemm_desc& d = ga.d;
+    if (walk_grid != nullptr) {
+        int status = DPP_OK;
+        walk_grid[0] = walk_grid[1] = 0;
+        (void)gemm_walk<ST, PB>(ga, bm, bn, wm, st, false, &walk_grid[0], &walk_grid[1], &status);
+        return DPP_OK;
+    }
     if (d.variant == 3) {
         const int rows = stream16_rows(d, ga);
         if (!rows) return DPP_E_UNSUPPORTED;
@@ -1427,6 +1771,10 @@ int gemm_dispatch(GemmArgs& ga, int bm, int bn, int wm, hipStream_t st) {
         DPP_RS(1, 1) DPP_RS(1, 2) DPP_RS(1, 4) DPP_RS(2, 1) DPP_RS(2, 2) DPP_RS(2, 4)
 #undef DPP_RS
         return DPP_E_UNSUPPORTED;
+    }
+    {   // more row tiles than are resident at once: the same tile, walking (gemm_walk_kernel)
+        int gx = 0, gy = 0, status = DPP_OK;
+        if (gemm_walk<ST, PB>(ga, bm, bn, wm, st, true, &gx, &gy, &status)) return status;
     }
 #define DPP_TILE(BM_, BN_, WM_) if (bm == BM_ && bn == BN_ && wm == WM_) return launch_layout<BM_, BN_, WM_, ST, PB>(ga, st);
     DPP_TILE(128, 64, 4)

@@ -3,4 +3,4 @@
 // storage flags are tested at run time there), so ONE set of instantiations serves the bf16 mode.
 #include "gemm_kernels.h"
 
-int dpp_gemm_dispatch_pb(GemmArgs& ga, int bm, int bn, int wm, hipStream_t st) { return gemm_dispatch<true, true>(ga, bm, bn, wm, st); }
+int dpp_gemm_dispatch_pb(GemmArgs& ga, int bm, int bn, int wm, hipStream_t st, int* walk_grid) { return gemm_dispatch<true, true>(ga, bm, bn, wm, st, walk_grid); }

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(os.path.dirname(_HERE), 'lib', 'libdpp_hip.so')
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 ST_A, ST_B, ST_C, ST_BNX = 1, 2, 4, 8      # DPP_ST_*: which pointers of a call address bf16-stored activation tensors
 c_float_p = C.c_void_p      # device pointers travel as integers
 stream_t = C.c_void_p
@@ -73,6 +73,7 @@ SIGNATURES = {
     'dpp_abi_version': (C.c_int, []),
     'dpp_gemm': (C.c_int, [C.POINTER(GemmDesc), stream_t]),
     'dpp_gemm_variant_rows': (C.c_int, [C.POINTER(GemmDesc)]),
+    'dpp_gemm_walk_grid': (C.c_int, [C.POINTER(GemmDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'dpp_fc_gemm': (C.c_int, [C.POINTER(GemmDesc), C.c_int, C.c_int, stream_t]),
     'dpp_reduce_partials': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, stream_t]),
     'dpp_conv3x3': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Act), C.c_void_p, C.c_int,

@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 17
+#define DPP_ABI_VERSION 18
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -152,6 +152,14 @@ int dpp_gemm(const dpp_gemm_desc* d, dpp_stream_t stream);
  * the problem with variant 0 and a generic tile instead (dpp_gemm itself returns DPP_E_UNSUPPORTED rather than change the partial
  * layout behind the caller's back).  Launches nothing. */
 int dpp_gemm_variant_rows(const dpp_gemm_desc* d);
+/* ABI v18.  A variant-0 launch of more row tiles than the device holds at once runs on the WALKING form of the LDS-tiled kernel: as many
+ * workgroups as are resident (hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs, shared among the column tiles), each staging its K x bn
+ * panel of B once and taking row tiles b, b + gx, ...; same tile, same arithmetic, bit-identical results, statistics partials indexed by
+ * the tile.  Taken for splitk == 1, a K-contiguous A with a mode 0-3 prologue, a plain B, K <= 128 in whole chunks, whole column tiles and
+ * the 16-byte epilogue; everything else keeps one workgroup per tile.  Environment DPP_GEMM_WALK (read per call): 0 = never walk, N = at most
+ * N workgroups per column tile.  This query returns 1 and the grid (gx row-walking workgroups x gy column tiles) when dpp_gemm would run `d`
+ * that way, 0 (and gx = gy = 0) when it would not.  Host only: launches nothing. */
+int dpp_gemm_walk_grid(const dpp_gemm_desc* d, int* gx, int* gy);
 
 /* Filter gradient of a 1x1 ConvLayer as a barrier-free row stream (csrc/wgrad.hip):
  *   partial[s][o][c] = sum over the pixel rows m of slice s of  dY[m][o] * act(X)[mapX(m)][c]
