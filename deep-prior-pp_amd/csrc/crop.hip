@@ -6,6 +6,7 @@
 //                           RealtimeHandposePipeline; ABI v13)
 //   several tracks          the *_ix entry points of the five tracking launches: T tracks over C frames (ABI v16)
 //   several hands           refine_com_iterative_ix: several centres of one frame refined in one launch (ABI v17)
+//   unlike sources          the *_src entry points: every frame source with its own camera and frame size (ABI v19)
 // They share CropRec, crop_geometry and crop_window_value; each section below names the reference lines it restates.  The training-time
 // augmentation of finished crops is augment.hip; finding the hand in a whole frame (connected components) is components.hip; the
 // camera, bounds and warp-coordinate arithmetic and the workgroup reductions these units share are geom.h.
@@ -310,12 +311,12 @@ __device__ __forceinline__ float bilinear_nd(const Src& src, int sw, int sh, int
 // src (null: row b reads frame b): the frame of row b, see "several tracks" below.
 __device__ __forceinline__ void crop_warp_body(const float* __restrict__ frames, int H, int W, const CropRec* __restrict__ rec, int dsz, int flags,
                                                float nd_value, float fill_value, float pad_value, const int* __restrict__ src,
-                                               float* __restrict__ out) {
+                                               const SourceRec* __restrict__ tab, float* __restrict__ out) {
     const int b = blockIdx.y;
     const int p = blockIdx.x * DPP_THREADS + threadIdx.x;
     if (p >= dsz * dsz) return;
     const CropRec r = rec[b];
-    const float* f = frames + (size_t)track_source(src, b) * H * W;
+    const float* f = source_frame(frames, tab, track_source(src, b), H, W);
     const int y = p / dsz, xo = p - y * dsz;
     const int x = (flags & CW_FLIP_X) ? dsz - 1 - xo : xo;      // crop[:, ::-1]: output column xo holds column dsz - 1 - xo
     float v = fill_value;
@@ -339,16 +340,16 @@ __device__ __forceinline__ void crop_warp_body(const float* __restrict__ frames,
 // compile-time constants apart from the normalise bit, so the bilinear, flip and no-range branches of the body are compiled out.
 __global__ __launch_bounds__(DPP_THREADS) void crop_warp_kernel(const float* __restrict__ frames, int H, int W, const CropRec* __restrict__ rec,
                                                                 int dsz, int normalize, float nd_value, const int* __restrict__ src,
-                                                                float* __restrict__ out) {
-    crop_warp_body(frames, H, W, rec, dsz, normalize ? CW_NORMALIZE : 0, nd_value, nd_value, 0.0f, src, out);
+                                                                const SourceRec* __restrict__ tab, float* __restrict__ out) {
+    crop_warp_body(frames, H, W, rec, dsz, normalize ? CW_NORMALIZE : 0, nd_value, nd_value, 0.0f, src, tab, out);
 }
 
 __global__ __launch_bounds__(DPP_THREADS) void crop_warp_ex_kernel(const float* __restrict__ frames, int H, int W, const CropRec* __restrict__ rec,
                                                                    int dsz, int flags, float nd_value, float fill_value, float pad_value,
                                                                    const int* __restrict__ src, const int* __restrict__ tflags,
-                                                                   float* __restrict__ out) {
+                                                                   const SourceRec* __restrict__ tab, float* __restrict__ out) {
     if (tflags && (tflags[blockIdx.y] & POSE_HAND_RIGHT)) flags |= CW_FLIP_X;      // the row's own hand side
-    crop_warp_body(frames, H, W, rec, dsz, flags, nd_value, fill_value, pad_value, src, out);
+    crop_warp_body(frames, H, W, rec, dsz, flags, nd_value, fill_value, pad_value, src, tab, out);
 }
 
 // resizeCrop on B same-size crops: cv2 2.4 resizeNN (source index min(floor(x * ifx), sw - 1)) or bilinearResize
@@ -433,10 +434,11 @@ __global__ __launch_bounds__(DPP_THREADS) void inverse_crop_kernel(const float* 
 // chain of dependent launches, so what counts is their number and that none of them walks the frame with a single workgroup.
 // min / max of frame b over FR_BANDS workgroups -> partial[b][band][2].  Interleaved 16-byte loads, four in flight per thread; a
 // lane past the end re-reads its first element (harmless for min / max).  Every band writes its partial, also an empty one.
-__global__ __launch_bounds__(DPP_THREADS) void frame_range_kernel(const float* __restrict__ frames, int H, int W, float* __restrict__ partial) {
+__global__ __launch_bounds__(DPP_THREADS) void frame_range_kernel(const float* __restrict__ frames, int H, int W,
+                                                                  const SourceRec* __restrict__ tab, float* __restrict__ partial) {
     __shared__ float s_mn[DPP_THREADS / DPP_WAVE], s_mx[DPP_THREADS / DPP_WAVE];
     const int b = blockIdx.y, band = blockIdx.x, tid = threadIdx.x;
-    const float* f = frames + (size_t)b * H * W;
+    const float* f = source_frame(frames, tab, b, H, W);                // with a table: source b's own frame and size
     const int npx = H * W;
     const int t = band * DPP_THREADS + tid, nt = FR_BANDS * DPP_THREADS;
     float mn = 3.4e38f, mx = -3.4e38f;
@@ -486,11 +488,13 @@ __device__ __forceinline__ void crop_empty_record(float min_depth, float max_dep
 __global__ __launch_bounds__(DPP_WAVE) void crop_prepare_ranged_kernel(const float* __restrict__ partial, const float* __restrict__ com,
                                                                        const float* __restrict__ cube, double fx, double fy, int dsz, int stretch,
                                                                        const int* __restrict__ src, const int* __restrict__ gate,
-                                                                       CropRec* __restrict__ rec, float* __restrict__ M_out) {
-    const int b = blockIdx.x;
+                                                                       const SourceRec* __restrict__ tab, CropRec* __restrict__ rec,
+                                                                       float* __restrict__ M_out) {
+    const int b = blockIdx.x, sc = track_source(src, b);
     float mn, mx;
-    frame_range_reduce(partial, track_source(src, b), threadIdx.x, mn, mx);
+    frame_range_reduce(partial, sc, threadIdx.x, mn, mx);
     if (threadIdx.x != 0) return;
+    if (tab) { fx = tab[sc].crop_fx; fy = tab[sc].crop_fy; }             // the source's own HandDetector focal lengths
     CropRec r;
     const float c[3] = {com[b * 3], com[b * 3 + 1], com[b * 3 + 2]};
     float* M = M_out ? M_out + (size_t)b * 9 : nullptr;
@@ -510,15 +514,20 @@ __global__ __launch_bounds__(DPP_WAVE) void track_refine_kernel(const float* __r
                                                                 const float* com_in, const float* __restrict__ cube,
                                                                 const float* __restrict__ net_out, AugCam cam, double fx, double fy, int dsz,
                                                                 const int* __restrict__ src, const int* __restrict__ gate,
-                                                                float* com_out, float* __restrict__ com3d_out, CropRec* rec_out,
+                                                                const SourceRec* __restrict__ tab, float* com_out,
+                                                                float* __restrict__ com3d_out, CropRec* rec_out,
                                                                 float* __restrict__ M_out, int* __restrict__ status) {
     const int b = blockIdx.x;
     if (threadIdx.x != 0) return;
+    const int c = track_source(src, b);
+    const float* frame = source_frame(frames, tab, c, H, W);
+    source_camera(tab, c, cam);
+    if (tab) { fx = tab[c].crop_fx; fy = tab[c].crop_fy; }
     const CropRec r0 = rec_in[b];
     const bool idle = track_gated(gate, b);
     const float c1[3] = {com_in[b * 3], com_in[b * 3 + 1], com_in[b * 3 + 2]};
     float c2[3] = {c1[0], c1[1], c1[2]};                                     // a gated track keeps its centre
-    if (!idle) refined_centre(cam, com_in + b * 3, net_out + b * 3, cube + b * 3, frames + (size_t)track_source(src, b) * H * W, H, W, r0, c2);
+    if (!idle) refined_centre(cam, com_in + b * 3, net_out + b * 3, cube + b * 3, frame, H, W, r0, c2);
     const bool lost = !idle && (com_ill_defined(c2) || com_ill_defined(c1));  // (a frame queued behind a lost one stays lost)
     if (!idle || com_out != com_in) { for (int d = 0; d < 3; ++d) com_out[b * 3 + d] = c2[d]; }
     status[b] = idle ? TRACK_IDLE : lost ? TRACK_LOST : TRACK_OK;
@@ -540,11 +549,13 @@ __global__ __launch_bounds__(DPP_WAVE) void track_refine_kernel(const float* __r
 // negated), bit 1 config['invX'] (column 1, as the reference has it), bit 2 config['invY'] (column 0).  One thread per joint.
 __global__ __launch_bounds__(DPP_THREADS) void pose_finish_kernel(const float* __restrict__ net_out, int B, int J, const float* __restrict__ cube,
                                                                   const float* __restrict__ com3d, AugCam cam, int flags,
-                                                                  const int* __restrict__ tflags, float* __restrict__ pose3d,
+                                                                  const int* __restrict__ tflags, const int* __restrict__ src,
+                                                                  const SourceRec* __restrict__ tab, float* __restrict__ pose3d,
                                                                   float* __restrict__ pose_img) {
     const int i = blockIdx.x * DPP_THREADS + threadIdx.x;
     if (i >= B * J) return;
     const int b = i / J;
+    source_camera(tab, track_source(src, b), cam);                     // the row's own camera (a workgroup may span rows)
     if (tflags) flags = tflags[b];                                     // the row's own sign rules
     float p[3] = {net_out[(size_t)i * 3], net_out[(size_t)i * 3 + 1], net_out[(size_t)i * 3 + 2]};
     if (flags & POSE_INV_X) p[1] = -p[1];
@@ -639,13 +650,19 @@ extern "C" int dpp_crop_prepare(const float* frames, int B, int H, int W, const 
     return dpp_launch_status();
 }
 
-extern "C" int dpp_crop_warp(const float* frames, const void* records, int B, int H, int W, int dsz, int normalize, float nd_value,
-                             float* out, dpp_stream_t stream) {
-    if (!frames || !records || !out || B < 1 || H < 1 || W < 1 || dsz < 1) return DPP_E_BADARG;
+// tab (null: the launch's H, W hold for every row): the table of the *_src entry points, which pass no frame size of their own
+static int launch_crop_warp(const float* frames, const void* records, int B, int H, int W, int dsz, int normalize, float nd_value,
+                            const int* src, const SourceRec* tab, float* out, dpp_stream_t stream) {
+    if (!frames || !records || !out || B < 1 || (!tab && (H < 1 || W < 1)) || dsz < 1) return DPP_E_BADARG;
     dim3 grid(dpp_cdiv(dsz * dsz, DPP_THREADS), B);
     DPP_LAUNCH(crop_warp_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
-                       static_cast<const CropRec*>(records), dsz, normalize, nd_value, static_cast<const int*>(nullptr), out);
+                       static_cast<const CropRec*>(records), dsz, normalize, nd_value, src, tab, out);
     return dpp_launch_status();
+}
+
+extern "C" int dpp_crop_warp(const float* frames, const void* records, int B, int H, int W, int dsz, int normalize, float nd_value,
+                             float* out, dpp_stream_t stream) {
+    return launch_crop_warp(frames, records, B, H, W, dsz, normalize, nd_value, nullptr, nullptr, out, stream);
 }
 
 extern "C" size_t dpp_crop_com_workspace_bytes(int B) { return (size_t)(B > 0 ? B : 0) * COM_BANDS * 4 * sizeof(double); }
@@ -678,17 +695,18 @@ extern "C" int dpp_crop_refine(const float* frames, const void* records, int B, 
 }
 
 static int launch_crop_warp_ex(const float* frames, const void* records, int B, int H, int W, int dsz, int flags, float nd_value,
-                               float fill_value, float pad_value, const int* src, const int* tflags, float* out, dpp_stream_t stream) {
+                               float fill_value, float pad_value, const int* src, const int* tflags, const SourceRec* tab, float* out,
+                               dpp_stream_t stream) {
     dim3 grid(dpp_cdiv(dsz * dsz, DPP_THREADS), B);
     DPP_LAUNCH(crop_warp_ex_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
-               static_cast<const CropRec*>(records), dsz, flags, nd_value, fill_value, pad_value, src, tflags, out);
+               static_cast<const CropRec*>(records), dsz, flags, nd_value, fill_value, pad_value, src, tflags, tab, out);
     return dpp_launch_status();
 }
 
 extern "C" int dpp_crop_warp_ex(const float* frames, const void* records, int B, int H, int W, int dsz, int flags, float nd_value,
                                 float fill_value, float pad_value, float* out, dpp_stream_t stream) {
     if (!frames || !records || !out || B < 1 || H < 1 || W < 1 || dsz < 1 || (flags & ~31)) return DPP_E_BADARG;
-    return launch_crop_warp_ex(frames, records, B, H, W, dsz, flags, nd_value, fill_value, pad_value, nullptr, nullptr, out, stream);
+    return launch_crop_warp_ex(frames, records, B, H, W, dsz, flags, nd_value, fill_value, pad_value, nullptr, nullptr, nullptr, out, stream);
 }
 
 extern "C" int dpp_resize_crops(const float* src, int B, int sh, int sw, int dh, int dw, int bilinear, float nd_value, float* out,
@@ -727,34 +745,36 @@ extern "C" size_t dpp_frame_range_bytes(int B) { return (size_t)(B > 0 ? B : 0) 
 
 extern "C" int dpp_frame_range(const float* frames, int B, int H, int W, float* partial, dpp_stream_t stream) {
     if (!frames || !partial || B < 1 || H < 1 || W < 1) return DPP_E_BADARG;
-    DPP_LAUNCH(frame_range_kernel, dim3(FR_BANDS, B), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W, partial);
+    DPP_LAUNCH(frame_range_kernel, dim3(FR_BANDS, B), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
+               static_cast<const SourceRec*>(nullptr), partial);
     return dpp_launch_status();
 }
 
 static int launch_crop_prepare_ranged(const float* partial, int B, const float* com, const float* cube, double fx, double fy, int dsz,
-                                      int stretch, const int* src, const int* gate, void* records, float* M_out, dpp_stream_t stream) {
-    if (!partial || !com || !cube || !records || B < 1 || dsz < 1 || fx == 0.0 || fy == 0.0) return DPP_E_BADARG;
+                                      int stretch, const int* src, const int* gate, const SourceRec* tab, void* records, float* M_out,
+                                      dpp_stream_t stream) {
+    if (!partial || !com || !cube || !records || B < 1 || dsz < 1 || (!tab && (fx == 0.0 || fy == 0.0))) return DPP_E_BADARG;
     DPP_LAUNCH(crop_prepare_ranged_kernel, dim3(B), dim3(DPP_WAVE), 0, static_cast<hipStream_t>(stream), partial, com, cube, fabs(fx), fabs(fy),
-               dsz, stretch, src, gate, static_cast<CropRec*>(records), M_out);
+               dsz, stretch, src, gate, tab, static_cast<CropRec*>(records), M_out);
     return dpp_launch_status();
 }
 
 extern "C" int dpp_crop_prepare_ranged(const float* partial, int B, const float* com, const float* cube, double fx, double fy, int dsz,
                                        int stretch, void* records, float* M_out, dpp_stream_t stream) {
-    return launch_crop_prepare_ranged(partial, B, com, cube, fx, fy, dsz, stretch, nullptr, nullptr, records, M_out, stream);
+    return launch_crop_prepare_ranged(partial, B, com, cube, fx, fy, dsz, stretch, nullptr, nullptr, nullptr, records, M_out, stream);
 }
 
 static int launch_track_refine(const float* frames, const void* records_in, int B, int H, int W, const float* com_in, const float* cube,
                                const float* net_out, double fx, double fy, double ux, double uy, int flip_y, double crop_fx, double crop_fy,
-                               int dsz, const int* src, const int* gate, float* com_out, float* com3d_out, void* records_out, float* M_out,
-                               int* status, dpp_stream_t stream) {
-    if (!frames || !records_in || !com_in || !cube || !net_out || !com_out || !com3d_out || !records_out || !status || B < 1 || H < 1 ||
-        W < 1 || dsz < 1 || fx == 0.0 || fy == 0.0 || crop_fx == 0.0 || crop_fy == 0.0)
+                               int dsz, const int* src, const int* gate, const SourceRec* tab, float* com_out, float* com3d_out,
+                               void* records_out, float* M_out, int* status, dpp_stream_t stream) {
+    if (!frames || !records_in || !com_in || !cube || !net_out || !com_out || !com3d_out || !records_out || !status || B < 1 || dsz < 1)
         return DPP_E_BADARG;
+    if (!tab && (H < 1 || W < 1 || fx == 0.0 || fy == 0.0 || crop_fx == 0.0 || crop_fy == 0.0)) return DPP_E_BADARG;
     AugCam cam;
     cam.fx = fx; cam.fy = fy; cam.ux = ux; cam.uy = uy; cam.flip_y = flip_y;
     DPP_LAUNCH(track_refine_kernel, dim3(B), dim3(DPP_WAVE), 0, static_cast<hipStream_t>(stream), frames, H, W,
-               static_cast<const CropRec*>(records_in), com_in, cube, net_out, cam, fabs(crop_fx), fabs(crop_fy), dsz, src, gate, com_out,
+               static_cast<const CropRec*>(records_in), com_in, cube, net_out, cam, fabs(crop_fx), fabs(crop_fy), dsz, src, gate, tab, com_out,
                com3d_out, static_cast<CropRec*>(records_out), M_out, status);
     return dpp_launch_status();
 }
@@ -764,22 +784,24 @@ extern "C" int dpp_track_refine(const float* frames, const void* records_in, int
                                 int dsz, float* com_out, float* com3d_out, void* records_out, float* M_out, int* status,
                                 dpp_stream_t stream) {
     return launch_track_refine(frames, records_in, B, H, W, com_in, cube, net_out, fx, fy, ux, uy, flip_y, crop_fx, crop_fy, dsz, nullptr,
-                               nullptr, com_out, com3d_out, records_out, M_out, status, stream);
+                               nullptr, nullptr, com_out, com3d_out, records_out, M_out, status, stream);
 }
 
 static int launch_pose_finish(const float* net_out, int B, int J, const float* cube, const float* com3d, double fx, double fy, double ux,
-                              double uy, int flip_y, int flags, const int* tflags, float* pose3d, float* pose_img, dpp_stream_t stream) {
-    if (!net_out || !cube || !com3d || !pose3d || !pose_img || B < 1 || J < 1 || fx == 0.0 || fy == 0.0 || (flags & ~7)) return DPP_E_BADARG;
+                              double uy, int flip_y, int flags, const int* tflags, const int* src, const SourceRec* tab, float* pose3d, float* pose_img,
+                              dpp_stream_t stream) {
+    if (!net_out || !cube || !com3d || !pose3d || !pose_img || B < 1 || J < 1 || (!tab && (fx == 0.0 || fy == 0.0)) || (flags & ~7))
+        return DPP_E_BADARG;
     AugCam cam;
     cam.fx = fx; cam.fy = fy; cam.ux = ux; cam.uy = uy; cam.flip_y = flip_y;
     DPP_LAUNCH(pose_finish_kernel, dim3(dpp_cdiv(B * J, DPP_THREADS)), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), net_out, B, J,
-               cube, com3d, cam, flags, tflags, pose3d, pose_img);
+               cube, com3d, cam, flags, tflags, src, tab, pose3d, pose_img);
     return dpp_launch_status();
 }
 
 extern "C" int dpp_pose_finish(const float* net_out, int B, int J, const float* cube, const float* com3d, double fx, double fy, double ux,
                                double uy, int flip_y, int flags, float* pose3d, float* pose_img, dpp_stream_t stream) {
-    return launch_pose_finish(net_out, B, J, cube, com3d, fx, fy, ux, uy, flip_y, flags, nullptr, pose3d, pose_img, stream);
+    return launch_pose_finish(net_out, B, J, cube, com3d, fx, fy, ux, uy, flip_y, flags, nullptr, nullptr, nullptr, pose3d, pose_img, stream);
 }
 
 static int launch_refine_com_iterative(const float* frames, const float* partial, int B, const int* src, int H, int W, const float* com_in,
@@ -809,16 +831,13 @@ extern "C" int dpp_refine_com_iterative_ix(const float* frames, const float* par
 extern "C" int dpp_crop_prepare_ranged_ix(const float* partial, int T, const int* src, const int* gate, const float* com, const float* cube,
                                           double fx, double fy, int dsz, int stretch, void* records, float* M_out, dpp_stream_t stream) {
     if (!src || !gate) return DPP_E_BADARG;
-    return launch_crop_prepare_ranged(partial, T, com, cube, fx, fy, dsz, stretch, src, gate, records, M_out, stream);
+    return launch_crop_prepare_ranged(partial, T, com, cube, fx, fy, dsz, stretch, src, gate, nullptr, records, M_out, stream);
 }
 
 extern "C" int dpp_crop_warp_ix(const float* frames, const void* records, int T, const int* src, int H, int W, int dsz, int normalize,
                                 float nd_value, float* out, dpp_stream_t stream) {
-    if (!frames || !records || !src || !out || T < 1 || H < 1 || W < 1 || dsz < 1) return DPP_E_BADARG;
-    dim3 grid(dpp_cdiv(dsz * dsz, DPP_THREADS), T);
-    DPP_LAUNCH(crop_warp_kernel, grid, dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, H, W,
-               static_cast<const CropRec*>(records), dsz, normalize, nd_value, src, out);
-    return dpp_launch_status();
+    if (!src) return DPP_E_BADARG;
+    return launch_crop_warp(frames, records, T, H, W, dsz, normalize, nd_value, src, nullptr, out, stream);
 }
 
 extern "C" int dpp_track_refine_ix(const float* frames, const void* records_in, int T, const int* src, const int* gate, int H, int W,
@@ -827,17 +846,64 @@ extern "C" int dpp_track_refine_ix(const float* frames, const void* records_in, 
                                    float* M_out, int* status, dpp_stream_t stream) {
     if (!src || !gate) return DPP_E_BADARG;
     return launch_track_refine(frames, records_in, T, H, W, com_in, cube, net_out, fx, fy, ux, uy, flip_y, crop_fx, crop_fy, dsz, src, gate,
-                               com_out, com3d_out, records_out, M_out, status, stream);
+                               nullptr, com_out, com3d_out, records_out, M_out, status, stream);
 }
 
 extern "C" int dpp_crop_warp_ex_ix(const float* frames, const void* records, int T, const int* src, const int* tflags, int H, int W, int dsz,
                                    int flags, float nd_value, float fill_value, float pad_value, float* out, dpp_stream_t stream) {
     if (!frames || !records || !src || !tflags || !out || T < 1 || H < 1 || W < 1 || dsz < 1 || (flags & ~15)) return DPP_E_BADARG;
-    return launch_crop_warp_ex(frames, records, T, H, W, dsz, flags, nd_value, fill_value, pad_value, src, tflags, out, stream);
+    return launch_crop_warp_ex(frames, records, T, H, W, dsz, flags, nd_value, fill_value, pad_value, src, tflags, nullptr, out, stream);
 }
 
 extern "C" int dpp_pose_finish_ix(const float* net_out, int T, int J, const int* tflags, const float* cube, const float* com3d, double fx,
                                   double fy, double ux, double uy, int flip_y, float* pose3d, float* pose_img, dpp_stream_t stream) {
     if (!tflags) return DPP_E_BADARG;
-    return launch_pose_finish(net_out, T, J, cube, com3d, fx, fy, ux, uy, flip_y, 0, tflags, pose3d, pose_img, stream);
+    return launch_pose_finish(net_out, T, J, cube, com3d, fx, fy, ux, uy, flip_y, 0, tflags, nullptr, nullptr, pose3d, pose_img, stream);
+}
+
+// ---- frame sources of unlike cameras and sizes (ABI v19): the launches that read a frame or a camera, with the per-source table -----
+// `sources`: C SourceRec on the device (geom.h), validated by the host; row t reads record src[t].  The same kernels as above: the
+// table pointer replaces the launch's (H, W) and camera scalars, which are not passed here.
+extern "C" size_t dpp_source_record_bytes(void) { return sizeof(SourceRec); }
+
+extern "C" int dpp_frame_range_src(const float* frames, const void* sources, int C, float* partial, dpp_stream_t stream) {
+    if (!frames || !sources || !partial || C < 1 || C > 65535) return DPP_E_BADARG;
+    DPP_LAUNCH(frame_range_kernel, dim3(FR_BANDS, C), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), frames, 0, 0,
+               static_cast<const SourceRec*>(sources), partial);
+    return dpp_launch_status();
+}
+
+extern "C" int dpp_crop_prepare_ranged_src(const float* partial, int T, const int* src, const int* gate, const void* sources, const float* com,
+                                           const float* cube, int dsz, int stretch, void* records, float* M_out, dpp_stream_t stream) {
+    if (!src || !gate || !sources) return DPP_E_BADARG;
+    return launch_crop_prepare_ranged(partial, T, com, cube, 0.0, 0.0, dsz, stretch, src, gate, static_cast<const SourceRec*>(sources), records,
+                                      M_out, stream);
+}
+
+extern "C" int dpp_crop_warp_src(const float* frames, const void* records, int T, const int* src, const void* sources, int dsz, int normalize,
+                                 float nd_value, float* out, dpp_stream_t stream) {
+    if (!src || !sources) return DPP_E_BADARG;
+    return launch_crop_warp(frames, records, T, 0, 0, dsz, normalize, nd_value, src, static_cast<const SourceRec*>(sources), out, stream);
+}
+
+extern "C" int dpp_track_refine_src(const float* frames, const void* records_in, int T, const int* src, const int* gate, const void* sources,
+                                    const float* com_in, const float* cube, const float* net_out, int dsz, float* com_out, float* com3d_out,
+                                    void* records_out, float* M_out, int* status, dpp_stream_t stream) {
+    if (!src || !gate || !sources) return DPP_E_BADARG;
+    return launch_track_refine(frames, records_in, T, 0, 0, com_in, cube, net_out, 0.0, 0.0, 0.0, 0.0, 0, 0.0, 0.0, dsz, src, gate,
+                               static_cast<const SourceRec*>(sources), com_out, com3d_out, records_out, M_out, status, stream);
+}
+
+extern "C" int dpp_crop_warp_ex_src(const float* frames, const void* records, int T, const int* src, const int* tflags, const void* sources,
+                                    int dsz, int flags, float nd_value, float fill_value, float pad_value, float* out, dpp_stream_t stream) {
+    if (!frames || !records || !src || !tflags || !sources || !out || T < 1 || dsz < 1 || (flags & ~15)) return DPP_E_BADARG;
+    return launch_crop_warp_ex(frames, records, T, 0, 0, dsz, flags, nd_value, fill_value, pad_value, src, tflags,
+                               static_cast<const SourceRec*>(sources), out, stream);
+}
+
+extern "C" int dpp_pose_finish_src(const float* net_out, int T, int J, const int* src, const int* tflags, const void* sources, const float* cube,
+                                   const float* com3d, float* pose3d, float* pose_img, dpp_stream_t stream) {
+    if (!src || !tflags || !sources) return DPP_E_BADARG;
+    return launch_pose_finish(net_out, T, J, cube, com3d, 0.0, 0.0, 0.0, 0.0, 0, 0, tflags, src, static_cast<const SourceRec*>(sources), pose3d,
+                              pose_img, stream);
 }

@@ -151,4 +151,28 @@ __device__ __forceinline__ void frame_range_reduce(const float* __restrict__ par
     for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
 }
 
+// ---- frame sources of unlike cameras and sizes (ABI v19) --------------------------------------------------------------------------
+// One record per frame source: its camera, what HandDetector is handed (crop_fx, crop_fy: already absolute), its frame size and where
+// its frame starts in the ragged float32 frame buffer and in the ragged raw sensor buffer (ELEMENT offsets, padded by the host to 16
+// bytes).  The kernels that read a frame or a camera take a pointer to the table: null in the plain and *_ix entry points, where the
+// scalars of the launch hold for every row as before.  The host has validated the table; the kernels trust it.
+struct SourceRec {
+    double fx, fy, ux, uy;
+    double crop_fx, crop_fy;
+    long long frame_off, raw_off;
+    int H, W, flip_y, pad_;
+};
+
+// Source c's float32 frame and its size: from the table, or frame c of equal [H][W] frames.  c is uniform over a workgroup.
+__device__ __forceinline__ const float* source_frame(const float* __restrict__ frames, const SourceRec* __restrict__ tab, int c, int& H, int& W) {
+    if (tab == nullptr) return frames + (size_t)c * H * W;
+    H = tab[c].H; W = tab[c].W;
+    return frames + tab[c].frame_off;
+}
+
+__device__ __forceinline__ void source_camera(const SourceRec* __restrict__ tab, int c, AugCam& cam) {
+    if (tab == nullptr) return;
+    cam.fx = tab[c].fx; cam.fy = tab[c].fy; cam.ux = tab[c].ux; cam.uy = tab[c].uy; cam.flip_y = tab[c].flip_y;
+}
+
 }  // namespace

@@ -20,6 +20,10 @@
 // compare-and-select exchanges only (no fminf / fmaxf: nothing hangs on the denormal mode).  A band taller or a frame wider than the
 // LDS tile is walked in row chunks / column tiles, whose halos are read again.  Without the median there is nothing to stage: one
 // group per thread straight from memory.  Source type and flags are template parameters.
+//
+// Sources of unlike sizes (ABI v19, dpp_frame_ingest_src): the same kernel with the per-source table of geom.h -- workgroup (band, c)
+// takes H, W and the element offsets of source c's frame in the ragged raw and float32 buffers from record c; the table pointer is
+// null in dpp_frame_ingest, where the launch's H, W hold for all B frames.  The tile is static and sized from the run-time W either way.
 #include "geom.h"
 
 namespace {
@@ -85,14 +89,16 @@ __device__ __forceinline__ void ig_emit(float* __restrict__ orow, int W, int c0,
 }
 
 template <class T, bool MED, bool MIR>
-__global__ __launch_bounds__(DPP_THREADS) void frame_ingest_kernel(const T* __restrict__ raw, int H, int W, float* __restrict__ frames,
-                                                                   float* __restrict__ partial) {
+__global__ __launch_bounds__(DPP_THREADS) void frame_ingest_kernel(const T* __restrict__ raw, int H, int W, const SourceRec* __restrict__ tab,
+                                                                   float* __restrict__ frames, float* __restrict__ partial) {
     typedef typename IgType<T>::reg R;
     constexpr int V = IgType<T>::V;
     __shared__ float s_mn[DPP_THREADS / DPP_WAVE], s_mx[DPP_THREADS / DPP_WAVE];
     const int b = blockIdx.y, band = blockIdx.x, tid = threadIdx.x;
-    const T* src = raw + (size_t)b * H * W;
-    float* dst = frames + (size_t)b * H * W;
+    // tab (null: B equal [H][W] frames): source b's own size and where its frame starts in the ragged raw and float32 buffers
+    if (tab) { H = tab[b].H; W = tab[b].W; }
+    const T* src = raw + (tab ? (size_t)tab[b].raw_off : (size_t)b * H * W);
+    float* dst = frames + (tab ? (size_t)tab[b].frame_off : (size_t)b * H * W);
     const int rows = (H + FR_BANDS - 1) / FR_BANDS;
     const int y0 = band * rows < H ? band * rows : H, y1 = y0 + rows < H ? y0 + rows : H;     // an empty band: y0 == y1
     float mn = 3.4e38f, mx = -3.4e38f;
@@ -189,14 +195,14 @@ __global__ __launch_bounds__(DPP_THREADS) void frame_ingest_kernel(const T* __re
 }
 
 template <class T>
-int ingest_launch(const void* raw, int B, int H, int W, int flags, float* frames, float* partial, hipStream_t st) {
+int ingest_launch(const void* raw, int B, int H, int W, const SourceRec* tab, int flags, float* frames, float* partial, hipStream_t st) {
     const T* r = static_cast<const T*>(raw);
     const dim3 grid(FR_BANDS, B), block(DPP_THREADS);
     switch (flags) {
-    case 0: DPP_LAUNCH((frame_ingest_kernel<T, false, false>), grid, block, 0, st, r, H, W, frames, partial); break;
-    case DPP_INGEST_MEDIAN3: DPP_LAUNCH((frame_ingest_kernel<T, true, false>), grid, block, 0, st, r, H, W, frames, partial); break;
-    case DPP_INGEST_MIRROR_X: DPP_LAUNCH((frame_ingest_kernel<T, false, true>), grid, block, 0, st, r, H, W, frames, partial); break;
-    default: DPP_LAUNCH((frame_ingest_kernel<T, true, true>), grid, block, 0, st, r, H, W, frames, partial); break;
+    case 0: DPP_LAUNCH((frame_ingest_kernel<T, false, false>), grid, block, 0, st, r, H, W, tab, frames, partial); break;
+    case DPP_INGEST_MEDIAN3: DPP_LAUNCH((frame_ingest_kernel<T, true, false>), grid, block, 0, st, r, H, W, tab, frames, partial); break;
+    case DPP_INGEST_MIRROR_X: DPP_LAUNCH((frame_ingest_kernel<T, false, true>), grid, block, 0, st, r, H, W, tab, frames, partial); break;
+    default: DPP_LAUNCH((frame_ingest_kernel<T, true, true>), grid, block, 0, st, r, H, W, tab, frames, partial); break;
     }
     return dpp_launch_status();
 }
@@ -212,6 +218,19 @@ extern "C" int dpp_frame_ingest(const void* raw, int src_type, int B, int H, int
     const uintptr_t f0 = reinterpret_cast<uintptr_t>(frames), f1 = f0 + npx * 4;
     if (a0 < f1 && f0 < a1) return DPP_E_BADARG;                       // every output pixel reads neighbours other workgroups write
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (src_type == DPP_INGEST_U16) return ingest_launch<uint16_t>(raw, B, H, W, flags, frames, partial, st);
-    return ingest_launch<float>(raw, B, H, W, flags, frames, partial, st);
+    if (src_type == DPP_INGEST_U16) return ingest_launch<uint16_t>(raw, B, H, W, nullptr, flags, frames, partial, st);
+    return ingest_launch<float>(raw, B, H, W, nullptr, flags, frames, partial, st);
+}
+
+// C sources of unlike sizes (ABI v19): source c is sources[c].H x sources[c].W, read at element sources[c].raw_off of `raw` and stored at
+// element sources[c].frame_off of `frames`; band b of source c covers ceil(H_c / FR_BANDS) rows of that source.  The host has validated
+// the table (sizes, offsets in range and 16-byte aligned, the two buffers apart); only what needs no device memory is checked here.
+extern "C" int dpp_frame_ingest_src(const void* raw, int src_type, const void* sources, int C, int flags, float* frames, float* partial,
+                                    dpp_stream_t stream) {
+    if (!raw || !frames || !sources || raw == static_cast<const void*>(frames) || C < 1 || C > 65535) return DPP_E_BADARG;
+    if ((src_type != DPP_INGEST_U16 && src_type != DPP_INGEST_F32) || (flags & ~(DPP_INGEST_MEDIAN3 | DPP_INGEST_MIRROR_X))) return DPP_E_BADARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const SourceRec* tab = static_cast<const SourceRec*>(sources);
+    if (src_type == DPP_INGEST_U16) return ingest_launch<uint16_t>(raw, C, 0, 0, tab, flags, frames, partial, st);
+    return ingest_launch<float>(raw, C, 0, 0, tab, flags, frames, partial, st);
 }

@@ -23,9 +23,22 @@ GATING.  A track sits a tick out (gate 0) when it is lost, was never started, or
 through the nets (on an all-zero crop), its centre's bits stay as they are, and it is reported IDLE -- or LOST, when that is why it
 was gated.  A lost track does not stop the others; it stays gated until reset(t, com) or a successful acquire(t, frame).
 
-One importer (camera) serves all sources: the camera is a launch argument.  Per-source intrinsics are out of scope here, and so is
-the overlapped process_sequence form for several sources (DESIGN.md names both as follow-ups).  acquire_source(c, frame) finds ALL
-hands of a source in one detector plan and starts the source's tracks from them.
+SOURCES.  With one importer and one (H, W) every source is the same camera: the camera and the frame size are launch arguments, the
+frames one [C][H][W] buffer, the launches the *_ix ones above.  `importer`, `H`, `W`, `fx`, `fy` may instead be sequences with one
+entry per source (a scalar anywhere: the same for all sources).  Where the entries differ -- a 640 x 480 camera beside a 320 x 240
+one, or one model with per-unit calibration -- the tracker builds a per-source table on the device (ops.SourceTable: camera,
+HandDetector's fx / fy, frame size, frame offsets), keeps the frames in ONE ragged buffer (every frame padded to 16 bytes) and
+builds the same plan through the *_src siblings of the launches that read a frame or a camera (ABI v19): the same kernels with the
+table in place of the scalars, the same launch count.  All entries equal is the homogeneous path, untouched.  The sensor options
+(dtype / median / mirror) stay common to all sources; extrinsics or any fusion across cameras are out of scope.
+
+acquire_source(c, frame) finds ALL hands of a source in one detector plan and starts the source's tracks from them; the detectors
+are built per source, at that source's size and focal lengths, on views of its frame slice.
+
+SEQUENCES.  process_sequence(ticks) is HandTracker.process_sequence for several sources: two sets of input buffers, the uploads of
+tick n + 1 on the copy stream under the plan of tick n, the result block of tick n read while tick n + 1 is in flight.  The host
+therefore learns one tick late that a track was lost: the track runs ungated for one more tick (track_refine reports it LOST there:
+a frame queued behind a lost one stays lost) and is gated from the tick after.  Nothing is detected inside a sequence.
 """
 import numpy as np
 
@@ -38,17 +51,18 @@ class MultiTracker(object):
     def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, tracks, sources=None, invX=False, invY=False, fx=None, fy=None,
                  sensor=None):
         """
-        :param importer:   the dataset importer: ONE camera for all sources (per-source intrinsics are out of scope)
+        :param importer:   the dataset importer (the camera) of all sources, or a sequence of C importers, one per source
         :param poseNet, comrefNet: as for HandTracker, but built for a batch of len(tracks): row t is track t
-        :param H, W:       frame size, the same for all sources
+        :param H, W:       frame size of all sources, or sequences of C ints
         :param cube:       metric cube (mm) every track starts with (set_cube(t, cube) changes one)
         :param tracks:     list of (source, hand_right): track t follows one hand in the frames of source `source`
         :param sources:    number of frame sources C (default: the largest source named, plus one); C <= T, every track reads one source
         :param invX, invY: estimatePose's mirroring, for all tracks
-        :param fx, fy:     what the reference hands to HandDetector; default: the importer's
+        :param fx, fy:     what the reference hands to HandDetector (a value for all sources or a sequence of C; None entries
+                           and the default: the source's importer's)
         :param sensor:     as for HandTracker, for ALL sources: frames are raw sensor frames and frame_ingest runs at B = C
         """
-        self.rt, self.H, self.W = rt, int(H), int(W)
+        self.rt = rt
         tracks = [(int(s), bool(r)) for s, r in tracks]
         if not tracks:
             raise ValueError("MultiTracker needs at least one track")
@@ -57,10 +71,20 @@ class MultiTracker(object):
         self.src_host = ops.track_index([s for s, _ in tracks], C)           # the kernels trust it: checked here
         if C > T:
             raise ValueError("%d sources for %d tracks: every source needs a track that reads it" % (C, T))
-        self.importer = importer
-        self.cam = camera_tuple(importer)
-        self.fx = abs(float(importer.fx if fx is None else fx))
-        self.fy = abs(float(importer.fy if fy is None else fy))
+        importers = self._per_source(importer, C, 'importer')
+        Hs, Ws = self._per_source(H, C, 'H'), self._per_source(W, C, 'W')
+        if any(int(h) != h or int(w) != w or h < 1 or w < 1 for h, w in zip(Hs, Ws)):
+            raise ValueError("frame sizes must be positive integers: H %r, W %r" % (Hs, Ws))
+        self.sizes = [(int(h), int(w)) for h, w in zip(Hs, Ws)]
+        self.importers, self.cams = importers, [camera_tuple(di) for di in importers]
+        self.fxs = [abs(float(di.fx if f is None else f)) for di, f in zip(importers, self._per_source(fx, C, 'fx'))]
+        self.fys = [abs(float(di.fy if f is None else f)) for di, f in zip(importers, self._per_source(fy, C, 'fy'))]
+        if any(v == 0. or not np.isfinite(v) for cam in self.cams for v in cam[:2]) or any(v == 0. or not np.isfinite(v) for v in self.fxs + self.fys):
+            raise ValueError("a source needs focal lengths other than zero: cameras %r, fx %r, fy %r" % (self.cams, self.fxs, self.fys))
+        # all entries equal: the homogeneous path -- the camera and the frame size as launch arguments, no table
+        self.hetero = len(set(zip(self.sizes, self.cams, self.fxs, self.fys))) > 1
+        self.importer, self.cam, self.fx, self.fy = importers[0], self.cams[0], self.fxs[0], self.fys[0]
+        self.H, self.W = (None, None) if self.hetero else self.sizes[0]
         self.ceng = _engine(comrefNet, rt, 'comrefNet', T, "one row per track")
         self.peng = _engine(poseNet, rt, 'poseNet', T, "one row per track")
         if len(self.peng.x_ins) != 1 or self.peng.out_dim % 3:
@@ -68,10 +92,18 @@ class MultiTracker(object):
         self.rs, self.ds, self.J = int(self.ceng.x_ins[0].shape[1]), int(self.peng.x_in.shape[1]), self.peng.out_dim // 3
         f32, i32 = np.float32, np.int32
         J3 = self.J * 3
-        self.frames = rt.alloc((C, self.H, self.W), f32, zero=False)
         self.sensor = None if sensor is None else ops.sensor_spec(sensor)
-        self.raw = None if sensor is None else rt.alloc((C, self.H, self.W), self.sensor[0], zero=False)
+        if self.hetero:                                                            # ragged buffers; _slice(buf, c) is source c's frame
+            self.table = ops.SourceTable(rt, self.cams, list(zip(self.fxs, self.fys)), self.sizes,
+                                         None if sensor is None else self.sensor[0].itemsize)
+            self.frames = self._ragged(False)
+            self.raw = None if sensor is None else self._ragged(True)
+        else:
+            self.table = None
+            self.frames = rt.alloc((C, self.H, self.W), f32, zero=False)
+            self.raw = None if sensor is None else rt.alloc((C, self.H, self.W), self.sensor[0], zero=False)
         self.inputs = self.frames if sensor is None else self.raw                 # what the host uploads into
+        self._inputs2 = self._frames2 = self._gate2 = None                         # process_sequence's second set, made when first used
         self.partial = ops.frame_range_workspace(rt, C)
         self._pstride = self.partial.size // C
         self.rec = rt.alloc(T * rt.lib.dpp_crop_record_bytes(), np.uint8)
@@ -100,9 +132,34 @@ class MultiTracker(object):
         self.com_host = np.zeros((T, 3), f32)                                      # the centres as last downloaded (or reset)
         for t in range(T):
             self.set_cube(t, cube)
-        self._plan = None
+        self._plans = {}
         self._detectors = {}
         self.runs = 0
+
+    @staticmethod
+    def _per_source(v, C, what):
+        """A scalar means "the same for all sources"; a sequence has one entry per source."""
+        if isinstance(v, (list, tuple, np.ndarray)):
+            if len(v) != C:
+                raise ValueError("%d entries of %s for %d sources" % (len(v), what, C))
+            return list(v)
+        return [v] * C
+
+    def _ragged(self, raw, zero=False):
+        """A ragged buffer for one frame of every source: float32 frames, or (raw) frames of the sensor's type."""
+        if raw:
+            return self.rt.alloc((self.table.raw_elems,), self.sensor[0], zero=zero)
+        return self.rt.alloc((self.table.frame_elems,), np.float32, zero=zero)
+
+    def _slice(self, buf, c, raw=False):
+        """Source c's frame in a frame buffer as a (1, H, W) view (raw: the buffer is a raw sensor buffer, whose offsets differ)."""
+        H, W = self.sizes[c]
+        if not self.hetero:
+            return buf.view(c * H * W, (1, H, W))
+        return buf.view(int(self.table.host['raw_off' if raw else 'frame_off'][c]), (1, H, W))
+
+    def _input(self, c, slot=0):
+        return self._slice(self.inputs if slot == 0 else self._inputs2, c, raw=self.sensor is not None)
 
     # ---- device state -----------------------------------------------------------------------------------------------------
     def _track(self, t):
@@ -141,13 +198,14 @@ class MultiTracker(object):
         t = self._track(t)
         if t not in self._detectors:
             from .detect import FrameDetector
-            c, px = int(self.src_host[t]), self.H * self.W
+            c = int(self.src_host[t])
+            (H, W) = self.sizes[c]
             self._detectors[t] = FrameDetector(
-                self.rt, self.H, self.W, self.fx, self.fy, 1, frames=self.frames.view(c * px, (1, self.H, self.W)),
+                self.rt, H, W, self.fxs[c], self.fys[c], 1, frames=self._slice(self.frames, c),
                 partial=self.partial.view(c * self._pstride, (self._pstride,)), com=self.com.view(3 * t, (1, 3)),
                 cube=self.cube.view(3 * t, (1, 3)), res=self.res.view(self._off['det'], (8,)),
                 sensor=None if self.sensor is None else dict(zip(('dtype', 'median', 'mirror'), self.sensor)),
-                raw=None if self.sensor is None else self.raw.view(c * px, (1, self.H, self.W)))
+                raw=None if self.sensor is None else self._slice(self.raw, c, raw=True))
         return self._detectors[t]
 
     def acquire(self, t, frame, do_hand_size=False):
@@ -156,10 +214,10 @@ class MultiTracker(object):
         source it finds the same one for both tracks; acquire_source(c, frame) finds both and shares them out.  Returns
         dict(com, cube, found); not found: the centre is (0, 0, 0) and the track stays lost."""
         t = self._track(t)
-        frame = self._frame(frame)
-        det = self.detector(t)
         c = int(self.src_host[t])
-        self.inputs.view(c * self.H * self.W, (1, self.H, self.W)).set(frame)
+        frame = self._frame(frame, c)
+        det = self.detector(t)
+        self._input(c).set(frame)
         det.plan(do_hand_size).run(self.rt)
         self.rt.synchronize()
         res, o = self.res.get(), self._off
@@ -182,12 +240,12 @@ class MultiTracker(object):
             return self.detector(ts[0]), ts
         if key not in self._detectors:
             from .detect import FrameDetector
-            px = self.H * self.W
+            (H, W) = self.sizes[c]
             self._detectors[key] = FrameDetector(
-                self.rt, self.H, self.W, self.fx, self.fy, 1, frames=self.frames.view(c * px, (1, self.H, self.W)),
+                self.rt, H, W, self.fxs[c], self.fys[c], 1, frames=self._slice(self.frames, c),
                 partial=self.partial.view(c * self._pstride, (self._pstride,)), cube=self.cube.view(3 * ts[0], (1, 3)),
                 sensor=None if self.sensor is None else dict(zip(('dtype', 'median', 'mirror'), self.sensor)),
-                raw=None if self.sensor is None else self.raw.view(c * px, (1, self.H, self.W)), hands=len(ts), max_extent=max_extent)
+                raw=None if self.sensor is None else self._slice(self.raw, c, raw=True), hands=len(ts), max_extent=max_extent)
         return self._detectors[key], ts
 
     def acquire_source(self, c, frame, max_extent=None, order='near'):
@@ -202,16 +260,16 @@ class MultiTracker(object):
         Returns one dict(com, cube, found) per track of the source, in ascending t (a followed track: its own centre, found True)."""
         if order not in ('near', 'x'):
             raise ValueError("order is 'near' or 'x', not %r" % (order,))
-        frame = self._frame(frame)
         det, ts = self.source_detector(c, max_extent)
         c = int(c)
+        frame = self._frame(frame, c)
         if not det.multi:                                                     # one track, no extent filter: acquire's plan, acquire's bits
             t = ts[0]
             if self.lost[t]:
                 return [self.acquire(t, frame)]
-            self.inputs.view(c * self.H * self.W, (1, self.H, self.W)).set(frame)
+            self._input(c).set(frame)
             return [dict(com=self.com_host[t].copy(), cube=self.cube_host[t].copy(), found=True)]
-        self.inputs.view(c * self.H * self.W, (1, self.H, self.W)).set(frame)
+        self._input(c).set(frame)
         det.plan(False).run(self.rt)
         self.rt.synchronize()
         coms, _, found = det.parse(det.res.get(), None, self.cube_host[ts[0]])[:3]
@@ -241,35 +299,68 @@ class MultiTracker(object):
         return [out[t] for t in ts]
 
     # ---- the per-tick plan --------------------------------------------------------------------------------------------------
-    def plan(self):
-        if self._plan is None:
-            rt, H, W, T, C, fr = self.rt, self.H, self.W, self.T, self.C, self.frames
+    def _second_set(self):
+        """process_sequence's second set of input buffers (and of gates): made the first time a sequence runs, so a tracker that only
+        ever ticks allocates what it always did.  Zeroed: an idle source's slice is read by the depth-range pass before anything
+        was uploaded into it."""
+        if self._inputs2 is None:
+            if self.hetero:
+                self._inputs2 = self._ragged(self.sensor is not None, zero=True)
+            else:
+                self._inputs2 = self.rt.alloc((self.C, self.H, self.W), np.float32 if self.sensor is None else self.sensor[0])
+            self._gate2 = self.rt.alloc((self.T,), np.int32)
+            self._gate2_host = np.zeros(self.T, np.int32)
+
+    def plan(self, slot=0):
+        """The plan of one tick on input set `slot` (1: process_sequence's second set; without a sensor the second set IS a second
+        frame buffer, with one the raw frames alone are doubled: the float32 frames are written and read inside one plan)."""
+        if slot not in self._plans:
+            rt, H, W, T, C = self.rt, self.H, self.W, self.T, self.C
+            if slot:
+                self._second_set()
+            gate = self._gate2 if slot else self.gate
+            fr = self._inputs2 if slot and self.sensor is None else self.frames
+            raw = self._inputs2 if slot else self.raw
+            tab = self.table
             p = ops.Plan('multitrack')
             if self.sensor is None:
-                p.add(ops.frame_range(rt, fr, C, H, W, self.partial))
+                p.add(ops.frame_range(rt, fr, C, H, W, self.partial) if tab is None else ops.frame_range_src(rt, fr, tab, self.partial))
+            elif tab is None:
+                p.add(ops.frame_ingest(rt, raw, C, H, W, fr, self.partial, median=self.sensor[1], mirror=self.sensor[2]))
             else:
-                p.add(ops.frame_ingest(rt, self.raw, C, H, W, fr, self.partial, median=self.sensor[1], mirror=self.sensor[2]))
+                p.add(ops.frame_ingest_src(rt, raw, tab, fr, self.partial, median=self.sensor[1], mirror=self.sensor[2]))
             # the T centres are read (prepare, track_refine) and then rewritten by one lane per track of track_refine: in place
+            tracks = (T, self.src, gate) if tab is None else (T, self.src, gate, tab)
             for op, side in refine_stage(rt, fr, H, W, self.partial, self.rec, self.com, self.cube, self.ceng, self.cam, self.fx, self.fy,
-                                         self.ds, self.com, self.com3d, self.rec, self.status, self.M, tracks=(T, self.src, self.gate)):
+                                         self.ds, self.com, self.com3d, self.rec, self.status, self.M, tracks=tracks):
                 p.add(op, side)
-            p.add(ops.crop_warp_ex_ix(rt, fr, self.rec, T, self.src, self.tflags, H, W, self.ds, self.crop, flags=ops.CROP_NORMALIZE,
-                                      nd_value=0.0, name='track_crop'))
+            if tab is None:
+                p.add(ops.crop_warp_ex_ix(rt, fr, self.rec, T, self.src, self.tflags, H, W, self.ds, self.crop, flags=ops.CROP_NORMALIZE,
+                                          nd_value=0.0, name='track_crop'))
+            else:
+                p.add(ops.crop_warp_ex_src(rt, fr, self.rec, T, self.src, self.tflags, tab, self.ds, self.crop, flags=ops.CROP_NORMALIZE,
+                                           nd_value=0.0, name='track_crop'))
             for op, side in self.peng.fwd.ops:
                 p.add(op, side)
-            p.add(ops.pose_finish_ix(rt, self.peng.out.buf, T, self.J, self.tflags, self.cube, self.com3d, self.cam, self.pose3d, self.pose_img))
-            self._plan = p
-        return self._plan
+            if tab is None:
+                p.add(ops.pose_finish_ix(rt, self.peng.out.buf, T, self.J, self.tflags, self.cube, self.com3d, self.cam, self.pose3d,
+                                         self.pose_img))
+            else:
+                p.add(ops.pose_finish_src(rt, self.peng.out.buf, T, self.J, self.src, self.tflags, tab, self.cube, self.com3d, self.pose3d,
+                                          self.pose_img))
+            self._plans[slot] = p
+        return self._plans[slot]
 
-    def _frame(self, frame):
+    def _frame(self, frame, c=0):
+        """`frame` checked against the size of source c (ITS source) and the sensor's dtype."""
         if self.sensor is None:
             frame = np.asarray(frame, np.float32)
         else:                                       # a raw frame is taken as it is or not at all: no silent conversion
             frame = np.asarray(frame)
             if frame.dtype != self.sensor[0]:
                 raise ValueError("frame dtype %s, the tracker's sensor delivers %s" % (frame.dtype, self.sensor[0]))
-        if frame.shape != (self.H, self.W):
-            raise ValueError("frame shape %s, expected %s" % (frame.shape, (self.H, self.W)))
+        if frame.shape != self.sizes[c]:
+            raise ValueError("frame shape %s, source %d delivers %s" % (frame.shape, c, self.sizes[c]))
         return frame
 
     def _results(self, res, gate, crops=None):
@@ -300,12 +391,11 @@ class MultiTracker(object):
         com) / acquire(t, frame).  For IDLE and LOST the other entries are finite but meaningless."""
         if len(frames) != self.C:
             raise ValueError("%d frames for %d sources" % (len(frames), self.C))
-        fresh = [None if f is None else self._frame(f) for f in frames]
+        fresh = [None if f is None else self._frame(f, c) for c, f in enumerate(frames)]
         gate = np.array([int(not self.lost[t] and fresh[self.src_host[t]] is not None) for t in range(self.T)], np.int32)
-        px = self.H * self.W
         for c, f in enumerate(fresh):
             if f is not None:
-                self.inputs.view(c * px, (1, self.H, self.W)).set(f)
+                self._input(c).set(f)
         if not np.array_equal(gate, self.gate_host):
             self.gate.set(gate)
             self.gate_host = gate
@@ -313,3 +403,73 @@ class MultiTracker(object):
         self.runs += 1
         self.rt.synchronize()
         return self._results(self.res.get(), gate, self.crop.get() if return_crop else None)
+
+    def process_sequence(self, ticks, return_crops=False):
+        """A sequence of ticks (an iterable of per-source frame lists, None for "no frame", as process takes them): the uploads of
+        tick n + 1 run on the copy stream under the plan of tick n (two sets of input buffers, one plan and one `gate` array per
+        set, so a plan in flight never sees the next tick's frames or gates), and the result block of tick n is read while tick
+        n + 1 is in flight.  Returns one list of per-track dicts per tick, as a process() loop would.
+
+        The host learns one tick late that a track was lost in tick n: the track runs ungated in tick n + 1, where track_refine
+        reports it LOST again (its centre is ill-defined), and is gated from tick n + 2 on, as in process().  A lost track stops
+        neither the sequence nor the other tracks; nothing is detected inside a sequence.  For every track-tick whose status is OK
+        or IDLE every key has the bits of the process() loop; for LOST only the status is promised.  self.lost, com_host, gate_host
+        and runs are afterwards what the loop would have left (a lost track's centre is put back to the one it was lost with)."""
+        rt = self.rt
+        staged = hasattr(rt, 'staged_upload')
+        self._second_set()
+        results, pending, free = [], None, [None, None]
+        gates = [self.gate, self._gate2]
+        lost_com = {}                                   # track -> the centre it was lost with (the tick after overwrites it)
+
+        def resolve(p):
+            res, crops, gate = p
+            was = self.lost.copy()
+            out = self._results(res.get(), gate, crops.get() if crops is not None else None)
+            for t in range(self.T):
+                if self.lost[t] and not was[t]:
+                    lost_com[t] = out[t]['com'].copy()
+            results.append(out)
+        last = None
+        for n, frames in enumerate(ticks):
+            if len(frames) != self.C:
+                raise ValueError("%d frames for %d sources" % (len(frames), self.C))
+            fresh = [None if f is None else self._frame(f, c) for c, f in enumerate(frames)]
+            k = n & 1
+            # self.lost is what the host knows: the results up to tick n - 2
+            gate = np.array([int(not self.lost[t] and fresh[self.src_host[t]] is not None) for t in range(self.T)], np.int32)
+            events = []
+            for c, f in enumerate(fresh):
+                if f is not None:
+                    if staged:
+                        events.append(rt.staged_upload(self._input(c, k), f[None], free[k]))
+                    else:
+                        self._input(c, k).set(f)
+            if not np.array_equal(gate, self._gate2_host if k else self.gate_host):   # the set's own gates: its last plan is behind us
+                gates[k].set(gate)
+                if k:
+                    self._gate2_host = gate
+                else:
+                    self.gate_host = gate
+            for ev in events:
+                rt.wait_event(ev)
+            self.plan(k).run(rt)
+            self.runs += 1
+            free[k] = rt.record_event() if staged else None
+            handle = (rt.read_async(self.res), rt.read_async(self.crop) if return_crops else None, gate)
+            if pending is not None:
+                resolve(pending)
+            pending = handle
+            # the gates a process() loop would have used for this tick: it knows tick n - 1's losses already
+            last = np.array([int(not self.lost[t] and fresh[self.src_host[t]] is not None) for t in range(self.T)], np.int32)
+        if pending is not None:
+            resolve(pending)
+        rt.synchronize()
+        if last is not None and not np.array_equal(last, self.gate_host):      # process() reads set 0: leave it what the loop would have
+            self.gate.set(last)
+            self.gate_host = last
+        for t, com in lost_com.items():
+            if self.lost[t]:
+                self.com.view(3 * t, (1, 3)).set(com)
+                self.com_host[t] = com
+        return results

@@ -857,6 +857,108 @@ def pose_finish_ix(rt, net_out, T, J, tflags, cube, com3d, cam, pose3d, pose_img
                   (net_out, tflags, cube, com3d, pose3d, pose_img), name)
 
 
+# ---- frame sources of unlike cameras and frame sizes (include/dpp_hip.h, ABI v19) -------------------------------------------------------
+# One record per source; the ragged frame buffers hold source c's H x W elements from its offset on, every offset padded to 16 bytes.
+SOURCE_RECORD = np.dtype([('fx', np.float64), ('fy', np.float64), ('ux', np.float64), ('uy', np.float64), ('crop_fx', np.float64),
+                          ('crop_fy', np.float64), ('frame_off', np.int64), ('raw_off', np.int64), ('H', np.int32), ('W', np.int32),
+                          ('flip_y', np.int32), ('pad', np.int32)])
+
+
+class SourceTable(object):
+    """The per-source table of the *_src launches: `host` (a SOURCE_RECORD array, validated here -- the kernels trust it), `dev` (its
+    device copy), and the element counts of the ragged float32 frame buffer and of the raw sensor buffer that hold its frames."""
+
+    def __init__(self, rt, cams, crop_f, sizes, raw_itemsize=None):
+        """cams: C (fx, fy, ux, uy, flip_y); crop_f: C (crop_fx, crop_fy); sizes: C (H, W); raw_itemsize: bytes per element of the raw
+        sensor buffer (None: there is none, its offsets repeat the frame buffer's)."""
+        assert SOURCE_RECORD.itemsize == rt.lib.dpp_source_record_bytes(), (SOURCE_RECORD.itemsize, rt.lib.dpp_source_record_bytes())
+        C = len(sizes)
+        if C < 1 or len(cams) != C or len(crop_f) != C:
+            raise ValueError("one camera, one (fx, fy) and one (H, W) per source: %d, %d, %d" % (len(cams), len(crop_f), C))
+        tab = np.zeros(C, SOURCE_RECORD)
+        pad_f, pad_r = 4, 16 // int(raw_itemsize or 4)                 # elements per 16 bytes
+        off_f = off_r = 0
+        for c in range(C):
+            (fx, fy, ux, uy, flip), (cfx, cfy), (H, W) = cams[c], crop_f[c], sizes[c]
+            if int(H) != H or int(W) != W or H < 1 or W < 1:
+                raise ValueError("source %d: frame size %r x %r" % (c, H, W))
+            vals = [float(v) for v in (fx, fy, ux, uy, cfx, cfy)]
+            if not all(np.isfinite(vals)) or vals[0] == 0. or vals[1] == 0. or vals[4] == 0. or vals[5] == 0.:
+                raise ValueError("source %d: a camera needs finite values and focal lengths other than zero: %r" % (c, vals))
+            tab[c] = (vals[0], vals[1], vals[2], vals[3], abs(vals[4]), abs(vals[5]), off_f, off_r, int(H), int(W), int(bool(flip)), 0)
+            off_f += -(-int(H) * int(W) // pad_f) * pad_f
+            off_r += -(-int(H) * int(W) // pad_r) * pad_r
+        self.host, self.C, self.frame_elems, self.raw_elems, self.raw_pad = tab, C, off_f, off_r, pad_r
+        self.check()
+        self.npx = float(sum(int(r['H']) * int(r['W']) for r in tab))     # the sources' real sizes: what the launches' meta sums over
+        self.dev = rt.upload(tab.view(np.uint8))
+
+    def check(self):
+        """Offsets in range and 16-byte aligned, sizes positive, focal lengths not zero -- once, on the host."""
+        t = self.host
+        for c in range(self.C):
+            px = int(t['H'][c]) * int(t['W'][c])
+            ok = (t['H'][c] > 0 and t['W'][c] > 0 and t['frame_off'][c] >= 0 and t['raw_off'][c] >= 0 and
+                  t['frame_off'][c] + px <= self.frame_elems and t['raw_off'][c] + px <= self.raw_elems and
+                  t['frame_off'][c] % 4 == 0 and t['raw_off'][c] % self.raw_pad == 0 and
+                  all(t[k][c] != 0. for k in ('fx', 'fy', 'crop_fx', 'crop_fy')))
+            if not ok:
+                raise ValueError("source record %d is not valid: %r" % (c, t[c]))
+
+    def size(self, c):
+        return int(self.host['H'][c]), int(self.host['W'][c])
+
+
+def frame_range_src(rt, frames, table, partial, name='frame_range'):
+    return Launch(rt.lib.dpp_frame_range_src, (frames.ptr, table.dev.ptr, table.C, partial.ptr), (frames, table.dev, partial), name,
+                  dict(kernel='frame_range', flops=2.0 * table.npx, bytes=4.0 * table.npx))
+
+
+def frame_ingest_src(rt, raw, table, frames, partial, median=False, mirror=False, name='frame_ingest'):
+    if raw.dtype.name not in INGEST_TYPES:
+        raise ValueError("frame_ingest reads uint16 or float32 frames, not %s" % raw.dtype.name)
+    flags = (INGEST_MEDIAN3 if median else 0) | (INGEST_MIRROR_X if mirror else 0)
+    return Launch(rt.lib.dpp_frame_ingest_src, (raw.ptr, INGEST_TYPES[raw.dtype.name], table.dev.ptr, table.C, flags, frames.ptr, _p(partial)),
+                  (raw, table.dev, frames, partial), name,
+                  dict(kernel='frame_ingest', flops=(22.0 if median else 2.0) * table.npx, bytes=(raw.dtype.itemsize + 4.0) * table.npx))
+
+
+def crop_prepare_ranged_src(rt, partial, T, src, gate, table, com, cube, dsz, records, M_out=None, stretch=False, name='crop_prepare_ranged'):
+    return Launch(rt.lib.dpp_crop_prepare_ranged_src, (partial.ptr, T, src.ptr, gate.ptr, table.dev.ptr, com.ptr, cube.ptr, dsz,
+                                                       int(bool(stretch)), records.ptr, _p(M_out)),
+                  (partial, src, gate, table.dev, com, cube, records, M_out), name)
+
+
+def crop_warp_src(rt, frames, records, T, src, table, dsz, out, normalize=True, nd_value=0.0, name='crop_warp'):
+    return Launch(rt.lib.dpp_crop_warp_src, (frames.ptr, records.ptr, T, src.ptr, table.dev.ptr, dsz, int(bool(normalize)), float(nd_value),
+                                             out.ptr),
+                  (frames, records, src, table.dev, out), name, dict(kernel='crop_warp', flops=10.0 * T * dsz * dsz, bytes=8.0 * T * dsz * dsz))
+
+
+def track_refine_src(rt, frames, records_in, T, src, gate, table, com_in, cube, net_out, dsz, com_out, com3d_out, records_out, status,
+                     M_out=None, name='track_refine'):
+    return Launch(rt.lib.dpp_track_refine_src,
+                  (frames.ptr, records_in.ptr, T, src.ptr, gate.ptr, table.dev.ptr, com_in.ptr, cube.ptr, net_out.ptr, dsz, com_out.ptr,
+                   com3d_out.ptr, records_out.ptr, _p(M_out), status.ptr),
+                  (frames, records_in, src, gate, table.dev, com_in, cube, net_out, com_out, com3d_out, records_out, M_out, status), name)
+
+
+def crop_warp_ex_src(rt, frames, records, T, src, tflags, table, dsz, out, flags=0, nd_value=0.0, fill_value=None, pad_value=0.0,
+                     name='crop_warp_ex'):
+    fill = float(nd_value) if fill_value is None else float(fill_value)
+    taps = 4 if flags & CROP_BILINEAR else 1
+    return Launch(rt.lib.dpp_crop_warp_ex_src, (frames.ptr, records.ptr, T, src.ptr, tflags.ptr, table.dev.ptr, dsz, int(flags), float(nd_value),
+                                                fill, float(pad_value), out.ptr),
+                  (frames, records, src, tflags, table.dev, out), name,
+                  dict(kernel='crop_warp', flops=(30.0 if taps == 4 else 10.0) * T * dsz * dsz, bytes=(4.0 * taps + 4.0) * T * dsz * dsz))
+
+
+def pose_finish_src(rt, net_out, T, J, src, tflags, table, cube, com3d, pose3d, pose_img, name='pose_finish'):
+    return Launch(rt.lib.dpp_pose_finish_src, (net_out.ptr, T, J, src.ptr, tflags.ptr, table.dev.ptr, cube.ptr, com3d.ptr, pose3d.ptr,
+                                               pose_img.ptr),
+                  (net_out, src, tflags, table.dev, cube, com3d, pose3d, pose_img), name)
+
+
 def refine_com_iterative(rt, frames, partial, B, H, W, com_in, cube, fx, fy, num_iter, com_out, status, name='refine_com_iterative'):
     """dpp_refine_com_iterative: refineCoMIterative of B frames, all iterations in one launch."""
     return Launch(rt.lib.dpp_refine_com_iterative, (frames.ptr, partial.ptr, B, H, W, com_in.ptr, cube.ptr, float(fx), float(fy), int(num_iter),

@@ -67,7 +67,9 @@ def refine_stage(rt, frame, H, W, partial, rec, com_in, cube, ceng, cam, fx, fy,
     """The (op, side) list of HandDetector.track for ONE frame whose depth-range partials are in `partial`: window around com_in,
     the refinement net's inputs, its forward plan, track_refine.  Shared by HandTracker's plan and HandDetector.track -- and, with
     tracks = (T, src, gate) (int32 device arrays, one entry per track: hipdp/multitrack.py), by MultiTracker's plan: the same steps
-    for T tracks that each read frame src[t] of `frame` and its partials, through the indexed siblings of the three crop launches."""
+    for T tracks that each read frame src[t] of `frame` and its partials, through the indexed siblings of the three crop launches.
+    tracks = (T, src, gate, table) (table: an ops.SourceTable): the sources have cameras and frame sizes of their own, `frame` is the
+    ragged frame buffer, the *_src siblings read (H, W, cam, fx, fy) per source from the table and the arguments of that name are unused."""
     nin = len(ceng.x_ins)
     if nin not in (1, 3):
         raise NotImplementedError("Number of inputs is {}".format(nin))
@@ -79,6 +81,10 @@ def refine_stage(rt, frame, H, W, partial, rec, com_in, cube, ceng, cam, fx, fy,
     if tracks is None:
         out = [(ops.crop_prepare_ranged(rt, partial, 1, com_in, cube, fx, fy, rs, rec, None, stretch=True), False),
                (ops.crop_warp(rt, frame, rec, 1, H, W, rs, in0, normalize=True, nd_value=0.0, name='track_in0'), False)]
+    elif len(tracks) == 4:
+        _, src, gate, table = tracks
+        out = [(ops.crop_prepare_ranged_src(rt, partial, B, src, gate, table, com_in, cube, rs, rec, None, stretch=True), False),
+               (ops.crop_warp_src(rt, frame, rec, B, src, table, rs, in0, normalize=True, nd_value=0.0, name='track_in0'), False)]
     else:
         _, src, gate = tracks
         out = [(ops.crop_prepare_ranged_ix(rt, partial, B, src, gate, com_in, cube, fx, fy, rs, rec, None, stretch=True), False),
@@ -90,6 +96,9 @@ def refine_stage(rt, frame, H, W, partial, rec, com_in, cube, ceng, cam, fx, fy,
     if tracks is None:
         out.append((ops.track_refine(rt, frame, rec, 1, H, W, com_in, cube, ceng.out.buf, cam, fx, fy, dsz_final, com_out, com3d, rec_out,
                                      status, M_out=M), False))
+    elif len(tracks) == 4:
+        out.append((ops.track_refine_src(rt, frame, rec, B, src, gate, table, com_in, cube, ceng.out.buf, dsz_final, com_out, com3d, rec_out,
+                                         status, M_out=M), False))
     else:
         out.append((ops.track_refine_ix(rt, frame, rec, B, src, gate, H, W, com_in, cube, ceng.out.buf, cam, fx, fy, dsz_final, com_out,
                                         com3d, rec_out, status, M_out=M), False))

@@ -393,7 +393,9 @@ class MultiStreamPipeline(object):
     """Several cameras and hands through ONE device plan per tick (hipdp.multitrack.MultiTracker): the headless processVideo of
     RealtimeHandposePipeline for a list of CameraDevices.  `hands` names the tracks, one (device index, hand) each with hand
     HAND_LEFT / HAND_RIGHT: N cameras with one hand each, both hands of one camera, or a mixture.  Both nets are built for a batch
-    of len(hands).  All devices share the importer's camera and the frame size.
+    of len(hands).  The devices may be unlike cameras: `di` is one importer for all devices or a list with one per device, config['fx'] /
+    ['fy'] may be lists with one value per device, and every device may deliver frames of a size of its own (the tracker is built for
+    the devices' frame shapes as they are first seen; MultiTracker keeps unlike sources in one plan through a per-source table).
 
     Seeds: init_com= one centre per track (image coordinates of its device, z in mm; None for a track without one), and / or
     seed_detect=True: a track without a centre -- never seeded, or lost -- is searched for in its device's next frame by the
@@ -408,8 +410,8 @@ class MultiStreamPipeline(object):
                  max_extent=None):
         """
         :param poseNet, comrefNet: built nets or their parameters (as for RealtimeHandposePipeline), with batchSize == len(hands)
-        :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=])
-        :param di:        depth importer (the one camera of all devices)
+        :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=]); fx / fy: one value, or a list with one per device
+        :param di:        depth importer (the one camera of all devices), or a list with one importer per device
         :param devices:   list of CameraDevice
         :param hands:     list of (device index, HAND_LEFT | HAND_RIGHT), one per track
         :param init_com:  None, or one centre (or None) per track
@@ -418,9 +420,12 @@ class MultiStreamPipeline(object):
         :param max_extent: None, or the largest metric width / height (mm) of a component that seed_detect may take for a hand
         """
         self.max_extent = max_extent
-        self.poseNet, self.comrefNet, self.importer = poseNet, comrefNet, di
         self.config = copy.deepcopy(config)
         self.devices = list(devices)
+        self.importers = list(di) if isinstance(di, (list, tuple)) else [di] * len(self.devices)
+        if len(self.importers) != len(self.devices):
+            raise ValueError("%d importers for %d devices" % (len(self.importers), len(self.devices)))
+        self.poseNet, self.comrefNet, self.importer = poseNet, comrefNet, self.importers[0]
         self.hands = [(int(d), int(h)) for d, h in hands]
         if not self.hands or not self.devices:
             raise ValueError("MultiStreamPipeline needs at least one device and one track")
@@ -438,6 +443,7 @@ class MultiStreamPipeline(object):
         self.verbose = verbose
         self.stop = _Value(False)
         self._tracker = None
+        self._shapes = [None] * len(self.devices)                      # every device's frame shape, as first seen
         self._seeded = [False] * len(self.hands)
 
     def initNets(self):
@@ -446,24 +452,42 @@ class MultiStreamPipeline(object):
         one.initNets()
         self.poseNet, self.comrefNet = one.poseNet, one.comrefNet
 
-    def tracker(self, H, W):
+    def tracker(self, H, W=None):
+        """The tracker for the devices' frame shapes: H a list with one (H, W) per device, or (H, W) the one shape of all devices."""
         from hipdp.multitrack import MultiTracker
         from hipdp.runtime import default_runtime
-        if self._tracker is None or (self._tracker.H, self._tracker.W) != (H, W):
+        shapes = tuple((int(h), int(w)) for h, w in H) if W is None else ((int(H), int(W)),) * len(self.devices)
+        if self._tracker is None or self._tracker_key != shapes:
             cfg = self.config
-            self._tracker = MultiTracker(default_runtime(), self.importer, self.poseNet, self.comrefNet, H, W, cfg['cube'],
-                                         [(d, h == self.HAND_RIGHT) for d, h in self.hands], sources=len(self.devices),
+            same = len(set(shapes)) == 1 and all(di is self.importer for di in self.importers)
+            self._tracker = MultiTracker(default_runtime(), self.importer if same else self.importers, self.poseNet, self.comrefNet,
+                                         shapes[0][0] if same else [s[0] for s in shapes], shapes[0][1] if same else [s[1] for s in shapes],
+                                         cfg['cube'], [(d, h == self.HAND_RIGHT) for d, h in self.hands], sources=len(self.devices),
                                          invX=cfg.get('invX') is True, invY=cfg.get('invY') is True, fx=cfg['fx'], fy=cfg['fy'],
                                          sensor=self.sensor)
+            self._tracker_key = shapes
             self._seeded = [False] * len(self.hands)
         return self._tracker
+
+    def _tracker_for(self, frames):
+        """The tracker keyed by the tuple of the devices' frame shapes; a device that has not delivered yet counts with the shape of
+        the first device that has (devices of one kind are the common case)."""
+        for d, f in enumerate(frames):
+            if f is not None and self._shapes[d] is None:
+                self._shapes[d] = tuple(numpy.asarray(f).shape)
+        first = next(s for s in self._shapes if s is not None)
+        return self.tracker([first if s is None else s for s in self._shapes])
+
+    def _to_seed(self, mt, frames):
+        """The tracks that processFrames would seed before this tick (from init_com or by detection)."""
+        return [t for t, (d, _) in enumerate(self.hands) if mt.lost[t] and frames[d] is not None and
+                ((not self._seeded[t] and self.init_com[t] is not None) or self.seed_detect)]
 
     def processFrames(self, frames):
         """One tick: one frame (or None) per device -> one result dict per track (MultiTracker.process).  Tracks without a centre are
         seeded first: from init_com once, else (seed_detect) by detection in their device's frame -- one detector plan per device
         for all its lost tracks."""
-        shape = next(numpy.asarray(f).shape for f in frames if f is not None)
-        mt = self.tracker(*shape)
+        mt = self._tracker_for(frames)
         search = set()
         for t, (d, _) in enumerate(self.hands):
             if not mt.lost[t] or frames[d] is None:
@@ -477,39 +501,82 @@ class MultiStreamPipeline(object):
             mt.acquire_source(d, frames[d], max_extent=self.max_extent)
         return mt.process(frames)
 
-    def processVideos(self, max_frames=None):
+    def _read(self):
+        """One frame (or None) per device; None when a FileDevice has ended or no device delivered."""
+        frames = []
+        try:
+            for dev in self.devices:
+                ret, frame = dev.getDepth()
+                frames.append(frame if ret is not False else None)
+        except IndexError:
+            return None
+        if all(f is None for f in frames):
+            print("Error while reading frames.")
+            return None
+        return frames
+
+    def processVideos(self, max_frames=None, overlapped=False):
         """Every tick one frame of every device through one plan, until a FileDevice ends, max_frames ticks, `stop`, or -- without
         seed_detect -- every track is lost.  Returns one (ticks followed, J, 3) float32 array of poses in mm per track: a tick in
-        which a track is lost or idle is left out of that track's list."""
+        which a track is lost or idle is left out of that track's list.
+
+        overlapped=True: stretches of ticks in which no track needs a seed go through MultiTracker.process_sequence (the uploads of
+        the next tick under the plan of this one, the results read one tick late); a tick in which a track is to be seeded -- the
+        first one, or after the host has learnt that a track was lost, with seed_detect -- is an ordinary tick.  The poses of the
+        followed ticks are the same either way; frame_times then holds a stretch's mean for each of its ticks."""
         self.initNets()
         for dev in self.devices:
             dev.start()
         poses = [[] for _ in self.hands]
-        times, ticks = [], 0
-        while not self.stop.value and (max_frames is None or ticks < max_frames):
-            frames = []
-            try:
-                for dev in self.devices:
-                    ret, frame = dev.getDepth()
-                    frames.append(frame if ret is not False else None)
-            except IndexError:
-                break
-            if all(f is None for f in frames):
-                print("Error while reading frames.")
-                break
-            start = time.time()
-            res = self.processFrames(frames)
-            times.append(time.time() - start)
-            ticks += 1
+        times = []
+        state = dict(ticks=0, carry=None, ended=False)
+
+        def go_on():
+            return not self.stop.value and (max_frames is None or state['ticks'] < max_frames) and not state['ended']
+
+        def collect(res, tick):
             for t, r in enumerate(res):
                 if r['status'] == 0:
                     poses[t].append(r['pose'].copy())
                 elif r['status'] == 1:
-                    print("Track {} lost (or no hand) in tick {}.".format(t, ticks - 1))
+                    print("Track {} lost (or no hand) in tick {}.".format(t, tick))
+
+        def stretch(mt):
+            """The ticks handed to process_sequence: until the input ends or the host knows of a track to seed (that tick is carried
+            over to the tick loop)."""
+            while go_on():
+                if not self.seed_detect and all(mt.lost):
+                    return
+                frames = self._read()
+                if frames is None:
+                    state['ended'] = True
+                    return
+                if self._to_seed(mt, frames) or self._tracker_for(frames) is not mt:
+                    state['carry'] = frames
+                    return
+                state['ticks'] += 1
+                yield frames
+        while go_on():
+            frames, state['carry'] = (state['carry'], None) if state['carry'] is not None else (self._read(), None)
+            if frames is None:
+                break
+            start = time.time()
+            res = self.processFrames(frames)
+            times.append(time.time() - start)
+            collect(res, state['ticks'])
+            state['ticks'] += 1
             if not self.seed_detect and all(self._tracker.lost):
                 break
             if self.verbose is True:
                 print("{}ms tick".format(times[-1] * 1000.))
+            if overlapped and go_on():
+                first, start = state['ticks'], time.time()
+                out = self._tracker.process_sequence(stretch(self._tracker))
+                for i, res in enumerate(out):
+                    collect(res, first + i)
+                times.extend([(time.time() - start) / max(1, len(out))] * len(out))
+                if not self.seed_detect and all(self._tracker.lost):
+                    break
         for dev in self.devices:
             dev.stop()
         self.frame_times = times

@@ -12,6 +12,11 @@ annotation is used at all: both tracks of the first camera are started by ONE de
 the second track then stays lost).  Prints the time per tick and, where the annotations match the pose net's joints, the mean joint error
 of every left-hand track.  Checkpoints are optional: without them the nets have random weights (a dry run of the machinery).
 
+--half-res-second plays the second sequence at half resolution (every second row and column) through an importer whose fx, fy, ux, uy
+are halved: the same scene through a different camera, in the same plan as the full-resolution first camera (MultiTracker's
+per-source table).  The second camera's 3-D poses must then land near those of the all-full-resolution run, which is made as well;
+the mean difference is printed -- a sanity figure, not a bar.  --overlapped runs the ticks through MultiTracker.process_sequence.
+
     python examples/realtime_multi.py --dataset icvl --data ../data/ICVL/ --seqs test_seq_1 test_seq_2
 """
 import argparse
@@ -23,7 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, 'deep-prior-pp_amd'))
 
 import numpy  # noqa: E402
 
-from data.importers import ICVLImporter, MSRA15Importer, NYUImporter  # noqa: E402
+from data.importers import DepthImporter, ICVLImporter, MSRA15Importer, NYUImporter  # noqa: E402
 from net.poseregnet import PoseRegNetParams  # noqa: E402
 from net.resnet import ResNetParams  # noqa: E402
 from net.scalenet import ScaleNetParams  # noqa: E402
@@ -34,6 +39,21 @@ from util.realtimehandposepipeline import MultiStreamPipeline  # noqa: E402
 DATASETS = {'icvl': (ICVLImporter, ('test_seq_1', 'test_seq_2'), {'fx': 241.42, 'fy': 241.42, 'cube': (250, 250, 250)}),
             'nyu': (NYUImporter, ('test_1', 'test_2'), {'fx': 588., 'fy': 587., 'cube': (300, 300, 300)}),
             'msra': (MSRA15Importer, ('P0', 'P1'), {'fx': 241.42, 'fy': 241.42, 'cube': (200, 200, 200)})}
+
+
+class HalfResFileDevice(FileDevice):
+    """A FileDevice that delivers every second row and column of its frames: the camera whose fx, fy, ux, uy are half the recorded one's."""
+
+    def getDepth(self):
+        ret, frame = super(HalfResFileDevice, self).getDepth()
+        return ret, numpy.ascontiguousarray(frame[::2, ::2])
+
+
+def half_res_importer(di):
+    from hipdp.augmenter import camera_tuple
+    half = DepthImporter(di.fx / 2., di.fy / 2., di.ux / 2., di.uy / 2.)
+    half.flip_y = camera_tuple(di)[4]
+    return half
 
 
 def main(argv=None):
@@ -49,6 +69,8 @@ def main(argv=None):
                     help="first centres: the annotations, detection where a camera has one track, or detection for every track")
     ap.add_argument('--max-extent', type=float, default=None, help='with detection: the largest width / height (mm) of a hand candidate')
     ap.add_argument('--max-frames', type=int, default=None)
+    ap.add_argument('--half-res-second', action='store_true', help='camera 1 at half resolution through a camera of its own')
+    ap.add_argument('--overlapped', action='store_true', help='upload tick n + 1 under the plan of tick n (process_sequence)')
     ap.add_argument('--cache', default='./cache/')
     args = ap.parse_args(argv)
     Importer, seq_names, config = DATASETS[args.dataset]
@@ -74,10 +96,19 @@ def main(argv=None):
         init[2] = None                                                 # alone on its camera: found by the detector
     elif args.seed == 'detect-all':
         init = [None] * T                                              # both hands of camera 0 from one detector plan
-    devices = [FileDevice([f.fileName for f in s.data], di) for s in seqs]
-    msp = MultiStreamPipeline(poseNetParams, config, di, devices, hands, comrefNetParams, init_com=init, seed_detect=args.seed != 'gt',
-                              max_extent=args.max_extent)
-    poses = msp.processVideos(max_frames=args.max_frames)
+    files = [[f.fileName for f in s.data] for s in seqs]
+
+    def run(half):
+        if half:
+            dis, cfg = [di, half_res_importer(di)], dict(config, fx=[config['fx'], config['fx'] / 2.], fy=[config['fy'], config['fy'] / 2.])
+            devices = [FileDevice(files[0], di), HalfResFileDevice(files[1], di)]
+            seeds = [c if c is None or d == 0 else numpy.asarray(c, numpy.float32) * numpy.float32([.5, .5, 1.]) for c, (d, _) in zip(init, hands)]
+        else:
+            dis, cfg, devices, seeds = di, config, [FileDevice(f, di) for f in files], init
+        msp = MultiStreamPipeline(poseNetParams, cfg, dis, devices, hands, comrefNetParams, init_com=seeds, seed_detect=args.seed != 'gt',
+                                  max_extent=args.max_extent)
+        return msp, msp.processVideos(max_frames=args.max_frames, overlapped=args.overlapped)
+    msp, poses = run(args.half_res_second)
     t = numpy.asarray(msp.frame_times[1:] or msp.frame_times)         # the first tick records the plan
     print("{} ticks, {} tracks, {:.3f} ms per tick (median; {:.3f} ms mean)".format(len(msp.frame_times), T, numpy.median(t) * 1000., t.mean() * 1000.))
     errs = []
@@ -87,6 +118,12 @@ def main(argv=None):
             err = HandposeEvaluation([f.gt3Dorig for f in seqs[d].data[:len(p)]], list(p)).getMeanError()
             print("camera {} left hand, mean error: {}mm".format(d, err))
         errs.append(err)
+    if args.half_res_second:                                           # the same scene through the other camera: the poses must be near
+        _, full = run(False)
+        n = min(len(full[2]), len(poses[2]))
+        diff = float(numpy.abs(full[2][:n] - poses[2][:n]).mean()) if n else float('nan')
+        print("camera 1 at half resolution against full resolution, mean difference over {} ticks: {:.3f} mm".format(n, diff))
+        return poses, errs, diff
     return poses, errs
 
 

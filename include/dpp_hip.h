@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 18
+#define DPP_ABI_VERSION 19
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -564,6 +564,38 @@ int dpp_pose_finish_ix(const float* net_out, int T, int J, const int* tflags, co
 #define DPP_INGEST_MEDIAN3 1
 #define DPP_INGEST_MIRROR_X 2
 int dpp_frame_ingest(const void* raw, int src_type, int B, int H, int W, int flags, float* frames, float* partial, dpp_stream_t stream);
+
+/* ---- frame sources of unlike cameras and frame sizes (ABI v19) ------------------------------------------------------------------------
+ * The tracking launches that read a frame or a camera, for C frame sources that each have a camera and a frame size of their own
+ * (hipdp/multitrack.py).  `sources` is a device array of C records of dpp_source_record_bytes() bytes:
+ *   double fx, fy, ux, uy;         the importer's camera, signs included (to3d / toimg of track_refine and pose_finish)
+ *   double crop_fx, crop_fy;       what the reference hands to HandDetector: abs(config fx / fy) (the crop geometry)
+ *   int64  frame_off, raw_off;     ELEMENT offset of the source's frame in the float32 frame buffer / in the raw sensor buffer
+ *   int32  H, W, flip_y, (pad);    the frame size; whether the camera flips the y axis
+ * The frames are ragged: source c's H x W floats start at frames + frame_off (raw: raw + raw_off elements of the sensor type); the
+ * host pads every offset to 16 bytes, the pad elements are never read or written.  The host validates the table once (offsets in range
+ * and aligned, H, W > 0, focal lengths != 0, raw and frames apart); the kernels trust it as they trust src[].  Row t of the
+ * track launches reads record src[t] (0 <= src[t] < C); the partials are dpp_frame_range's at B = C.
+ * These are the kernels of the plain and *_ix entry points with the table in place of the launch's (H, W, fx, fy, ux, uy, flip_y,
+ * crop_fx, crop_fy): with C equal records they give the bytes of the *_ix launches.  frame_ingest_src: band b of source c covers
+ * ceil(H_c / 64) rows of that source; an empty band writes its identities as in dpp_frame_ingest.
+ * DPP_E_BADARG (nothing launched): a NULL pointer (M_out and frame_ingest_src's partial may be NULL), T / C / J / dsz below 1, C above
+ * 65535, raw == frames, an unknown src_type or flag bit (DPP_CROP_FLIP_X comes from tflags, as in crop_warp_ex_ix). */
+size_t dpp_source_record_bytes(void);
+int dpp_frame_range_src(const float* frames, const void* sources, int C, float* partial, dpp_stream_t stream);
+int dpp_frame_ingest_src(const void* raw, int src_type, const void* sources, int C, int flags, float* frames, float* partial,
+                         dpp_stream_t stream);
+int dpp_crop_prepare_ranged_src(const float* partial, int T, const int* src, const int* gate, const void* sources, const float* com,
+                                const float* cube, int dsz, int stretch, void* records, float* M_out, dpp_stream_t stream);
+int dpp_crop_warp_src(const float* frames, const void* records, int T, const int* src, const void* sources, int dsz, int normalize,
+                      float nd_value, float* out, dpp_stream_t stream);
+int dpp_track_refine_src(const float* frames, const void* records_in, int T, const int* src, const int* gate, const void* sources,
+                         const float* com_in, const float* cube, const float* net_out, int dsz, float* com_out, float* com3d_out,
+                         void* records_out, float* M_out, int* status, dpp_stream_t stream);
+int dpp_crop_warp_ex_src(const float* frames, const void* records, int T, const int* src, const int* tflags, const void* sources, int dsz,
+                         int flags, float nd_value, float fill_value, float pad_value, float* out, dpp_stream_t stream);
+int dpp_pose_finish_src(const float* net_out, int T, int J, const int* src, const int* tflags, const void* sources, const float* cube,
+                        const float* com3d, float* pose3d, float* pose_img, dpp_stream_t stream);
 
 /* ---- whole-frame hand detection by connected components (ABI v14) -------------------------------------------------------------
  * What HandDetector.detect / estimateHandsize (handdetector.py:569-632, :911-937) take from cv2.findContours, restated with

@@ -15,6 +15,16 @@ configuration, after warm-up, five repetitions per process (median and spread = 
 of its own, the legs alternating.  Verdicts: at T = C = 8 the median tick lies below HALF the yardstick's median and the gap exceeds the
 larger of the two spreads; at T = C = 1 the tick is not slower than HandTracker.process by more than the larger spread.
 
+Further legs, same protocol (a child process per leg, the legs alternating, 2 processes per leg, median and spread = max - min):
+  --homogeneous --parent DIR   MultiTracker.process of this tree against the PARENT's at T = C = 1 and 8: the homogeneous tick must be
+                               within the larger of the two spreads (two-sided verdict: which side a miss falls on)
+  --mixed                      C sources alternating 480x640 (NYU camera) / 240x320 (the camera of half the intrinsics, every second
+                               row and column of the same frames) in ONE plan through the per-source table, against C homogeneous
+                               480x640 sources of this tree, at T = C = 8: wall clock per tick and the plans' device time
+  --sequence                   MultiTracker.process_sequence (uploads of tick n + 1 under the plan of tick n) against the process()
+                               loop of this tree at T = C = 1, 8, 16
+--configs 1x1,8x8 overrides a leg's (T, C) list.
+
 As in tools/track_bench.py the refinement net's last layer is zeroed, so every track stays on its seed whatever the random weights
 are; no timing depends on the values."""
 import argparse
@@ -65,6 +75,7 @@ def child(args):
     frames, com0 = _frames(nfr)
     N, reps = args.ticks, args.reps
     out = dict(leg=args.leg, tree=tree, ticks=N, reps=reps)
+    configs = [tuple(int(v) for v in c.split('x')) for c in args.configs.split(',')] if args.configs else CONFIGS
 
     def timed(fn):
         vals = []
@@ -80,10 +91,65 @@ def child(args):
     def tick_frames(i, C):
         return [frames[(i + c) % nfr] for c in range(C)]
 
-    if args.leg == 'yardstick':
+    def device_time(plan):
+        vals = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record(torch.cuda.current_stream())
+            for _ in range(N):
+                plan.run(rt)
+            e1.record(torch.cuda.current_stream())
+            torch.cuda.synchronize()
+            vals.append(e0.elapsed_time(e1) / N)
+        return vals
+
+    if args.leg in ('mixed', 'sequence'):
+        from data.importers import DepthImporter
+        from hipdp.multitrack import MultiTracker
+        half = DepthImporter(di.fx / 2., di.fy / 2., di.ux / 2., di.uy / 2.)
+        half.flip_y = True                                             # the NYU convention, as the full-size camera
+        small, com_small = np.ascontiguousarray(frames[:, ::2, ::2]), com0 * np.float32([.5, .5, 1.])
+        for T, C in configs:
+            pnet, snet = nets(T)
+            mixed = args.leg == 'mixed'
+            tracks = [(t % C, bool(t // C)) for t in range(T)]
+            if mixed:                                                  # even sources 480x640, odd ones 240x320 with their own camera
+                mt = MultiTracker(rt, [half if c % 2 else di for c in range(C)], pnet, snet, [240 if c % 2 else 480 for c in range(C)],
+                                  [320 if c % 2 else 640 for c in range(C)], cube, tracks)
+                assert mt.hetero == (C > 1)
+            else:
+                mt = MultiTracker(rt, di, pnet, snet, 480, 640, cube, tracks)
+            for t, (c, _) in enumerate(tracks):
+                mt.reset(t, com_small if mixed and c % 2 else com0)
+
+            def tick_of(i):
+                return [(small if mixed and c % 2 else frames)[(i + c) % nfr] for c in range(C)]
+            if mixed:
+                def run(i0):
+                    for i in range(N):
+                        assert all(r['status'] == 0 for r in mt.process(tick_of(i0 + i)))
+            else:
+                def run(i0):
+                    res = mt.process_sequence(tick_of(i0 + i) for i in range(N))
+                    assert len(res) == N and all(r['status'] == 0 for r in res[-1])
+            run(0)
+            vals = []
+            for r in range(reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run(r)
+                torch.cuda.synchronize()
+                vals.append((time.perf_counter() - t0) / N * 1e3)
+            out[args.leg + '_ms_' + _key(T, C)] = vals
+            if mixed:
+                out['mixed_device_ms_' + _key(T, C)] = device_time(mt.plan())
+                out['mixed_launches_' + _key(T, C)] = len(mt.plan().launches())
+            assert not mt.lost.any()
+    elif args.leg == 'yardstick':
         from hipdp.tracker import HandTracker
         pnet, snet = nets(1)
-        for T, C in CONFIGS:
+        for T, C in configs:
             trs = [HandTracker(rt, di, pnet, snet, 480, 640, cube, hand_right=bool(t % 2) and C < T) for t in range(T)]
             for tr in trs:
                 tr.reset(com0)
@@ -97,7 +163,7 @@ def child(args):
             out['yardstick_ms_' + _key(T, C)] = timed(tick)
     else:
         from hipdp.multitrack import MultiTracker
-        for T, C in CONFIGS:
+        for T, C in configs:
             pnet, snet = nets(T)
             mt = MultiTracker(rt, di, pnet, snet, 480, 640, cube, [(t % C, bool(t // C)) for t in range(T)])
             for t in range(T):
@@ -109,17 +175,7 @@ def child(args):
                 tick(i)
             out['multi_ms_' + _key(T, C)] = timed(tick)
             plan = mt.plan()
-            vals = []
-            for _ in range(reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                e0.record(torch.cuda.current_stream())
-                for _ in range(N):
-                    plan.run(rt)
-                e1.record(torch.cuda.current_stream())
-                torch.cuda.synchronize()
-                vals.append(e0.elapsed_time(e1) / N)
-            out['device_ms_' + _key(T, C)] = vals
+            out['device_ms_' + _key(T, C)] = device_time(plan)
             out['launches_' + _key(T, C)] = len(plan.launches())
             assert not mt.lost.any()
     print('MULTITRACK_BENCH ' + json.dumps(out))
@@ -131,26 +187,95 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--parent', default=None, help='checkout of the parent tree (built): it runs the yardstick')
     ap.add_argument('--rounds', type=int, default=2, help='alternations of the two legs')
-    ap.add_argument('--leg', choices=['multi', 'yardstick'], default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--homogeneous', action='store_true', help="this tree's process() against the parent's (needs --parent)")
+    ap.add_argument('--mixed', action='store_true', help='sources of unlike sizes and cameras against homogeneous ones')
+    ap.add_argument('--sequence', action='store_true', help='process_sequence against the process() loop')
+    ap.add_argument('--configs', default=None, help='T x C list of a leg, e.g. 1x1,8x8')
+    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence'], default=None, help=argparse.SUPPRESS)
     ap.add_argument('--tree', default=ROOT, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.leg:
         return child(args)
     ytree = os.path.abspath(args.parent) if args.parent else ROOT
-    res = {}
-    for r in range(args.rounds):
-        for leg, tree in (('yardstick', ytree), ('multi', ROOT)):
-            cmd = [sys.executable, os.path.abspath(__file__), '--leg', leg, '--tree', tree, '--ticks', str(args.ticks), '--reps', str(args.reps)]
-            p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=420, cwd=tree)
-            lines = [ln for ln in p.stdout.splitlines() if ln.startswith('MULTITRACK_BENCH ')]
-            if p.returncode != 0 or not lines:
-                sys.stdout.write(p.stdout[-4000:])
-                raise SystemExit("%s leg in %s failed (exit %d)" % (leg, tree, p.returncode))
-            for k, v in json.loads(lines[-1][len('MULTITRACK_BENCH '):]).items():
-                if isinstance(v, list):
-                    res.setdefault(k, []).extend(v)
-                else:
-                    res[k] = v
+
+    def run_legs(legs, configs):
+        """legs: (leg, tree, key prefix); every leg a child process of its own, alternating, args.rounds times."""
+        res = {}
+        for r in range(args.rounds):
+            for leg, tree, prefix in legs:
+                cmd = [sys.executable, os.path.abspath(__file__), '--leg', leg, '--tree', tree, '--ticks', str(args.ticks), '--reps', str(args.reps)]
+                if configs:
+                    cmd += ['--configs', configs]
+                p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=420, cwd=tree)
+                lines = [ln for ln in p.stdout.splitlines() if ln.startswith('MULTITRACK_BENCH ')]
+                if p.returncode != 0 or not lines:
+                    sys.stdout.write(p.stdout[-4000:])
+                    raise SystemExit("%s leg in %s failed (exit %d)" % (leg, tree, p.returncode))
+                for k, v in json.loads(lines[-1][len('MULTITRACK_BENCH '):]).items():
+                    if isinstance(v, list):
+                        res.setdefault(prefix + k, []).extend(v)
+                    else:
+                        res[prefix + k] = v
+        return res
+
+    def two_sided(what, a, b, na, nb):
+        """`a` against `b` (median, spread): within the larger spread, or which side the miss falls on."""
+        d, bar = a[0] - b[0], max(a[1], b[1])
+        side = 'within the larger spread' if abs(d) <= bar else ('%s is SLOWER' % na if d > 0 else '%s is FASTER' % na)
+        print("verdict %s: %s %.4f ms against %s %.4f ms; difference %+.4f ms, larger spread %.4f ms -> %s" % (what, na, a[0], nb, b[0], d, bar, side))
+        return d <= bar
+
+    head = "480x640 frames, ResNet type 1 (14 joints) + ScaleNet, fp32; %d ticks x %d repetitions x %d processes per leg" % (args.ticks, args.reps, args.rounds)
+    if args.homogeneous:
+        if not args.parent:
+            raise SystemExit("--homogeneous compares against --parent DIR")
+        cfgs = args.configs or '1x1,8x8'
+        res = run_legs([('multi', ytree, 'parent_'), ('multi', ROOT, '')], cfgs)
+        print("the homogeneous tick, MultiTracker.process of this tree against the parent checkout's; " + head)
+        print("all times in ms per tick: median (spread = max - min over the repetitions)")
+        ok = True
+        for c in cfgs.split(','):
+            T, C = (int(v) for v in c.split('x'))
+            k = _key(T, C)
+            m, y = _stat(res['multi_ms_' + k]), _stat(res['parent_multi_ms_' + k])
+            d, dy = _stat(res['device_ms_' + k]), _stat(res['parent_device_ms_' + k])
+            print("T = C = %d: this tree %.4f (%.4f), parent %.4f (%.4f); plan, device time: %.4f (%.4f), parent %.4f (%.4f)" % ((T,) + m + y + d + dy))
+            ok = two_sided('T = C = %d' % T, m, y, 'this tree', 'the parent') and ok
+        return 0 if ok else 1
+    if args.mixed:
+        cfgs = args.configs or '8x8'
+        res = run_legs([('multi', ROOT, ''), ('mixed', ROOT, '')], cfgs)
+        print("sources alternating 480x640 / 240x320 with cameras of their own (one plan, per-source table) against homogeneous 480x640 "
+              "sources; " + head)
+        print("all times in ms per tick: median (spread = max - min over the repetitions)")
+        ok = True
+        for c in cfgs.split(','):
+            T, C = (int(v) for v in c.split('x'))
+            k = _key(T, C)
+            m, h = _stat(res['mixed_ms_' + k]), _stat(res['multi_ms_' + k])
+            dm, dh = _stat(res['mixed_device_ms_' + k]), _stat(res['device_ms_' + k])
+            print("T = %d, C = %d: mixed tick %.4f (%.4f), homogeneous tick %.4f (%.4f); plan, device time: mixed %.4f (%.4f), homogeneous %.4f "
+                  "(%.4f); launches %d / %d" % ((T, C) + m + h + dm + dh + (res['mixed_launches_' + k], res['launches_' + k])))
+            ok = two_sided('T = %d, C = %d' % (T, C), m, h, 'the mixed tick', 'the homogeneous tick') and ok
+        return 0 if ok else 1
+    if args.sequence:
+        cfgs = args.configs or '1x1,8x8,16x16'
+        res = run_legs([('multi', ROOT, ''), ('sequence', ROOT, '')], cfgs)
+        print("MultiTracker.process_sequence (uploads of tick n + 1 under the plan of tick n) against the process() loop; " + head)
+        print("all times in ms per tick: median (spread = max - min over the repetitions)")
+        ok = True
+        for c in cfgs.split(','):
+            T, C = (int(v) for v in c.split('x'))
+            k = _key(T, C)
+            q, m, d = _stat(res['sequence_ms_' + k]), _stat(res['multi_ms_' + k]), _stat(res['device_ms_' + k])
+            print("T = C = %d: process_sequence %.4f (%.4f), process loop %.4f (%.4f), plan device time %.4f (%.4f)" % ((T,) + q + m + d))
+            within = two_sided('T = C = %d' % T, q, m, 'process_sequence', 'the process loop')
+            faster = m[0] - q[0] > max(q[1], m[1])
+            ok = (faster if C >= 8 else within) and ok
+            if C >= 8:
+                print("  claim at C >= 8 (faster by more than the larger spread): %s" % ('holds' if faster else 'DOES NOT hold'))
+        return 0 if ok else 1
+    res = run_legs([('yardstick', ytree, ''), ('multi', ROOT, '')], None)
     print("one tick of T tracks over C cameras, 480x640 frames, ResNet type 1 (14 joints) + ScaleNet, fp32; %d ticks x %d repetitions x %d "
           "processes per leg" % (args.ticks, args.reps, args.rounds))
     print("yardstick (T sequential HandTracker.process calls, nets at batch one) measured on: %s" % ('the parent checkout' if args.parent else 'this tree'))
