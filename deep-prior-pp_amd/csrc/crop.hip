@@ -467,12 +467,6 @@ __global__ __launch_bounds__(DPP_THREADS) void frame_range_kernel(const float* _
     partial[((size_t)b * FR_BANDS + band) * 2 + 1] = mx;
 }
 
-// a centre that cannot be cropped around: its depth is numpy.isclose to 0 (comToBounds' "CoM ill-defined" test) or it is not finite
-__device__ __forceinline__ bool com_ill_defined(const float c[3]) {
-    const bool finite = fabs((double)c[0]) <= 3.4e38 && fabs((double)c[1]) <= 3.4e38 && fabs((double)c[2]) <= 3.4e38;   // false for NaN
-    return !finite || fabs((double)c[2]) <= 1e-8;
-}
-
 // the record of an EMPTY window: crop_warp writes its fill value everywhere (0 when normalised), nothing divides by zero; M = identity
 __device__ __forceinline__ void crop_empty_record(float min_depth, float max_depth, CropRec& r, float* __restrict__ M) {
     r.xstart = 0; r.ystart = 0; r.cw = 0; r.ch = 0; r.szw = 0; r.szh = 0; r.xs = 0; r.ys = 0;

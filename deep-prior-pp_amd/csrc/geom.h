@@ -1,4 +1,4 @@
-// geom.h -- the camera, crop-bounds and warp-coordinate arithmetic that augment.hip, crop.hip, components.hip and prior.hip share,
+// geom.h -- the camera, crop-bounds and warp-coordinate arithmetic that augment.hip, crop.hip, components.hip, prior.hip and fuse.hip share,
 // and the workgroup reductions of the whole-frame kernels (crop.hip, components.hip, ingest.hip).
 //
 // Everything here restates NumPy / OpenCV 2.4 arithmetic that rounds after every operation and is pinned bit for bit to the reference,
@@ -115,6 +115,14 @@ __device__ __forceinline__ float z_threshold(float v, float zlo, float zhi) {
 
 // numpy.isclose(v, ref) of a float32 pixel against recropHand's nv_val (handdetector.py:782-803; NumPy 1: the comparison is float64)
 __device__ __forceinline__ bool is_close(float v, double ref) { return fabs((double)v - ref) <= 1e-8 + 1e-5 * fabs(ref); }
+
+
+// a centre that cannot be cropped around: its depth is numpy.isclose to 0 (comToBounds' "CoM ill-defined" test) or it is not finite
+// (crop.hip's tracking launches, fuse.hip's peer centre)
+__device__ __forceinline__ bool com_ill_defined(const float c[3]) {
+    const bool finite = fabs((double)c[0]) <= 3.4e38 && fabs((double)c[1]) <= 3.4e38 && fabs((double)c[2]) <= 3.4e38;   // false for NaN
+    return !finite || fabs((double)c[2]) <= 1e-8;
+}
 
 
 // ---- workgroup reductions that crop.hip and components.hip share ---------------------------------------------------------------

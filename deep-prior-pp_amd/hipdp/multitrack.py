@@ -13,8 +13,9 @@ again.  Here every launch of that plan runs once per tick for all tracks:
     crop_warp_ex_ix                 at B = T       the final crop, mirrored where tflags[t] has POSE_HAND_RIGHT
     the pose net's forward plan, built for a batch of T
     pose_finish_ix                  at B = T       the sign rules per track from tflags[t]
+    pose_fuse                       at G groups    only with `groups`: the tracks of one hand fused, lost tracks handed over (below)
 
-so the launch count is HandTracker's whatever T and C are.  A track names its source (`src`), its hand side and invX / invY
+so the launch count is HandTracker's whatever T and C are (plus one with `groups`).  A track names its source (`src`), its hand side and invX / invY
 (`tflags`) and whether it takes part in this tick (`gate`) in three small int32 device arrays; the hand side is data, not a launch
 argument, so there is one plan, not one per flag combination.  C cameras with one hand each is tracks = [(c, False) for c in
 range(C)]; both hands of one camera is tracks = [(0, False), (0, True)]; mixtures are allowed.
@@ -30,7 +31,25 @@ one, or one model with per-unit calibration -- the tracker builds a per-source t
 HandDetector's fx / fy, frame size, frame offsets), keeps the frames in ONE ragged buffer (every frame padded to 16 bytes) and
 builds the same plan through the *_src siblings of the launches that read a frame or a camera (ABI v19): the same kernels with the
 table in place of the scalars, the same launch count.  All entries equal is the homogeneous path, untouched.  The sensor options
-(dtype / median / mirror) stay common to all sources; extrinsics or any fusion across cameras are out of scope.
+(dtype / median / mirror) stay common to all sources.
+
+FUSION (ABI v20; csrc/fuse.hip).  The reference has one device and one camera: what follows is THIS PROJECT'S OWN, stated in
+include/dpp_hip.h, restated in NumPy by tests/fuse_ref.py and pinned to it bit for bit.  `extrinsics` gives every source an (R, t)
+with w = R p + t from its camera frame (the frame of `pose` / `com3D`: the importer's jointImgTo3D frame, flip_y included) to one
+world frame (mm); `groups` lists the tracks that observe the same physical hand from different sources.  One more launch at the end of
+the plan, one workgroup per group, then
+  - averages the group's OK tracks in the world frame: MultiTracker.fused[g] = dict(pose, com, spread, n) -- the fused joints, the
+    fused centre, per joint the largest distance of a member's joint from the fused one, the number of tracks that went in;
+  - with `max_dev` (mm) drops from the average a track whose world centre is farther than that from the componentwise median of
+    three or more (`outlier`: it slid onto something else), and marks two that are farther apart than that (`disagree`: both still go in);
+  - gives every member the centre its peers see, projected by its own camera (`peer_com`), and with `handover` writes that centre
+    into a member that lost the hand in this tick or is an outlier (`handed`).  A handed track is reported LOST for the tick but is
+    not marked lost: it runs ungated in the next tick from its peers' centre -- one tick of outage, no detector plan, no upload.
+A track that is gated because it is lost (it lost the hand while no peer had it) is restarted by process() through reset(t, peer_com)
+in the first tick in which its peers have the hand: one small upload, as acquire makes.  Tracks in no group are left entirely alone, and
+without `groups` the tracker allocates, uploads, launches and returns exactly what it did before.  Confidence weighting, temporal
+filtering, triangulation from 2-D alone, calibrating the extrinsics, fusing the depth frames themselves, hand size for several hands
+and per-source sensor options are out of scope.
 
 acquire_source(c, frame) finds ALL hands of a source in one detector plan and starts the source's tracks from them; the detectors
 are built per source, at that source's size and focal lengths, on views of its frame slice.
@@ -38,7 +57,9 @@ are built per source, at that source's size and focal lengths, on views of its f
 SEQUENCES.  process_sequence(ticks) is HandTracker.process_sequence for several sources: two sets of input buffers, the uploads of
 tick n + 1 on the copy stream under the plan of tick n, the result block of tick n read while tick n + 1 is in flight.  The host
 therefore learns one tick late that a track was lost: the track runs ungated for one more tick (track_refine reports it LOST there:
-a frame queued behind a lost one stays lost) and is gated from the tick after.  Nothing is detected inside a sequence.
+a frame queued behind a lost one stays lost) and is gated from the tick after.  Nothing is detected inside a sequence, and nothing is
+reset from the host inside one: the hand-over on the device needs no host knowledge, so a track lost and handed in tick n is OK again
+in tick n + 1 as in the process() loop, but a track that is gated because it is lost stays gated until the sequence ends.
 """
 import numpy as np
 
@@ -49,7 +70,7 @@ from .tracker import IDLE, LOST, OK, _engine, refine_stage
 
 class MultiTracker(object):
     def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, tracks, sources=None, invX=False, invY=False, fx=None, fy=None,
-                 sensor=None):
+                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True):
         """
         :param importer:   the dataset importer (the camera) of all sources, or a sequence of C importers, one per source
         :param poseNet, comrefNet: as for HandTracker, but built for a batch of len(tracks): row t is track t
@@ -61,6 +82,11 @@ class MultiTracker(object):
         :param fx, fy:     what the reference hands to HandDetector (a value for all sources or a sequence of C; None entries
                            and the default: the source's importer's)
         :param sensor:     as for HandTracker, for ALL sources: frames are raw sensor frames and frame_ingest runs at B = C
+        :param extrinsics: one (R, t) per source: R a 3 x 3 rotation, t in mm, w = R p + t from the source's camera frame to the world
+        :param groups:     list of lists of track indices: the tracks of a group observe the same hand from pairwise distinct sources
+                           (disjoint, 1 .. 16 members each; needs `extrinsics`).  None: no fusion, the tracker of before
+        :param max_dev:    None, or the distance (mm) beyond which a member's world centre is an outlier / two members disagree
+        :param handover:   a member that lost the hand (or is an outlier) goes on from its peers' centre; False: fusion reports only
         """
         self.rt = rt
         tracks = [(int(s), bool(r)) for s, r in tracks]
@@ -71,6 +97,11 @@ class MultiTracker(object):
         self.src_host = ops.track_index([s for s, _ in tracks], C)           # the kernels trust it: checked here
         if C > T:
             raise ValueError("%d sources for %d tracks: every source needs a track that reads it" % (C, T))
+        if groups is not None and extrinsics is None:
+            raise ValueError("groups needs extrinsics: one (R, t) per source")
+        if max_dev is not None and not (np.isfinite(max_dev) and max_dev > 0.):
+            raise ValueError("max_dev is None or a distance > 0 (mm): %r" % (max_dev,))
+        self.max_dev, self.handover = None if max_dev is None else float(max_dev), bool(handover)
         importers = self._per_source(importer, C, 'importer')
         Hs, Ws = self._per_source(H, C, 'H'), self._per_source(W, C, 'W')
         if any(int(h) != h or int(w) != w or h < 1 or w < 1 for h, w in zip(Hs, Ws)):
@@ -115,7 +146,20 @@ class MultiTracker(object):
         # pose (mm), pose in image coordinates, centres (= the state), com3D, M, status (+ one detector's 8 words: acquire)
         self._off = off = dict(pose=0, pose_img=T * J3, com=2 * T * J3, com3D=2 * T * J3 + 3 * T, M=2 * T * J3 + 6 * T,
                                status=2 * T * J3 + 15 * T, det=2 * T * J3 + 16 * T)
-        self.res = rt.alloc(off['det'] + 8, f32)
+        n_res = off['det'] + 8
+        self.rig = None if groups is None else ops.FuseRig(rt, extrinsics, groups, self.src_host, C)   # validated there, uploaded once
+        if self.rig is not None:                                                   # the fused arrays follow: every offset above keeps its value
+            G = self.rig.G
+            off.update(fused_pose=n_res, fused_com=n_res + G * J3, spread=n_res + G * J3 + 3 * G, n=n_res + G * J3 + 3 * G + G * self.J)
+            off.update(peer_com=off['n'] + G, fstat=off['n'] + G + 3 * T)
+            n_res = off['fstat'] + T
+        self.res = rt.alloc(n_res, f32)
+        self.fused = []
+        if self.rig is not None:
+            G = self.rig.G
+            self.fused_pose, self.fused_com = self.res.view(off['fused_pose'], (G, self.J, 3)), self.res.view(off['fused_com'], (G, 3))
+            self.spread, self.fused_n = self.res.view(off['spread'], (G, self.J)), self.res.view(off['n'], (G,), i32)
+            self.peer_com, self.fstat = self.res.view(off['peer_com'], (T, 3)), self.res.view(off['fstat'], (T,), i32)
         self.pose3d, self.pose_img = self.res.view(off['pose'], (T, self.J, 3)), self.res.view(off['pose_img'], (T, self.J, 3))
         self.com, self.com3d = self.res.view(off['com'], (T, 3)), self.res.view(off['com3D'], (T, 3))
         self.M, self.status = self.res.view(off['M'], (T, 9)), self.res.view(off['status'], (T,), i32)
@@ -177,6 +221,11 @@ class MultiTracker(object):
         self.com.view(3 * t, (1, 3)).set(com)
         self.com_host[t] = com
         self.lost[t] = False
+
+    def drop(self, t):
+        """Mark track t lost: the application knows what the tracker cannot see (the only loss test is a centre at depth 0) -- its
+        camera is covered, the hand left.  The track is gated until reset / acquire, or, in a group, until its peers have the hand."""
+        self.lost[self._track(t)] = True
 
     def set_cube(self, t, cube):
         t = self._track(t)
@@ -348,6 +397,10 @@ class MultiTracker(object):
             else:
                 p.add(ops.pose_finish_src(rt, self.peng.out.buf, T, self.J, self.src, self.tflags, tab, self.cube, self.com3d, self.pose3d,
                                           self.pose_img))
+            if self.rig is not None:                    # the last launch of the main lane: the next tick's prepare is ordered behind it
+                p.add(ops.pose_fuse(rt, self.pose3d, self.com3d, self.status, self.src, T, self.J, self.rig, tab, H, W, self.cam, self.max_dev,
+                                    self.handover, self.com, self.fused_pose, self.fused_com, self.spread, self.fused_n, self.peer_com,
+                                    self.fstat))
             self._plans[slot] = p
         return self._plans[slot]
 
@@ -370,14 +423,29 @@ class MultiTracker(object):
         com, com3d = res[o['com']:o['com3D']].reshape(T, 3), res[o['com3D']:o['M']].reshape(T, 3)
         M = res[o['M']:o['status']].reshape(T, 3, 3)
         self.com_host[:] = com
+        rig = self.rig
+        if rig is not None:
+            G = rig.G
+            fstat, peer = res[o['fstat']:o['fstat'] + T].view(np.int32), res[o['peer_com']:o['fstat']].reshape(T, 3)
+            fpose, fcom = res[o['fused_pose']:o['fused_com']].reshape(G, J, 3), res[o['fused_com']:o['spread']].reshape(G, 3)
+            spread, fn = res[o['spread']:o['n']].reshape(G, J), res[o['n']:o['peer_com']].view(np.int32)
+            self.fused = [dict(pose=fpose[g], com=fcom[g], spread=spread[g], n=int(fn[g])) for g in range(G)]
+            self._peer_ok = (fstat & ops.FUSE_PEER_OK) != 0
         out = []
         for t in range(T):
             status = int(st[t])
+            grouped = rig is not None and rig.group_of[t] >= 0
+            handed = grouped and bool(fstat[t] & ops.FUSE_HANDED)
             if not gate[t]:                          # gated because it is lost (or never started): LOST; because its source idles: IDLE
                 status = LOST if self.lost[t] else IDLE
             else:
-                self.lost[t] = status != OK
+                # handed over on the device: LOST in this tick, but it goes on from its peers' centre.  (Not in the tick that
+                # process_sequence runs ungated behind a loss the host had not seen yet: that track is gated in a process() loop.)
+                self.lost[t] = status != OK and (bool(self.lost[t]) or not handed)
             d = dict(pose=pose[t], pose_img=pimg[t], com=com[t], com3D=com3d[t], M=M[t], status=status)
+            if grouped:
+                d.update(group=int(rig.group_of[t]), outlier=bool(fstat[t] & ops.FUSE_OUTLIER), disagree=bool(fstat[t] & ops.FUSE_DISAGREE),
+                         handed=handed, peer_com=peer[t])
             if crops is not None:
                 d['crop'] = crops[t]
             out.append(d)
@@ -402,7 +470,13 @@ class MultiTracker(object):
         self.plan().run(self.rt)
         self.runs += 1
         self.rt.synchronize()
-        return self._results(self.res.get(), gate, self.crop.get() if return_crop else None)
+        out = self._results(self.res.get(), gate, self.crop.get() if return_crop else None)
+        if self.rig is not None and self.handover:
+            for t in np.flatnonzero(self.rig.group_of >= 0):
+                # gated BECAUSE it is lost, and its peers have the hand now: start it again from their centre (one small upload)
+                if not gate[t] and self.lost[t] and self._peer_ok[t]:
+                    self.reset(t, out[t]['peer_com'])
+        return out
 
     def process_sequence(self, ticks, return_crops=False):
         """A sequence of ticks (an iterable of per-source frame lists, None for "no frame", as process takes them): the uploads of
@@ -414,7 +488,8 @@ class MultiTracker(object):
         reports it LOST again (its centre is ill-defined), and is gated from tick n + 2 on, as in process().  A lost track stops
         neither the sequence nor the other tracks; nothing is detected inside a sequence.  For every track-tick whose status is OK
         or IDLE every key has the bits of the process() loop; for LOST only the status is promised.  self.lost, com_host, gate_host
-        and runs are afterwards what the loop would have left (a lost track's centre is put back to the one it was lost with)."""
+        and runs are afterwards what the loop would have left (a lost track's centre is put back to the one it was lost with; a track
+        that was handed its peers' centre is not lost and keeps it).  With `groups`, self.fused_ticks holds self.fused of every tick."""
         rt = self.rt
         staged = hasattr(rt, 'staged_upload')
         self._second_set()
@@ -430,7 +505,9 @@ class MultiTracker(object):
                 if self.lost[t] and not was[t]:
                     lost_com[t] = out[t]['com'].copy()
             results.append(out)
+            self.fused_ticks.append(self.fused)
         last = None
+        self.fused_ticks = []                           # MultiTracker.fused of every tick of this sequence (empty lists without groups)
         for n, frames in enumerate(ticks):
             if len(frames) != self.C:
                 raise ValueError("%d frames for %d sources" % (len(frames), self.C))

@@ -959,6 +959,66 @@ def pose_finish_src(rt, net_out, T, J, src, tflags, table, cube, com3d, pose3d, 
                   (net_out, src, tflags, table.dev, cube, com3d, pose3d, pose_img), name)
 
 
+# ---- tracks of one hand across calibrated cameras (include/dpp_hip.h, ABI v20; csrc/fuse.hip) ------------------------------------------
+FUSE_USED, FUSE_OUTLIER, FUSE_DISAGREE, FUSE_PEER_OK, FUSE_HANDED = 1, 2, 4, 8, 16     # DPP_FUSE_*: dpp_pose_fuse's per-track word
+FUSE_HANDOVER = 1                                                                      # ... and its launch flag
+FUSE_MAX_MEMBERS = 16
+
+
+class FuseRig(object):
+    """What dpp_pose_fuse reads about the rig, validated here (the kernel trusts it) and uploaded ONCE: `extr` (float64 [C][12]: R
+    row-major, then t in mm, per source: w = R p + t takes the source's camera frame to the world), `members` / `offsets` (int32: group
+    g is the tracks members[offsets[g]:offsets[g + 1]] in list order) and, on the host, `groups` and `group_of` (track -> group or -1)."""
+
+    def __init__(self, rt, extrinsics, groups, src, C):
+        src = np.asarray(src, np.int32).reshape(-1)
+        T = src.size
+        if extrinsics is None or len(extrinsics) != C:
+            raise ValueError("one (R, t) per source: %s for %d sources" % ('none' if extrinsics is None else len(extrinsics), C))
+        ext = np.zeros((C, 12), np.float64)
+        for c, (Rm, t) in enumerate(extrinsics):
+            Rm, t = np.asarray(Rm, np.float64), np.asarray(t, np.float64).reshape(-1)
+            if Rm.shape != (3, 3) or t.shape != (3,) or not np.isfinite(Rm).all() or not np.isfinite(t).all():
+                raise ValueError("source %d: R is a finite 3 x 3 rotation, t a finite 3-vector (mm)" % c)
+            if np.abs(Rm.T.dot(Rm) - np.eye(3)).max() > 1e-6 or not np.linalg.det(Rm) > 0.:
+                raise ValueError("source %d: R is not a rotation (max |R^T R - I| <= 1e-6 and det R > 0): %r" % (c, Rm))
+            ext[c, :9], ext[c, 9:] = Rm.ravel(), t
+        groups = [[int(m) for m in g] for g in groups]
+        group_of = np.full(T, -1, np.int32)
+        if not groups:
+            raise ValueError("groups needs at least one group")
+        for g, ms in enumerate(groups):
+            if not 1 <= len(ms) <= FUSE_MAX_MEMBERS:
+                raise ValueError("group %d has %d members: 1 .. %d" % (g, len(ms), FUSE_MAX_MEMBERS))
+            if any(not 0 <= m < T for m in ms):
+                raise ValueError("group %d names a track outside 0 .. %d: %r" % (g, T - 1, ms))
+            if any(group_of[m] >= 0 for m in ms) or len(set(ms)) != len(ms):
+                raise ValueError("groups are disjoint: group %d repeats a track: %r" % (g, ms))
+            if len(set(int(src[m]) for m in ms)) != len(ms):
+                raise ValueError("the members of group %d read pairwise distinct sources: %r" % (g, [int(src[m]) for m in ms]))
+            group_of[ms] = g
+        self.G, self.C, self.T, self.groups, self.group_of, self.extr_host = len(groups), int(C), T, groups, group_of, ext
+        self.members_host = np.int32([m for ms in groups for m in ms])
+        self.offsets_host = np.int32(np.concatenate([[0], np.cumsum([len(ms) for ms in groups])]))
+        self.extr, self.members, self.offsets = rt.upload(ext), rt.upload(self.members_host), rt.upload(self.offsets_host)
+
+
+def pose_fuse(rt, pose3d, com3d, status, src, T, J, rig, table, H, W, cam, max_dev, handover, com, fused_pose, fused_com, spread, n_out,
+              peer_com, fstat, name='pose_fuse'):
+    """dpp_pose_fuse: one workgroup per group of `rig`.  table: an ops.SourceTable, or None with (H, W, cam) for every source; max_dev:
+    None (no consistency test) or > 0 (mm)."""
+    if max_dev is not None and not (np.isfinite(max_dev) and max_dev > 0.):
+        raise ValueError("max_dev is None or a distance > 0 (mm): %r" % (max_dev,))
+    fx, fy, ux, uy, flip = (0., 0., 0., 0., 0) if table is not None else cam
+    return Launch(rt.lib.dpp_pose_fuse,
+                  (pose3d.ptr, com3d.ptr, status.ptr, src.ptr, T, J, rig.extr.ptr, rig.C, rig.members.ptr, rig.offsets.ptr, rig.G,
+                   None if table is None else table.dev.ptr, 0 if table is not None else int(H), 0 if table is not None else int(W), float(fx),
+                   float(fy), float(ux), float(uy), int(flip), 0.0 if max_dev is None else float(max_dev), FUSE_HANDOVER if handover else 0,
+                   com.ptr, fused_pose.ptr, fused_com.ptr, spread.ptr, n_out.ptr, peer_com.ptr, fstat.ptr),
+                  (pose3d, com3d, status, src, rig.extr, rig.members, rig.offsets, None if table is None else table.dev, com, fused_pose,
+                   fused_com, spread, n_out, peer_com, fstat), name)
+
+
 def refine_com_iterative(rt, frames, partial, B, H, W, com_in, cube, fx, fy, num_iter, com_out, status, name='refine_com_iterative'):
     """dpp_refine_com_iterative: refineCoMIterative of B frames, all iterations in one launch."""
     return Launch(rt.lib.dpp_refine_com_iterative, (frames.ptr, partial.ptr, B, H, W, com_in.ptr, cube.ptr, float(fx), float(fy), int(num_iter),

@@ -402,12 +402,19 @@ class MultiStreamPipeline(object):
     component detector, as RealtimeHandposePipeline's _need_seed does after a lost frame: ONE detector plan per device with lost
     tracks (MultiTracker.acquire_source) finds as many hands as the device has tracks and shares them out -- followed tracks keep
     theirs, the lost ones take the rest, nearest first -- so both hands of one camera start, and come back, without an init_com.
-    max_extent (mm) keeps things larger than a hand (a wall behind one hand) from being taken for the second."""
+    max_extent (mm) keeps things larger than a hand (a wall behind one hand) from being taken for the second.
+
+    Fusion (this project's own; hipdp/multitrack.py): with config['extrinsics'] -- one (R, t) per device, camera frame to world, mm --
+    and groups= (lists of tracks that observe the same hand from different devices) every tick also fuses each group: processFrames'
+    results carry MultiTracker's group / outlier / disagree / handed / peer_com per grouped track, `fused` holds the last tick's
+    dict(pose, com, spread, n) per group, and processVideos leaves in `fused_poses` one (ticks, J, 3) array per group of the fused
+    poses (world frame, mm) of the ticks in which at least one of its tracks was followed.  A grouped track that loses the hand is
+    handed its peers' centre instead of waiting for a detection."""
 
     HAND_LEFT, HAND_RIGHT = RealtimeHandposePipeline.HAND_LEFT, RealtimeHandposePipeline.HAND_RIGHT
 
     def __init__(self, poseNet, config, di, devices, hands, comrefNet, init_com=None, seed_detect=False, sensor=None, verbose=False,
-                 max_extent=None):
+                 max_extent=None, groups=None, max_dev=None, handover=True):
         """
         :param poseNet, comrefNet: built nets or their parameters (as for RealtimeHandposePipeline), with batchSize == len(hands)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=]); fx / fy: one value, or a list with one per device
@@ -418,8 +425,11 @@ class MultiStreamPipeline(object):
         :param seed_detect: acquire tracks without a centre by detection, again after they are lost
         :param sensor:    as for RealtimeHandposePipeline, for all devices
         :param max_extent: None, or the largest metric width / height (mm) of a component that seed_detect may take for a hand
+        :param groups, max_dev, handover: MultiTracker's, with config['extrinsics'] (one (R, t) per device)
         """
         self.max_extent = max_extent
+        self.groups, self.max_dev, self.handover = groups, max_dev, handover
+        self.fused, self.fused_poses = [], []
         self.config = copy.deepcopy(config)
         self.devices = list(devices)
         self.importers = list(di) if isinstance(di, (list, tuple)) else [di] * len(self.devices)
@@ -464,7 +474,8 @@ class MultiStreamPipeline(object):
                                          shapes[0][0] if same else [s[0] for s in shapes], shapes[0][1] if same else [s[1] for s in shapes],
                                          cfg['cube'], [(d, h == self.HAND_RIGHT) for d, h in self.hands], sources=len(self.devices),
                                          invX=cfg.get('invX') is True, invY=cfg.get('invY') is True, fx=cfg['fx'], fy=cfg['fy'],
-                                         sensor=self.sensor)
+                                         sensor=self.sensor, extrinsics=cfg.get('extrinsics'), groups=self.groups, max_dev=self.max_dev,
+                                         handover=self.handover)
             self._tracker_key = shapes
             self._seeded = [False] * len(self.hands)
         return self._tracker
@@ -499,7 +510,9 @@ class MultiStreamPipeline(object):
             self._seeded[t] = True
         for d in sorted(search):
             mt.acquire_source(d, frames[d], max_extent=self.max_extent)
-        return mt.process(frames)
+        res = mt.process(frames)
+        self.fused = mt.fused
+        return res
 
     def _read(self):
         """One frame (or None) per device; None when a FileDevice has ended or no device delivered."""
@@ -534,7 +547,12 @@ class MultiStreamPipeline(object):
         def go_on():
             return not self.stop.value and (max_frames is None or state['ticks'] < max_frames) and not state['ended']
 
-        def collect(res, tick):
+        fused_poses = [[] for _ in (self.groups or [])]
+
+        def collect(res, tick, fused):
+            for g, f in enumerate(fused):
+                if f['n'] > 0:
+                    fused_poses[g].append(f['pose'].copy())
             for t, r in enumerate(res):
                 if r['status'] == 0:
                     poses[t].append(r['pose'].copy())
@@ -563,7 +581,7 @@ class MultiStreamPipeline(object):
             start = time.time()
             res = self.processFrames(frames)
             times.append(time.time() - start)
-            collect(res, state['ticks'])
+            collect(res, state['ticks'], self.fused)
             state['ticks'] += 1
             if not self.seed_detect and all(self._tracker.lost):
                 break
@@ -573,7 +591,8 @@ class MultiStreamPipeline(object):
                 first, start = state['ticks'], time.time()
                 out = self._tracker.process_sequence(stretch(self._tracker))
                 for i, res in enumerate(out):
-                    collect(res, first + i)
+                    collect(res, first + i, self._tracker.fused_ticks[i])
+                self.fused = self._tracker.fused
                 times.extend([(time.time() - start) / max(1, len(out))] * len(out))
                 if not self.seed_detect and all(self._tracker.lost):
                     break
@@ -581,4 +600,5 @@ class MultiStreamPipeline(object):
             dev.stop()
         self.frame_times = times
         J = self.poseNet.cfgParams.outputDim[1] // 3
+        self.fused_poses = [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in fused_poses]
         return [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in poses]

@@ -17,6 +17,15 @@ are halved: the same scene through a different camera, in the same plan as the f
 per-source table).  The second camera's 3-D poses must then land near those of the all-full-resolution run, which is made as well;
 the mean difference is printed -- a sanity figure, not a bar.  --overlapped runs the ticks through MultiTracker.process_sequence.
 
+--fuse plays the SAME sequence through two cameras and fuses the two tracks of its one hand (hipdp/multitrack.py `groups=`, this
+project's own semantics): camera 0 is the recording, camera 1 delivers it at half resolution AND upside down (rotated by 180 degrees
+about the optical axis) through the importer that fits -- a known rigid transform of the camera, whose inverse is handed to the tracker
+as camera 1's extrinsics (camera 0: the identity), so that both see one world.  Prints the mean spread of the fused joints and the
+mean distance of the fused pose from each camera's own -- sanity figures, not bars.  --drop-second A:B covers camera 1 in ticks A ..
+B - 1: its frames are all zero and the example marks its track lost (an empty frame moves no centre to depth 0, which is the tracker's
+only loss test; the application knows that its camera sees nothing).  In every covered tick the track is handed the centre camera 0
+sees, so it is followed again in the first tick in which the frames are back, without a detector plan; the ticks are printed.
+
     python examples/realtime_multi.py --dataset icvl --data ../data/ICVL/ --seqs test_seq_1 test_seq_2
 """
 import argparse
@@ -56,6 +65,79 @@ def half_res_importer(di):
     return half
 
 
+class UpsideDownHalfResFileDevice(FileDevice):
+    """Every second row and column, rotated by 180 degrees: the half-resolution camera mounted upside down."""
+
+    def getDepth(self):
+        ret, frame = super(UpsideDownHalfResFileDevice, self).getDepth()
+        return ret, numpy.ascontiguousarray(frame[::2, ::2][::-1, ::-1])
+
+
+def upside_down_half_res_importer(di, H2, W2):
+    """The camera of UpsideDownHalfResFileDevice: pixel (u, v) of the half-resolution frame lands at (W2 - 1 - u, H2 - 1 - v), so with the
+    principal point mirrored in the same way x and y change sign: its frame is the recorded camera's rotated by diag(-1, -1, 1)."""
+    half = half_res_importer(di)
+    half.ux, half.uy = (W2 - 1) - half.ux, (H2 - 1) - half.uy
+    return half
+
+
+def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
+    """--fuse: one sequence through two cameras, the two tracks of its hand fused; returns a dict of what is printed."""
+    files = [f.fileName for f in seqs[0].data]
+    H, W = numpy.asarray(di.loadDepthMap(files[0])).shape
+    H2, W2 = (H + 1) // 2, (W + 1) // 2
+    di2 = upside_down_half_res_importer(di, H2, W2)
+    Rz = numpy.diag([-1., -1., 1.])                                    # camera 1's frame -> world (= camera 0's frame): its own inverse
+    cfg = dict(config, fx=[config['fx'], config['fx'] / 2.], fy=[config['fy'], config['fy'] / 2.],
+               extrinsics=[(numpy.eye(3), numpy.zeros(3)), (Rz, numpy.zeros(3))])
+    c0 = numpy.asarray(seqs[0].data[0].gtorig[di.crop_joint_idx], numpy.float32)
+    seeds = [c0, numpy.float32([(W2 - 1) - c0[0] / 2., (H2 - 1) - c0[1] / 2., c0[2]])]
+    devices = [FileDevice(files, di), UpsideDownHalfResFileDevice(files, di)]
+    msp = MultiStreamPipeline(poseNetParams, cfg, [di, di2], devices, hands, comrefNetParams, init_com=seeds, groups=[[0, 1]],
+                              max_dev=args.max_dev)
+    drop = range(0)
+    if args.drop_second:
+        a, b = (int(v) for v in args.drop_second.split(':'))
+        drop = range(a, b)
+    msp.initNets()
+    for dev in devices:
+        dev.start()
+    status, spread, dist, fused = [], [], [[], []], []
+    tick = 0
+    while args.max_frames is None or tick < args.max_frames:
+        frames = msp._read()
+        if frames is None:
+            break
+        if tick in drop:                                               # camera 1 is covered: no depth at all, so no hand
+            frames[1] = numpy.zeros_like(frames[1])
+            if msp._tracker is not None:
+                msp._tracker.drop(1)
+        res = msp.processFrames(frames)
+        status.append([r['status'] for r in res])
+        f = msp.fused[0]
+        if f['n'] == 2:
+            spread.append(float(f['spread'].mean()))
+            for t, (Rm, tv) in enumerate(cfg['extrinsics']):
+                world = res[t]['pose'].astype(numpy.float64).dot(Rm.T) + tv
+                dist[t].append(float(numpy.sqrt(((world - f['pose']) ** 2).sum(1)).mean()))
+        if f['n'] > 0:
+            fused.append(f['pose'].copy())
+        tick += 1
+    for dev in devices:
+        dev.stop()
+    out = dict(status=status, spread=float(numpy.mean(spread)) if spread else float('nan'),
+               dist=[float(numpy.mean(d)) if d else float('nan') for d in dist], fused=numpy.asarray(fused, numpy.float32), dropped=list(drop),
+               back=None)
+    print("{} ticks, both cameras followed in {}: mean spread {:.3f} mm, fused pose {:.3f} mm from camera 0's, {:.3f} mm from camera 1's"
+          .format(tick, len(spread), out['spread'], out['dist'][0], out['dist'][1]))
+    if len(drop):
+        after = [i for i in range(drop[-1] + 1, tick) if status[i][1] == 0]
+        out['back'] = after[0] if after else None
+        print("camera 1 covered in ticks {} .. {}; its track is followed again in tick {} (expected: {}, the tick after the last covered one)"
+              .format(drop[0], drop[-1], out['back'], drop[-1] + 1))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--dataset', choices=sorted(DATASETS), default='nyu')
@@ -71,6 +153,9 @@ def main(argv=None):
     ap.add_argument('--max-frames', type=int, default=None)
     ap.add_argument('--half-res-second', action='store_true', help='camera 1 at half resolution through a camera of its own')
     ap.add_argument('--overlapped', action='store_true', help='upload tick n + 1 under the plan of tick n (process_sequence)')
+    ap.add_argument('--fuse', action='store_true', help='one sequence through two cameras, the two tracks of its hand fused in the world frame')
+    ap.add_argument('--drop-second', default=None, metavar='A:B', help='with --fuse: camera 1 delivers all-zero frames in ticks A .. B - 1')
+    ap.add_argument('--max-dev', type=float, default=None, help='with --fuse: MultiTracker max_dev (mm)')
     ap.add_argument('--cache', default='./cache/')
     args = ap.parse_args(argv)
     Importer, seq_names, config = DATASETS[args.dataset]
@@ -81,6 +166,8 @@ def main(argv=None):
         raise SystemExit("no frames in one of %s" % (args.seqs or seq_names,))
     L, R = MultiStreamPipeline.HAND_LEFT, MultiStreamPipeline.HAND_RIGHT
     hands = [(0, L), (0, R), (1, L)]                                   # both hands of camera 0, one hand of camera 1
+    if args.fuse:
+        hands = [(0, L), (1, L)]                                       # ONE hand, seen by both cameras
     T = len(hands)
     J = args.joints or int(seqs[0].data[0].gt3Dorig.shape[0])
     if args.net == 'resnet':
@@ -91,6 +178,8 @@ def main(argv=None):
     comrefNetParams = ScaleNetParams(type=1, nChan=1, wIn=128, hIn=128, batchSize=T, resizeFactor=2, numJoints=1, nDims=3)
     comrefNetParams.loadFile = args.comref_net
     config = dict(config, cube=tuple(seqs[0].config['cube']))
+    if args.fuse:
+        return fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands)
     init = [seqs[d].data[0].gtorig[di.crop_joint_idx] for d, _ in hands]
     if args.seed == 'detect':
         init[2] = None                                                 # alone on its camera: found by the detector

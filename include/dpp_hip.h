@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 19
+#define DPP_ABI_VERSION 20
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -596,6 +596,49 @@ int dpp_crop_warp_ex_src(const float* frames, const void* records, int T, const 
                          int flags, float nd_value, float fill_value, float pad_value, float* out, dpp_stream_t stream);
 int dpp_pose_finish_src(const float* net_out, int T, int J, const int* src, const int* tflags, const void* sources, const float* cube,
                         const float* com3d, float* pose3d, float* pose_img, dpp_stream_t stream);
+
+/* ---- tracks of one hand across calibrated cameras (ABI v20; csrc/fuse.hip) --------------------------------------------------------------
+ * ONE launch at the end of MultiTracker's tick (hipdp/multitrack.py) that fuses the tracks which observe the same physical hand from
+ * different frame sources, and hands a track that lost the hand the centre its peers see.  The reference has no counterpart (one
+ * device, one camera): these semantics are THIS PROJECT'S OWN, restated in NumPy by tests/fuse_ref.py and pinned to it bit for bit.
+ * All arithmetic is float64 in the order given (no FMA contraction); every output is rounded to float32 once.
+ *   extrinsics [C][12] float64: R (3 x 3, row-major) then t (mm) of every source; w = R p + t takes a point of the source's camera
+ *              frame (the importer's jointImgTo3D frame, flip_y included: the frame of pose3d / com3d) to the common world frame.
+ *              Row i is ((R_i0 x + R_i1 y) + R_i2 z) + t_i.  The inverse p = R^T (w - t): d = w - t, row i (R_0i d0 + R_1i d1) + R_2i d2.
+ *   members / offsets [G + 1]: group g is the tracks members[offsets[g] .. offsets[g + 1]), in that (list) order; 1 to
+ *              DPP_FUSE_MAX_MEMBERS of them, groups disjoint, a group's members on pairwise distinct sources.  The host has validated
+ *              all of it (and R orthonormal, det > 0); the kernel trusts the arrays as it trusts src[].  Tracks in no group are not
+ *              touched: none of their outputs is written.
+ * Per group, one workgroup:
+ *   1. contributors: the members with status[m] == DPP_TRACK_OK; world centre W_m = R com3d[m] + t of the member's source.
+ *   2. consistency, only with max_dev > 0 (0: off).  n >= 3 contributors: the componentwise median of the W_m (even n: (a + b) / 2 of
+ *      the two middle values); a contributor with sqrt((dx^2 + dy^2) + dz^2) > max_dev from it is an OUTLIER and stops contributing
+ *      (all decided at once against the one median).  n == 2 farther apart than max_dev: both get DISAGREE and both still contribute.
+ *   3. over the remaining contributors (the inliers, n_out[g] of them) in list order, sums starting from 0.0:
+ *      fused_com [G][3] = sum of W_m / n; fused_pose [G][J][3] = sum of (R pose3d[m][j] + t) / n; spread [G][J] = the largest distance
+ *      of an inlier's world joint from the (unrounded) fused joint.  n == 0: all zeros.
+ *   4. peer_com [T][3], per member t: the mean world centre of the inliers OTHER than t (sum in list order / count), brought into t's
+ *      camera frame, rounded to float32, projected by t's own camera with joint3DToImg on a float32 array (as pose_finish does) ->
+ *      (u, v, z).  PEER_OK: such an inlier exists, z > 0 and the centre is not ill-defined (finite, |z| > 1e-8), 0 <= u < W and
+ *      0 <= v < H of t's source.  No such inlier: (0, 0, 0).
+ *   5. hand-over (flags & DPP_FUSE_HANDOVER): a member with PEER_OK whose status is DPP_TRACK_LOST, or which is an OUTLIER, gets
+ *      com[t] = peer_com[t] and HANDED.  No other centre is written; a gated member (DPP_TRACK_IDLE) is never rewritten.
+ *   6. fstat [T]: USED (an inlier) | OUTLIER | DISAGREE | PEER_OK | HANDED.
+ * sources: NULL (every source has the camera and the H x W of the launch scalars) or the ABI v19 table.  src, status [T] int32;
+ * pose3d [T][J][3], com3d [T][3], com [T][3] float32 (com is only written).
+ * DPP_E_BADARG (nothing launched): a NULL pointer (sources may be NULL), T / J / C / G below 1, G above T, max_dev negative or not
+ * finite, an unknown flag bit, and without a table H / W below 1 or a zero focal length. */
+#define DPP_FUSE_MAX_MEMBERS 16
+#define DPP_FUSE_USED 1
+#define DPP_FUSE_OUTLIER 2
+#define DPP_FUSE_DISAGREE 4
+#define DPP_FUSE_PEER_OK 8
+#define DPP_FUSE_HANDED 16
+#define DPP_FUSE_HANDOVER 1 /* launch flag */
+int dpp_pose_fuse(const float* pose3d, const float* com3d, const int* status, const int* src, int T, int J, const double* extrinsics, int C,
+                  const int* members, const int* offsets, int G, const void* sources, int H, int W, double fx, double fy, double ux, double uy,
+                  int flip_y, double max_dev, int flags, float* com, float* fused_pose, float* fused_com, float* spread, int* n_out,
+                  float* peer_com, int* fstat, dpp_stream_t stream);
 
 /* ---- whole-frame hand detection by connected components (ABI v14) -------------------------------------------------------------
  * What HandDetector.detect / estimateHandsize (handdetector.py:569-632, :911-937) take from cv2.findContours, restated with

@@ -23,6 +23,14 @@ Further legs, same protocol (a child process per leg, the legs alternating, 2 pr
                                480x640 sources of this tree, at T = C = 8: wall clock per tick and the plans' device time
   --sequence                   MultiTracker.process_sequence (uploads of tick n + 1 under the plan of tick n) against the process()
                                loop of this tree at T = C = 1, 8, 16
+  --fuse --parent DIR          the grouped tick (two groups of T / 2 tracks, identity extrinsics, max_dev 50 mm: one more launch,
+                               dpp_pose_fuse) at T = C = 8 against this tree's ungrouped tick and against the PARENT's tick.  Claims:
+                               the ungrouped tick is within the larger spread of the parent's; the grouped tick exceeds the ungrouped
+                               one by no more than the larger spread plus ONE launch's device time (the grouped plan's back-to-back
+                               device time over its launch count, from the same run).  And the recovery of a track that lost its hand:
+                               wall clock of the two ticks after the frames return by hand-over (tick: gated, restarted from its
+                               peers' centre; tick: followed) against the same two ticks through acquire(t, frame) (the detector
+                               plan) in the same process: the gap must exceed the larger spread.
 --configs 1x1,8x8 overrides a leg's (T, C) list.
 
 As in tools/track_bench.py the refinement net's last layer is zeroed, so every track stays on its seed whatever the random weights
@@ -146,6 +154,55 @@ def child(args):
                 out['mixed_device_ms_' + _key(T, C)] = device_time(mt.plan())
                 out['mixed_launches_' + _key(T, C)] = len(mt.plan().launches())
             assert not mt.lost.any()
+    elif args.leg == 'fuse':
+        from hipdp.multitrack import MultiTracker
+        eye = (np.eye(3), np.zeros(3))
+        for T, C in configs:
+            pnet, snet = nets(T)
+            tracks = [(t % C, bool(t // C)) for t in range(T)]
+            half = max(1, T // 2)
+            groups = [g for g in (list(range(half)), list(range(half, T))) if g]
+            mt = MultiTracker(rt, di, pnet, snet, 480, 640, cube, tracks, extrinsics=[eye] * C, groups=groups, max_dev=50.)
+            plain = MultiTracker(rt, di, pnet, snet, 480, 640, cube, tracks)
+            for t in range(T):
+                mt.reset(t, com0)
+                plain.reset(t, com0)
+
+            def tick(i):
+                assert all(r['status'] == 0 for r in mt.process(tick_frames(i, C)))
+            for i in range(10):
+                tick(i)
+            assert all(f['n'] == len(g) for f, g in zip(mt.fused, groups)) and len(mt.plan().launches()) == len(plain.plan().launches()) + 1
+            out['fuse_ms_' + _key(T, C)] = timed(tick)
+            out['fuse_device_ms_' + _key(T, C)] = device_time(mt.plan())
+            out['fuse_launches_' + _key(T, C)] = len(mt.plan().launches())
+            if T < 2:
+                continue
+            # recovery of track 0: the two ticks after the frames return, by hand-over and through the detector
+            n_rec = max(1, N // 10)
+
+            def recover(tr, acquire):
+                vals = []
+                for _ in range(reps):
+                    total = 0.0
+                    for i in range(n_rec):
+                        fr = tick_frames(i, C)
+                        tr.drop(0)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        if acquire:
+                            assert tr.acquire(0, fr[0])['found']
+                        first = tr.process(fr)
+                        second = tr.process(fr)
+                        torch.cuda.synchronize()
+                        total += time.perf_counter() - t0
+                        assert second[0]['status'] == 0 and first[0]['status'] == (0 if acquire else 1)
+                    vals.append(total / n_rec * 1e3)
+                return vals
+            recover(mt, False), recover(plain, True)
+            out['recover_handover_ms_' + _key(T, C)] = recover(mt, False)
+            out['recover_acquire_ms_' + _key(T, C)] = recover(plain, True)
+            assert not mt.lost.any() and not plain.lost.any() and mt._detectors == {}
     elif args.leg == 'yardstick':
         from hipdp.tracker import HandTracker
         pnet, snet = nets(1)
@@ -191,7 +248,8 @@ def main():
     ap.add_argument('--mixed', action='store_true', help='sources of unlike sizes and cameras against homogeneous ones')
     ap.add_argument('--sequence', action='store_true', help='process_sequence against the process() loop')
     ap.add_argument('--configs', default=None, help='T x C list of a leg, e.g. 1x1,8x8')
-    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence'], default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--fuse', action='store_true', help="the grouped tick against this tree's and the parent's ungrouped tick; recovery (needs --parent)")
+    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse'], default=None, help=argparse.SUPPRESS)
     ap.add_argument('--tree', default=ROOT, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.leg:
@@ -241,6 +299,40 @@ def main():
             d, dy = _stat(res['device_ms_' + k]), _stat(res['parent_device_ms_' + k])
             print("T = C = %d: this tree %.4f (%.4f), parent %.4f (%.4f); plan, device time: %.4f (%.4f), parent %.4f (%.4f)" % ((T,) + m + y + d + dy))
             ok = two_sided('T = C = %d' % T, m, y, 'this tree', 'the parent') and ok
+        return 0 if ok else 1
+    if args.fuse:
+        if not args.parent:
+            raise SystemExit("--fuse compares against --parent DIR")
+        cfgs = args.configs or '8x8'
+        res = run_legs([('multi', ytree, 'parent_'), ('multi', ROOT, ''), ('fuse', ROOT, '')], cfgs)
+        print("the grouped tick (two groups of T / 2 tracks fused by one more launch) against the ungrouped tick of this tree and of the parent "
+              "checkout; " + head)
+        print("all times in ms per tick: median (spread = max - min over the repetitions)")
+        ok = True
+        for c in cfgs.split(','):
+            T, C = (int(v) for v in c.split('x'))
+            k = _key(T, C)
+            f, m, y = _stat(res['fuse_ms_' + k]), _stat(res['multi_ms_' + k]), _stat(res['parent_multi_ms_' + k])
+            df, dm, dy = _stat(res['fuse_device_ms_' + k]), _stat(res['device_ms_' + k]), _stat(res['parent_device_ms_' + k])
+            nl = res['fuse_launches_' + k]
+            per = df[0] / nl
+            print("T = C = %d: grouped %.4f (%.4f), ungrouped %.4f (%.4f), parent %.4f (%.4f); plan, device time: grouped %.4f (%.4f), ungrouped "
+                  "%.4f (%.4f), parent %.4f (%.4f); launches %d / %d; device time per launch of the grouped plan %.2f us"
+                  % ((T,) + f + m + y + df + dm + dy + (nl, res['launches_' + k], per * 1e3)))
+            ok = two_sided('T = C = %d, nothing existing got slower' % T, m, y, 'the ungrouped tick', "the parent's tick") and ok
+            bar = max(f[1], m[1]) + per
+            fits = f[0] - m[0] <= bar
+            print("verdict T = C = %d, the grouped tick: %+.4f ms over the ungrouped one; larger spread %.4f ms + one launch %.4f ms = %.4f ms -> %s"
+                  % (T, f[0] - m[0], max(f[1], m[1]), per, bar, 'holds' if fits else 'DOES NOT hold'))
+            print("  plan device time, grouped - ungrouped: %+.2f us" % ((df[0] - dm[0]) * 1e3))
+            ok = fits and ok
+            if 'recover_handover_ms_' + k in res:
+                h, a = _stat(res['recover_handover_ms_' + k]), _stat(res['recover_acquire_ms_' + k])
+                gap = a[0] - h[0]
+                wins = gap > max(h[1], a[1])
+                print("recovery T = C = %d, the two ticks after the frames return: hand-over %.4f (%.4f), acquire + the same ticks %.4f (%.4f); gap "
+                      "%.4f ms, larger spread %.4f ms -> %s" % ((T,) + h + a + (gap, max(h[1], a[1]), 'holds' if wins else 'DOES NOT hold')))
+                ok = wins and ok
         return 0 if ok else 1
     if args.mixed:
         cfgs = args.configs or '8x8'
