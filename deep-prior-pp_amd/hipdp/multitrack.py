@@ -65,7 +65,7 @@ import numpy as np
 
 from . import ops
 from .augmenter import camera_tuple
-from .tracker import IDLE, LOST, OK, _engine, refine_stage
+from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, refine_stage, track_fields, valid_centre
 
 
 class MultiTracker(object):
@@ -73,7 +73,7 @@ class MultiTracker(object):
                  sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True):
         """
         :param importer:   the dataset importer (the camera) of all sources, or a sequence of C importers, one per source
-        :param poseNet, comrefNet: as for HandTracker, but built for a batch of len(tracks): row t is track t
+        :param poseNet, comrefNet: as for HandTracker, but built for a batch of T, the number of tracks: row t is track t
         :param H, W:       frame size of all sources, or sequences of C ints
         :param cube:       metric cube (mm) every track starts with (set_cube(t, cube) changes one)
         :param tracks:     list of (source, hand_right): track t follows one hand in the frames of source `source`
@@ -92,9 +92,10 @@ class MultiTracker(object):
         tracks = [(int(s), bool(r)) for s, r in tracks]
         if not tracks:
             raise ValueError("MultiTracker needs at least one track")
-        self.T = T = len(tracks)
-        self.C = C = int(max(s for s, _ in tracks) + 1 if sources is None else sources)
-        self.src_host = ops.track_index([s for s, _ in tracks], C)           # the kernels trust it: checked here
+        srcs = [s for s, _ in tracks]
+        self.T = T = len(srcs)
+        self.C = C = int(max(srcs) + 1 if sources is None else sources)
+        self.src_host = ops.track_index(srcs, C)                             # the kernels trust it: checked here
         if C > T:
             raise ValueError("%d sources for %d tracks: every source needs a track that reads it" % (C, T))
         if groups is not None and extrinsics is None:
@@ -122,7 +123,6 @@ class MultiTracker(object):
             raise ValueError("the pose net takes one crop and regresses J x 3 coordinates")
         self.rs, self.ds, self.J = int(self.ceng.x_ins[0].shape[1]), int(self.peng.x_in.shape[1]), self.peng.out_dim // 3
         f32, i32 = np.float32, np.int32
-        J3 = self.J * 3
         self.sensor = None if sensor is None else ops.sensor_spec(sensor)
         if self.hetero:                                                            # ragged buffers; _slice(buf, c) is source c's frame
             self.table = ops.SourceTable(rt, self.cams, list(zip(self.fxs, self.fys)), self.sizes,
@@ -142,27 +142,22 @@ class MultiTracker(object):
         ix = rt.alloc((3, T), i32)                                                 # src, gate (all zero: nobody has started), tflags
         self.src, self.gate, self.tflags = ix.view(0, (T,)), ix.view(T, (T,)), ix.view(2 * T, (T,))
         self.src.set(self.src_host)
-        # everything the host reads per tick is ONE block, every entry an array over the tracks (the launches write [T][...] arrays):
-        # pose (mm), pose in image coordinates, centres (= the state), com3D, M, status (+ one detector's 8 words: acquire)
-        self._off = off = dict(pose=0, pose_img=T * J3, com=2 * T * J3, com3D=2 * T * J3 + 3 * T, M=2 * T * J3 + 6 * T,
-                               status=2 * T * J3 + 15 * T, det=2 * T * J3 + 16 * T)
-        n_res = off['det'] + 8
+        self.trackset = ops.TrackSet(T, self.src, self.gate, self.tflags, self.table)    # what the plan's launches know about their rows
+        # everything the host reads per tick is ONE block, every entry an array over the tracks (the launches write [T][...] arrays)
+        fields = track_fields(T, self.J)
         self.rig = None if groups is None else ops.FuseRig(rt, extrinsics, groups, self.src_host, C)   # validated there, uploaded once
         if self.rig is not None:                                                   # the fused arrays follow: every offset above keeps its value
             G = self.rig.G
-            off.update(fused_pose=n_res, fused_com=n_res + G * J3, spread=n_res + G * J3 + 3 * G, n=n_res + G * J3 + 3 * G + G * self.J)
-            off.update(peer_com=off['n'] + G, fstat=off['n'] + G + 3 * T)
-            n_res = off['fstat'] + T
-        self.res = rt.alloc(n_res, f32)
+            fields += [('fused_pose', (G, self.J, 3), f32), ('fused_com', (G, 3), f32), ('spread', (G, self.J), f32), ('n', (G,), i32),
+                       ('peer_com', (T, 3), f32), ('fstat', (T,), i32)]
+        self.block = blk = ResultBlock(rt, fields)
+        self.res, self._off = blk.buf, blk.offsets
         self.fused = []
         if self.rig is not None:
-            G = self.rig.G
-            self.fused_pose, self.fused_com = self.res.view(off['fused_pose'], (G, self.J, 3)), self.res.view(off['fused_com'], (G, 3))
-            self.spread, self.fused_n = self.res.view(off['spread'], (G, self.J)), self.res.view(off['n'], (G,), i32)
-            self.peer_com, self.fstat = self.res.view(off['peer_com'], (T, 3)), self.res.view(off['fstat'], (T,), i32)
-        self.pose3d, self.pose_img = self.res.view(off['pose'], (T, self.J, 3)), self.res.view(off['pose_img'], (T, self.J, 3))
-        self.com, self.com3d = self.res.view(off['com'], (T, 3)), self.res.view(off['com3D'], (T, 3))
-        self.M, self.status = self.res.view(off['M'], (T, 9)), self.res.view(off['status'], (T,), i32)
+            self.fused_pose, self.fused_com, self.spread = blk.view('fused_pose'), blk.view('fused_com'), blk.view('spread')
+            self.fused_n, self.peer_com, self.fstat = blk.view('n'), blk.view('peer_com'), blk.view('fstat')
+        self.pose3d, self.pose_img, self.com, self.com3d = blk.view('pose'), blk.view('pose_img'), blk.view('com'), blk.view('com3D')
+        self.M, self.status = blk.view('M'), blk.view('status')
         self.crop = self.peng.x_in.buf.reshape(T, self.ds, self.ds)             # the pose net's input IS the final crops
         self.flags_host = np.zeros(T, i32)
         self.flags_host[:] = (ops.POSE_INV_X if invX else 0) | (ops.POSE_INV_Y if invY else 0)
@@ -216,7 +211,7 @@ class MultiTracker(object):
         """Start track t (again) from the centre `com` (image coordinates of its source, z in mm)."""
         t = self._track(t)
         com = np.asarray(com, np.float32).reshape(3)
-        if not np.all(np.isfinite(com)) or np.isclose(com[2], 0.):
+        if not valid_centre(com):
             raise ValueError("reset needs a centre with a depth: %r" % (com,))
         self.com.view(3 * t, (1, 3)).set(com)
         self.com_host[t] = com
@@ -252,8 +247,7 @@ class MultiTracker(object):
             self._detectors[t] = FrameDetector(
                 self.rt, H, W, self.fxs[c], self.fys[c], 1, frames=self._slice(self.frames, c),
                 partial=self.partial.view(c * self._pstride, (self._pstride,)), com=self.com.view(3 * t, (1, 3)),
-                cube=self.cube.view(3 * t, (1, 3)), res=self.res.view(self._off['det'], (8,)),
-                sensor=None if self.sensor is None else dict(zip(('dtype', 'median', 'mirror'), self.sensor)),
+                cube=self.cube.view(3 * t, (1, 3)), res=self.block.view('det'), sensor=self.sensor,
                 raw=None if self.sensor is None else self._slice(self.raw, c, raw=True))
         return self._detectors[t]
 
@@ -269,9 +263,9 @@ class MultiTracker(object):
         self._input(c).set(frame)
         det.plan(do_hand_size).run(self.rt)
         self.rt.synchronize()
-        res, o = self.res.get(), self._off
-        coms, cubes, found, _, _ = det.parse(res[o['det']:], res[o['com'] + 3 * t:o['com'] + 3 * t + 3], None if do_hand_size else self.cube_host[t])
-        ok = bool(found[0]) and bool(np.all(np.isfinite(coms[0]))) and not np.isclose(coms[0][2], 0.)
+        res = self.block.split(self.res.get())
+        coms, cubes, found, _, _ = det.parse(res['det'], res['com'][t], None if do_hand_size else self.cube_host[t])
+        ok = bool(found[0]) and valid_centre(coms[0])
         self.lost[t] = not ok
         self.com_host[t] = coms[0]
         return dict(com=coms[0], cube=cubes[0], found=ok)
@@ -292,8 +286,7 @@ class MultiTracker(object):
             (H, W) = self.sizes[c]
             self._detectors[key] = FrameDetector(
                 self.rt, H, W, self.fxs[c], self.fys[c], 1, frames=self._slice(self.frames, c),
-                partial=self.partial.view(c * self._pstride, (self._pstride,)), cube=self.cube.view(3 * ts[0], (1, 3)),
-                sensor=None if self.sensor is None else dict(zip(('dtype', 'median', 'mirror'), self.sensor)),
+                partial=self.partial.view(c * self._pstride, (self._pstride,)), cube=self.cube.view(3 * ts[0], (1, 3)), sensor=self.sensor,
                 raw=None if self.sensor is None else self._slice(self.raw, c, raw=True), hands=len(ts), max_extent=max_extent)
         return self._detectors[key], ts
 
@@ -323,7 +316,7 @@ class MultiTracker(object):
         self.rt.synchronize()
         coms, _, found = det.parse(det.res.get(), None, self.cube_host[ts[0]])[:3]
         coms, found = coms[0], found[0]
-        ok = [bool(found[k]) and bool(np.all(np.isfinite(coms[k]))) and not np.isclose(coms[k][2], 0.) for k in range(len(ts))]
+        ok = [bool(found[k]) and valid_centre(coms[k]) for k in range(len(ts))]
         free = [k for k in range(len(ts)) if ok[k]]
         out = {}
         followed = [t for t in ts if not self.lost[t]]
@@ -359,6 +352,7 @@ class MultiTracker(object):
                 self._inputs2 = self.rt.alloc((self.C, self.H, self.W), np.float32 if self.sensor is None else self.sensor[0])
             self._gate2 = self.rt.alloc((self.T,), np.int32)
             self._gate2_host = np.zeros(self.T, np.int32)
+            self._trackset2 = ops.TrackSet(self.T, self.src, self._gate2, self.tflags, self.table)
 
     def plan(self, slot=0):
         """The plan of one tick on input set `slot` (1: process_sequence's second set; without a sensor the second set IS a second
@@ -367,72 +361,50 @@ class MultiTracker(object):
             rt, H, W, T, C = self.rt, self.H, self.W, self.T, self.C
             if slot:
                 self._second_set()
-            gate = self._gate2 if slot else self.gate
+            tracks = self._trackset2 if slot else self.trackset           # the slot's own gates; with a table H, W, cam, fx, fy go unread
             fr = self._inputs2 if slot and self.sensor is None else self.frames
             raw = self._inputs2 if slot else self.raw
-            tab = self.table
             p = ops.Plan('multitrack')
             if self.sensor is None:
-                p.add(ops.frame_range(rt, fr, C, H, W, self.partial) if tab is None else ops.frame_range_src(rt, fr, tab, self.partial))
-            elif tab is None:
-                p.add(ops.frame_ingest(rt, raw, C, H, W, fr, self.partial, median=self.sensor[1], mirror=self.sensor[2]))
+                p.add(ops.frame_range(rt, fr, C, H, W, self.partial, table=self.table))
             else:
-                p.add(ops.frame_ingest_src(rt, raw, tab, fr, self.partial, median=self.sensor[1], mirror=self.sensor[2]))
+                p.add(ops.frame_ingest(rt, raw, C, H, W, fr, self.partial, median=self.sensor[1], mirror=self.sensor[2], table=self.table))
             # the T centres are read (prepare, track_refine) and then rewritten by one lane per track of track_refine: in place
-            tracks = (T, self.src, gate) if tab is None else (T, self.src, gate, tab)
             for op, side in refine_stage(rt, fr, H, W, self.partial, self.rec, self.com, self.cube, self.ceng, self.cam, self.fx, self.fy,
                                          self.ds, self.com, self.com3d, self.rec, self.status, self.M, tracks=tracks):
                 p.add(op, side)
-            if tab is None:
-                p.add(ops.crop_warp_ex_ix(rt, fr, self.rec, T, self.src, self.tflags, H, W, self.ds, self.crop, flags=ops.CROP_NORMALIZE,
-                                          nd_value=0.0, name='track_crop'))
-            else:
-                p.add(ops.crop_warp_ex_src(rt, fr, self.rec, T, self.src, self.tflags, tab, self.ds, self.crop, flags=ops.CROP_NORMALIZE,
-                                           nd_value=0.0, name='track_crop'))
+            p.add(ops.crop_warp_ex(rt, fr, self.rec, T, H, W, self.ds, self.crop, flags=ops.CROP_NORMALIZE, nd_value=0.0, name='track_crop',
+                                   tracks=tracks))
             for op, side in self.peng.fwd.ops:
                 p.add(op, side)
-            if tab is None:
-                p.add(ops.pose_finish_ix(rt, self.peng.out.buf, T, self.J, self.tflags, self.cube, self.com3d, self.cam, self.pose3d,
-                                         self.pose_img))
-            else:
-                p.add(ops.pose_finish_src(rt, self.peng.out.buf, T, self.J, self.src, self.tflags, tab, self.cube, self.com3d, self.pose3d,
-                                          self.pose_img))
+            p.add(ops.pose_finish(rt, self.peng.out.buf, T, self.J, self.cube, self.com3d, self.cam, None, self.pose3d, self.pose_img,
+                                  tracks=tracks))
             if self.rig is not None:                    # the last launch of the main lane: the next tick's prepare is ordered behind it
-                p.add(ops.pose_fuse(rt, self.pose3d, self.com3d, self.status, self.src, T, self.J, self.rig, tab, H, W, self.cam, self.max_dev,
-                                    self.handover, self.com, self.fused_pose, self.fused_com, self.spread, self.fused_n, self.peer_com,
-                                    self.fstat))
+                p.add(ops.pose_fuse(rt, self.pose3d, self.com3d, self.status, self.src, T, self.J, self.rig, self.table, H, W, self.cam,
+                                    self.max_dev, self.handover, self.com, self.fused_pose, self.fused_com, self.spread, self.fused_n,
+                                    self.peer_com, self.fstat))
             self._plans[slot] = p
         return self._plans[slot]
 
     def _frame(self, frame, c=0):
         """`frame` checked against the size of source c (ITS source) and the sensor's dtype."""
-        if self.sensor is None:
-            frame = np.asarray(frame, np.float32)
-        else:                                       # a raw frame is taken as it is or not at all: no silent conversion
-            frame = np.asarray(frame)
-            if frame.dtype != self.sensor[0]:
-                raise ValueError("frame dtype %s, the tracker's sensor delivers %s" % (frame.dtype, self.sensor[0]))
-        if frame.shape != self.sizes[c]:
-            raise ValueError("frame shape %s, source %d delivers %s" % (frame.shape, c, self.sizes[c]))
-        return frame
+        return check_frame(frame, self.sensor, self.sizes[c], 'source %d delivers' % c)
+
+    def _gates(self, fresh):
+        """The tick's gate vector: a track takes part when the host does not know it lost and its source has a fresh frame."""
+        return np.array([int(not self.lost[t] and fresh[self.src_host[t]] is not None) for t in range(self.T)], np.int32)
 
     def _results(self, res, gate, crops=None):
-        o, T, J = self._off, self.T, self.J
-        st = res[o['status']:o['status'] + T].view(np.int32)
-        pose, pimg = res[:o['pose_img']].reshape(T, J, 3), res[o['pose_img']:o['com']].reshape(T, J, 3)
-        com, com3d = res[o['com']:o['com3D']].reshape(T, 3), res[o['com3D']:o['M']].reshape(T, 3)
-        M = res[o['M']:o['status']].reshape(T, 3, 3)
+        f = self.block.split(res)
+        st, pose, pimg, com, com3d, M = f['status'], f['pose'], f['pose_img'], f['com'], f['com3D'], f['M']
         self.com_host[:] = com
         rig = self.rig
         if rig is not None:
-            G = rig.G
-            fstat, peer = res[o['fstat']:o['fstat'] + T].view(np.int32), res[o['peer_com']:o['fstat']].reshape(T, 3)
-            fpose, fcom = res[o['fused_pose']:o['fused_com']].reshape(G, J, 3), res[o['fused_com']:o['spread']].reshape(G, 3)
-            spread, fn = res[o['spread']:o['n']].reshape(G, J), res[o['n']:o['peer_com']].view(np.int32)
-            self.fused = [dict(pose=fpose[g], com=fcom[g], spread=spread[g], n=int(fn[g])) for g in range(G)]
+            fstat, peer = f['fstat'], f['peer_com']
+            self.fused = [dict(pose=f['fused_pose'][g], com=f['fused_com'][g], spread=f['spread'][g], n=int(f['n'][g])) for g in range(rig.G)]
             self._peer_ok = (fstat & ops.FUSE_PEER_OK) != 0
         out = []
-        for t in range(T):
+        for t in range(self.T):
             status = int(st[t])
             grouped = rig is not None and rig.group_of[t] >= 0
             handed = grouped and bool(fstat[t] & ops.FUSE_HANDED)
@@ -460,7 +432,7 @@ class MultiTracker(object):
         if len(frames) != self.C:
             raise ValueError("%d frames for %d sources" % (len(frames), self.C))
         fresh = [None if f is None else self._frame(f, c) for c, f in enumerate(frames)]
-        gate = np.array([int(not self.lost[t] and fresh[self.src_host[t]] is not None) for t in range(self.T)], np.int32)
+        gate = self._gates(fresh)
         for c, f in enumerate(fresh):
             if f is not None:
                 self._input(c).set(f)
@@ -514,7 +486,7 @@ class MultiTracker(object):
             fresh = [None if f is None else self._frame(f, c) for c, f in enumerate(frames)]
             k = n & 1
             # self.lost is what the host knows: the results up to tick n - 2
-            gate = np.array([int(not self.lost[t] and fresh[self.src_host[t]] is not None) for t in range(self.T)], np.int32)
+            gate = self._gates(fresh)
             events = []
             for c, f in enumerate(fresh):
                 if f is not None:
@@ -538,7 +510,7 @@ class MultiTracker(object):
                 resolve(pending)
             pending = handle
             # the gates a process() loop would have used for this tick: it knows tick n - 1's losses already
-            last = np.array([int(not self.lost[t] and fresh[self.src_host[t]] is not None) for t in range(self.T)], np.int32)
+            last = self._gates(fresh)
         if pending is not None:
             resolve(pending)
         rt.synchronize()

@@ -691,20 +691,43 @@ def crop_com(rt, frames, records, B, H, W, com_out, name='crop_com'):
                   kernels=2)
 
 
-def crop_warp(rt, frames, records, B, H, W, dsz, out, normalize=True, nd_value=0.0, name='crop_warp'):
-    return Launch(rt.lib.dpp_crop_warp, (frames.ptr, records.ptr, B, H, W, dsz, int(bool(normalize)), float(nd_value), out.ptr),
-                  (frames, records, out), name, dict(kernel='crop_warp', flops=10.0 * B * dsz * dsz, bytes=8.0 * B * dsz * dsz))
+# The launches that take `tracks=` (and frame_range / frame_ingest, which take `table=`) are ONE op over a family of C entry points
+# (include/dpp_hip.h): without a TrackSet the plain symbol on B frames; with one (below) the *_ix symbol on tracks.T rows, row t in
+# frame src[t] (B is not read); with one that has a SourceTable the *_src symbol, which reads the frame size, the camera and fx / fy
+# per source from the table (H, W, cam, fx, fy are not read: pass None).
+def crop_warp(rt, frames, records, B, H, W, dsz, out, normalize=True, nd_value=0.0, name='crop_warp', tracks=None):
+    tail = (dsz, int(bool(normalize)), float(nd_value), out.ptr)
+    if tracks is None:
+        fn, args, keep = rt.lib.dpp_crop_warp, (frames.ptr, records.ptr, B, H, W) + tail, (frames, records, out)
+    elif tracks.table is None:
+        B = tracks.T
+        fn, args, keep = rt.lib.dpp_crop_warp_ix, (frames.ptr, records.ptr, B, tracks.src.ptr, H, W) + tail, (frames, records, tracks.src, out)
+    else:
+        B, tab = tracks.T, tracks.table.dev
+        fn, args, keep = rt.lib.dpp_crop_warp_src, (frames.ptr, records.ptr, B, tracks.src.ptr, tab.ptr) + tail, (frames, records, tracks.src, tab, out)
+    return Launch(fn, args, keep, name, dict(kernel='crop_warp', flops=10.0 * B * dsz * dsz, bytes=8.0 * B * dsz * dsz))
 
 
 CROP_NORMALIZE, CROP_BILINEAR, CROP_NO_RANGE, CROP_NO_THRESH, CROP_FLIP_X = 1, 2, 4, 8, 16      # dpp_crop_warp_ex flags
 
 
-def crop_warp_ex(rt, frames, records, B, H, W, dsz, out, flags=0, nd_value=0.0, fill_value=None, pad_value=0.0, name='crop_warp_ex'):
-    """dpp_crop_warp_ex: the initial crop with the bilinear mode and applyCrop3D's options (fill_value defaults to nd_value)."""
+def crop_warp_ex(rt, frames, records, B, H, W, dsz, out, flags=0, nd_value=0.0, fill_value=None, pad_value=0.0, name='crop_warp_ex',
+                 tracks=None):
+    """dpp_crop_warp_ex: the initial crop with the bilinear mode and applyCrop3D's options (fill_value defaults to nd_value).  With
+    tracks, CROP_FLIP_X comes per track from tflags[t] & POSE_HAND_RIGHT, the other flags hold for all tracks."""
     fill = float(nd_value) if fill_value is None else float(fill_value)
     taps = 4 if flags & CROP_BILINEAR else 1
-    return Launch(rt.lib.dpp_crop_warp_ex, (frames.ptr, records.ptr, B, H, W, dsz, int(flags), float(nd_value), fill, float(pad_value), out.ptr),
-                  (frames, records, out), name,
+    tail = (dsz, int(flags), float(nd_value), fill, float(pad_value), out.ptr)
+    if tracks is None:
+        fn, args, keep = rt.lib.dpp_crop_warp_ex, (frames.ptr, records.ptr, B, H, W) + tail, (frames, records, out)
+    elif tracks.table is None:
+        B, src, tf = tracks.T, tracks.src, tracks.tflags
+        fn, args, keep = rt.lib.dpp_crop_warp_ex_ix, (frames.ptr, records.ptr, B, src.ptr, tf.ptr, H, W) + tail, (frames, records, src, tf, out)
+    else:
+        B, src, tf, tab = tracks.T, tracks.src, tracks.tflags, tracks.table.dev
+        fn, args = rt.lib.dpp_crop_warp_ex_src, (frames.ptr, records.ptr, B, src.ptr, tf.ptr, tab.ptr) + tail
+        keep = (frames, records, src, tf, tab, out)
+    return Launch(fn, args, keep, name,
                   dict(kernel='crop_warp', flops=(30.0 if taps == 4 else 10.0) * B * dsz * dsz, bytes=(4.0 * taps + 4.0) * B * dsz * dsz))
 
 
@@ -744,10 +767,14 @@ def frame_range_workspace(rt, B):
     return rt.alloc(max(1, int(rt.lib.dpp_frame_range_bytes(B)) // 4), np.float32, zero=False)
 
 
-def frame_range(rt, frames, B, H, W, partial, name='frame_range'):
-    """dpp_frame_range: the depth range of every frame, many workgroups per frame -- the ONE pass over the whole frame of a tracked frame."""
-    return Launch(rt.lib.dpp_frame_range, (frames.ptr, B, H, W, partial.ptr), (frames, partial), name,
-                  dict(kernel='frame_range', flops=2.0 * B * H * W, bytes=4.0 * B * H * W))
+def frame_range(rt, frames, B, H, W, partial, name='frame_range', table=None):
+    """dpp_frame_range: the depth range of every frame, many workgroups per frame -- the ONE pass over the whole frame of a tracked frame.
+    table (a SourceTable): dpp_frame_range_src on the ragged buffer of the table's sources; B, H, W are not read."""
+    if table is None:
+        fn, args, keep, npx = rt.lib.dpp_frame_range, (frames.ptr, B, H, W, partial.ptr), (frames, partial), float(B) * H * W
+    else:
+        fn, args, keep, npx = rt.lib.dpp_frame_range_src, (frames.ptr, table.dev.ptr, table.C, partial.ptr), (frames, table.dev, partial), table.npx
+    return Launch(fn, args, keep, name, dict(kernel='frame_range', flops=2.0 * npx, bytes=4.0 * npx))
 
 
 INGEST_U16, INGEST_F32 = 1, 2                 # DPP_INGEST_*: source types of dpp_frame_ingest
@@ -756,7 +783,10 @@ INGEST_TYPES = {'uint16': INGEST_U16, 'float32': INGEST_F32}
 
 
 def sensor_spec(sensor):
-    """A sensor description dict(dtype='uint16' | 'float32', median=bool, mirror=bool) checked and normalised to (numpy dtype, median, mirror)."""
+    """A sensor description dict(dtype='uint16' | 'float32', median=bool, mirror=bool) checked and normalised to (numpy dtype, median,
+    mirror); such a tuple (a tracker hands its own to its detectors) passes through."""
+    if isinstance(sensor, tuple):
+        return sensor
     unknown = set(sensor) - {'dtype', 'median', 'mirror'}
     if unknown:
         raise ValueError("unknown sensor options: %s" % sorted(unknown))
@@ -766,44 +796,72 @@ def sensor_spec(sensor):
     return dt, bool(sensor.get('median', False)), bool(sensor.get('mirror', False))
 
 
-def frame_ingest(rt, raw, B, H, W, frames, partial, median=False, mirror=False, name='frame_ingest'):
+def frame_ingest(rt, raw, B, H, W, frames, partial, median=False, mirror=False, name='frame_ingest', table=None):
     """dpp_frame_ingest: raw sensor frames (uint16 or float32, by raw.dtype) -> float32 frames, optionally mirrored and 3x3-median
-    filtered, and frame_range's partials of the result (partial may be None) -- in a plan it stands where frame_range stood."""
+    filtered, and frame_range's partials of the result (partial may be None) -- in a plan it stands where frame_range stood.
+    table (a SourceTable): dpp_frame_ingest_src on the ragged buffers of the table's sources; B, H, W are not read."""
     if raw.dtype.name not in INGEST_TYPES:
         raise ValueError("frame_ingest reads uint16 or float32 frames, not %s" % raw.dtype.name)
     flags = (INGEST_MEDIAN3 if median else 0) | (INGEST_MIRROR_X if mirror else 0)
-    npx = float(B) * H * W
+    head, tail = (raw.ptr, INGEST_TYPES[raw.dtype.name]), (flags, frames.ptr, _p(partial))
+    if table is None:
+        fn, args, keep, npx = rt.lib.dpp_frame_ingest, head + (B, H, W) + tail, (raw, frames, partial), float(B) * H * W
+    else:
+        fn, args, keep, npx = rt.lib.dpp_frame_ingest_src, head + (table.dev.ptr, table.C) + tail, (raw, table.dev, frames, partial), table.npx
     # a median output takes 8 compare-exchanges' worth of its columns' sorts (shared by three outputs) + 12 of its own; min / max: 2
-    return Launch(rt.lib.dpp_frame_ingest, (raw.ptr, INGEST_TYPES[raw.dtype.name], B, H, W, flags, frames.ptr, _p(partial)), (raw, frames, partial),
-                  name, dict(kernel='frame_ingest', flops=(22.0 if median else 2.0) * npx, bytes=(raw.dtype.itemsize + 4.0) * npx))
+    return Launch(fn, args, keep, name, dict(kernel='frame_ingest', flops=(22.0 if median else 2.0) * npx, bytes=(raw.dtype.itemsize + 4.0) * npx))
 
 
-def crop_prepare_ranged(rt, partial, B, com, cube, fx, fy, dsz, records, M_out=None, stretch=False, name='crop_prepare_ranged'):
+def crop_prepare_ranged(rt, partial, B, com, cube, fx, fy, dsz, records, M_out=None, stretch=False, name='crop_prepare_ranged', tracks=None):
     """dpp_crop_prepare_ranged: crop_prepare's records from frame_range's partials (no pass over the frame)."""
-    return Launch(rt.lib.dpp_crop_prepare_ranged, (partial.ptr, B, com.ptr, cube.ptr, float(fx), float(fy), dsz, int(bool(stretch)), records.ptr,
-                                                   _p(M_out)),
-                  (partial, com, cube, records, M_out), name)
+    tail = (dsz, int(bool(stretch)), records.ptr, _p(M_out))
+    if tracks is None:
+        fn, args, keep = rt.lib.dpp_crop_prepare_ranged, (partial.ptr, B, com.ptr, cube.ptr, float(fx), float(fy)) + tail, (partial,)
+    elif tracks.table is None:
+        fn, keep = rt.lib.dpp_crop_prepare_ranged_ix, (partial, tracks.src, tracks.gate)
+        args = (partial.ptr, tracks.T, tracks.src.ptr, tracks.gate.ptr, com.ptr, cube.ptr, float(fx), float(fy)) + tail
+    else:
+        fn, keep = rt.lib.dpp_crop_prepare_ranged_src, (partial, tracks.src, tracks.gate, tracks.table.dev)
+        args = (partial.ptr, tracks.T, tracks.src.ptr, tracks.gate.ptr, tracks.table.dev.ptr, com.ptr, cube.ptr) + tail
+    return Launch(fn, args, keep + (com, cube, records, M_out), name)
 
 
 def track_refine(rt, frames, records_in, B, H, W, com_in, cube, net_out, cam, crop_fx, crop_fy, dsz, com_out, com3d_out, records_out, status,
-                 M_out=None, name='track_refine'):
+                 M_out=None, name='track_refine', tracks=None):
     """dpp_track_refine: the tracked centre from the refinement net's output, fused with the prepare of the final crop around it."""
-    fx, fy, ux, uy, flip = cam
-    return Launch(rt.lib.dpp_track_refine,
-                  (frames.ptr, records_in.ptr, B, H, W, com_in.ptr, cube.ptr, net_out.ptr, float(fx), float(fy), float(ux), float(uy), int(flip),
-                   float(crop_fx), float(crop_fy), dsz, com_out.ptr, com3d_out.ptr, records_out.ptr, _p(M_out), status.ptr),
-                  (frames, records_in, com_in, cube, net_out, com_out, com3d_out, records_out, M_out, status), name)
+    nets, tail = (com_in.ptr, cube.ptr, net_out.ptr), (dsz, com_out.ptr, com3d_out.ptr, records_out.ptr, _p(M_out), status.ptr)
+    if tracks is None or tracks.table is None:
+        fx, fy, ux, uy, flip = cam
+        cams = (float(fx), float(fy), float(ux), float(uy), int(flip), float(crop_fx), float(crop_fy))
+    if tracks is None:
+        fn, args, keep = rt.lib.dpp_track_refine, (frames.ptr, records_in.ptr, B, H, W) + nets + cams + tail, (frames, records_in)
+    elif tracks.table is None:
+        fn, keep = rt.lib.dpp_track_refine_ix, (frames, records_in, tracks.src, tracks.gate)
+        args = (frames.ptr, records_in.ptr, tracks.T, tracks.src.ptr, tracks.gate.ptr, H, W) + nets + cams + tail
+    else:
+        fn, keep = rt.lib.dpp_track_refine_src, (frames, records_in, tracks.src, tracks.gate, tracks.table.dev)
+        args = (frames.ptr, records_in.ptr, tracks.T, tracks.src.ptr, tracks.gate.ptr, tracks.table.dev.ptr) + nets + tail
+    return Launch(fn, args, keep + (com_in, cube, net_out, com_out, com3d_out, records_out, M_out, status), name)
 
 
 POSE_HAND_RIGHT, POSE_INV_X, POSE_INV_Y = 1, 2, 4      # dpp_pose_finish flags
 
 
-def pose_finish(rt, net_out, B, J, cube, com3d, cam, flags, pose3d, pose_img, name='pose_finish'):
-    """dpp_pose_finish: estimatePose's sign rules, pose * cube_z / 2 + com3D and joints3DToImg of the result."""
-    fx, fy, ux, uy, flip = cam
-    return Launch(rt.lib.dpp_pose_finish, (net_out.ptr, B, J, cube.ptr, com3d.ptr, float(fx), float(fy), float(ux), float(uy), int(flip), int(flags),
-                                           pose3d.ptr, pose_img.ptr),
-                  (net_out, cube, com3d, pose3d, pose_img), name)
+def pose_finish(rt, net_out, B, J, cube, com3d, cam, flags, pose3d, pose_img, name='pose_finish', tracks=None):
+    """dpp_pose_finish: estimatePose's sign rules, pose * cube_z / 2 + com3D and joints3DToImg of the result.  With tracks the sign
+    rules come per track from tflags[t] and `flags` is not read."""
+    if tracks is None or tracks.table is None:
+        fx, fy, ux, uy, flip = cam
+        cams = (float(fx), float(fy), float(ux), float(uy), int(flip))
+    if tracks is None:
+        fn, args, keep = rt.lib.dpp_pose_finish, (net_out.ptr, B, J, cube.ptr, com3d.ptr) + cams + (int(flags), pose3d.ptr, pose_img.ptr), (net_out,)
+    elif tracks.table is None:
+        fn, keep = rt.lib.dpp_pose_finish_ix, (net_out, tracks.tflags)
+        args = (net_out.ptr, tracks.T, J, tracks.tflags.ptr, cube.ptr, com3d.ptr) + cams + (pose3d.ptr, pose_img.ptr)
+    else:
+        fn, keep = rt.lib.dpp_pose_finish_src, (net_out, tracks.src, tracks.tflags, tracks.table.dev)
+        args = (net_out.ptr, tracks.T, J, tracks.src.ptr, tracks.tflags.ptr, tracks.table.dev.ptr, cube.ptr, com3d.ptr, pose3d.ptr, pose_img.ptr)
+    return Launch(fn, args, keep + (cube, com3d, pose3d, pose_img), name)
 
 
 TRACK_OK, TRACK_LOST, TRACK_IDLE = 0, 1, 2           # DPP_TRACK_*: dpp_track_refine's status word
@@ -817,44 +875,18 @@ def track_index(src, C):
     return src
 
 
-# The five tracking launches for T tracks over C frames: src / gate / tflags are int32 device arrays with one entry per track
-# (include/dpp_hip.h, ABI v16).  The caller has checked `src` with track_index before uploading it.
-def crop_prepare_ranged_ix(rt, partial, T, src, gate, com, cube, fx, fy, dsz, records, M_out=None, stretch=False, name='crop_prepare_ranged'):
-    return Launch(rt.lib.dpp_crop_prepare_ranged_ix, (partial.ptr, T, src.ptr, gate.ptr, com.ptr, cube.ptr, float(fx), float(fy), dsz,
-                                                      int(bool(stretch)), records.ptr, _p(M_out)),
-                  (partial, src, gate, com, cube, records, M_out), name)
+class TrackSet(object):
+    """What a tracking launch knows about its rows (include/dpp_hip.h, ABI v16 / v19): T tracks; `src`, `gate`, `tflags`, int32 device
+    arrays with one entry per track (frame source, takes part in this tick, POSE_* flags; the caller has checked `src` with track_index
+    before uploading it -- a launch reads the ones its C entry point takes, a caller of single launches may leave the others out); `table`,
+    the SourceTable of sources with cameras and frame sizes of their own, or None: one camera and one size, given as launch arguments."""
+    __slots__ = ('T', 'src', 'gate', 'tflags', 'table')
 
-
-def crop_warp_ix(rt, frames, records, T, src, H, W, dsz, out, normalize=True, nd_value=0.0, name='crop_warp'):
-    return Launch(rt.lib.dpp_crop_warp_ix, (frames.ptr, records.ptr, T, src.ptr, H, W, dsz, int(bool(normalize)), float(nd_value), out.ptr),
-                  (frames, records, src, out), name, dict(kernel='crop_warp', flops=10.0 * T * dsz * dsz, bytes=8.0 * T * dsz * dsz))
-
-
-def track_refine_ix(rt, frames, records_in, T, src, gate, H, W, com_in, cube, net_out, cam, crop_fx, crop_fy, dsz, com_out, com3d_out,
-                    records_out, status, M_out=None, name='track_refine'):
-    fx, fy, ux, uy, flip = cam
-    return Launch(rt.lib.dpp_track_refine_ix,
-                  (frames.ptr, records_in.ptr, T, src.ptr, gate.ptr, H, W, com_in.ptr, cube.ptr, net_out.ptr, float(fx), float(fy), float(ux),
-                   float(uy), int(flip), float(crop_fx), float(crop_fy), dsz, com_out.ptr, com3d_out.ptr, records_out.ptr, _p(M_out), status.ptr),
-                  (frames, records_in, src, gate, com_in, cube, net_out, com_out, com3d_out, records_out, M_out, status), name)
-
-
-def crop_warp_ex_ix(rt, frames, records, T, src, tflags, H, W, dsz, out, flags=0, nd_value=0.0, fill_value=None, pad_value=0.0,
-                    name='crop_warp_ex'):
-    """dpp_crop_warp_ex_ix: CROP_FLIP_X comes per track from tflags[t] & POSE_HAND_RIGHT, the other flags hold for all tracks."""
-    fill = float(nd_value) if fill_value is None else float(fill_value)
-    taps = 4 if flags & CROP_BILINEAR else 1
-    return Launch(rt.lib.dpp_crop_warp_ex_ix, (frames.ptr, records.ptr, T, src.ptr, tflags.ptr, H, W, dsz, int(flags), float(nd_value), fill,
-                                               float(pad_value), out.ptr),
-                  (frames, records, src, tflags, out), name,
-                  dict(kernel='crop_warp', flops=(30.0 if taps == 4 else 10.0) * T * dsz * dsz, bytes=(4.0 * taps + 4.0) * T * dsz * dsz))
-
-
-def pose_finish_ix(rt, net_out, T, J, tflags, cube, com3d, cam, pose3d, pose_img, name='pose_finish'):
-    fx, fy, ux, uy, flip = cam
-    return Launch(rt.lib.dpp_pose_finish_ix, (net_out.ptr, T, J, tflags.ptr, cube.ptr, com3d.ptr, float(fx), float(fy), float(ux), float(uy),
-                                              int(flip), pose3d.ptr, pose_img.ptr),
-                  (net_out, tflags, cube, com3d, pose3d, pose_img), name)
+    def __init__(self, T, src=None, gate=None, tflags=None, table=None):
+        arrays = [a for a in (src, gate, tflags) if a is not None]
+        if T < 1 or not arrays or any(a.size != T for a in arrays) or (table is not None and src is None):
+            raise ValueError("a TrackSet has T >= 1 tracks and int32 device arrays of T entries (with a table: src among them)")
+        self.T, self.src, self.gate, self.tflags, self.table = int(T), src, gate, tflags, table
 
 
 # ---- frame sources of unlike cameras and frame sizes (include/dpp_hip.h, ABI v19) -------------------------------------------------------
@@ -907,56 +939,6 @@ class SourceTable(object):
 
     def size(self, c):
         return int(self.host['H'][c]), int(self.host['W'][c])
-
-
-def frame_range_src(rt, frames, table, partial, name='frame_range'):
-    return Launch(rt.lib.dpp_frame_range_src, (frames.ptr, table.dev.ptr, table.C, partial.ptr), (frames, table.dev, partial), name,
-                  dict(kernel='frame_range', flops=2.0 * table.npx, bytes=4.0 * table.npx))
-
-
-def frame_ingest_src(rt, raw, table, frames, partial, median=False, mirror=False, name='frame_ingest'):
-    if raw.dtype.name not in INGEST_TYPES:
-        raise ValueError("frame_ingest reads uint16 or float32 frames, not %s" % raw.dtype.name)
-    flags = (INGEST_MEDIAN3 if median else 0) | (INGEST_MIRROR_X if mirror else 0)
-    return Launch(rt.lib.dpp_frame_ingest_src, (raw.ptr, INGEST_TYPES[raw.dtype.name], table.dev.ptr, table.C, flags, frames.ptr, _p(partial)),
-                  (raw, table.dev, frames, partial), name,
-                  dict(kernel='frame_ingest', flops=(22.0 if median else 2.0) * table.npx, bytes=(raw.dtype.itemsize + 4.0) * table.npx))
-
-
-def crop_prepare_ranged_src(rt, partial, T, src, gate, table, com, cube, dsz, records, M_out=None, stretch=False, name='crop_prepare_ranged'):
-    return Launch(rt.lib.dpp_crop_prepare_ranged_src, (partial.ptr, T, src.ptr, gate.ptr, table.dev.ptr, com.ptr, cube.ptr, dsz,
-                                                       int(bool(stretch)), records.ptr, _p(M_out)),
-                  (partial, src, gate, table.dev, com, cube, records, M_out), name)
-
-
-def crop_warp_src(rt, frames, records, T, src, table, dsz, out, normalize=True, nd_value=0.0, name='crop_warp'):
-    return Launch(rt.lib.dpp_crop_warp_src, (frames.ptr, records.ptr, T, src.ptr, table.dev.ptr, dsz, int(bool(normalize)), float(nd_value),
-                                             out.ptr),
-                  (frames, records, src, table.dev, out), name, dict(kernel='crop_warp', flops=10.0 * T * dsz * dsz, bytes=8.0 * T * dsz * dsz))
-
-
-def track_refine_src(rt, frames, records_in, T, src, gate, table, com_in, cube, net_out, dsz, com_out, com3d_out, records_out, status,
-                     M_out=None, name='track_refine'):
-    return Launch(rt.lib.dpp_track_refine_src,
-                  (frames.ptr, records_in.ptr, T, src.ptr, gate.ptr, table.dev.ptr, com_in.ptr, cube.ptr, net_out.ptr, dsz, com_out.ptr,
-                   com3d_out.ptr, records_out.ptr, _p(M_out), status.ptr),
-                  (frames, records_in, src, gate, table.dev, com_in, cube, net_out, com_out, com3d_out, records_out, M_out, status), name)
-
-
-def crop_warp_ex_src(rt, frames, records, T, src, tflags, table, dsz, out, flags=0, nd_value=0.0, fill_value=None, pad_value=0.0,
-                     name='crop_warp_ex'):
-    fill = float(nd_value) if fill_value is None else float(fill_value)
-    taps = 4 if flags & CROP_BILINEAR else 1
-    return Launch(rt.lib.dpp_crop_warp_ex_src, (frames.ptr, records.ptr, T, src.ptr, tflags.ptr, table.dev.ptr, dsz, int(flags), float(nd_value),
-                                                fill, float(pad_value), out.ptr),
-                  (frames, records, src, tflags, table.dev, out), name,
-                  dict(kernel='crop_warp', flops=(30.0 if taps == 4 else 10.0) * T * dsz * dsz, bytes=(4.0 * taps + 4.0) * T * dsz * dsz))
-
-
-def pose_finish_src(rt, net_out, T, J, src, tflags, table, cube, com3d, pose3d, pose_img, name='pose_finish'):
-    return Launch(rt.lib.dpp_pose_finish_src, (net_out.ptr, T, J, src.ptr, tflags.ptr, table.dev.ptr, cube.ptr, com3d.ptr, pose3d.ptr,
-                                               pose_img.ptr),
-                  (net_out, src, tflags, table.dev, cube, com3d, pose3d, pose_img), name)
 
 
 # ---- tracks of one hand across calibrated cameras (include/dpp_hip.h, ABI v20; csrc/fuse.hip) ------------------------------------------

@@ -66,43 +66,76 @@ def _engine_b1(net, rt, what):
 def refine_stage(rt, frame, H, W, partial, rec, com_in, cube, ceng, cam, fx, fy, dsz_final, com_out, com3d, rec_out, status, M=None, tracks=None):
     """The (op, side) list of HandDetector.track for ONE frame whose depth-range partials are in `partial`: window around com_in,
     the refinement net's inputs, its forward plan, track_refine.  Shared by HandTracker's plan and HandDetector.track -- and, with
-    tracks = (T, src, gate) (int32 device arrays, one entry per track: hipdp/multitrack.py), by MultiTracker's plan: the same steps
-    for T tracks that each read frame src[t] of `frame` and its partials, through the indexed siblings of the three crop launches.
-    tracks = (T, src, gate, table) (table: an ops.SourceTable): the sources have cameras and frame sizes of their own, `frame` is the
-    ragged frame buffer, the *_src siblings read (H, W, cam, fx, fy) per source from the table and the arguments of that name are unused."""
+    tracks = an ops.TrackSet (hipdp/multitrack.py), by MultiTracker's plan: the same steps for T tracks that each read frame src[t] of
+    `frame` and its partials, through the indexed siblings of the three crop launches.  Where the TrackSet has a table the sources have
+    cameras and frame sizes of their own, `frame` is the ragged frame buffer, the *_src siblings read (H, W, cam, fx, fy) per source
+    from the table and the arguments of that name are unused."""
     nin = len(ceng.x_ins)
     if nin not in (1, 3):
         raise NotImplementedError("Number of inputs is {}".format(nin))
     if ceng.out_dim != 3:
         raise ValueError("the refinement net must regress one 3-D offset")
     rs = int(ceng.x_ins[0].shape[1])
-    B = 1 if tracks is None else int(tracks[0])
+    B = 1 if tracks is None else tracks.T
     in0 = ceng.x_ins[0].buf.reshape(B, rs, rs)
-    if tracks is None:
-        out = [(ops.crop_prepare_ranged(rt, partial, 1, com_in, cube, fx, fy, rs, rec, None, stretch=True), False),
-               (ops.crop_warp(rt, frame, rec, 1, H, W, rs, in0, normalize=True, nd_value=0.0, name='track_in0'), False)]
-    elif len(tracks) == 4:
-        _, src, gate, table = tracks
-        out = [(ops.crop_prepare_ranged_src(rt, partial, B, src, gate, table, com_in, cube, rs, rec, None, stretch=True), False),
-               (ops.crop_warp_src(rt, frame, rec, B, src, table, rs, in0, normalize=True, nd_value=0.0, name='track_in0'), False)]
-    else:
-        _, src, gate = tracks
-        out = [(ops.crop_prepare_ranged_ix(rt, partial, B, src, gate, com_in, cube, fx, fy, rs, rec, None, stretch=True), False),
-               (ops.crop_warp_ix(rt, frame, rec, B, src, H, W, rs, in0, normalize=True, nd_value=0.0, name='track_in0'), False)]
+    out = [(ops.crop_prepare_ranged(rt, partial, B, com_in, cube, fx, fy, rs, rec, None, stretch=True, tracks=tracks), False),
+           (ops.crop_warp(rt, frame, rec, B, H, W, rs, in0, normalize=True, nd_value=0.0, name='track_in0', tracks=tracks), False)]
     for k in range(1, nin):                        # 1/2 and 1/4 CENTRE crops, handdetector.py:657-669
         f = 2 ** k
         out.append((ops.crop_center(rt, in0, B, rs, rs, ceng.x_ins[k].buf, rs // f, rs // f, name='track_in%d' % k), False))
     out.extend(ceng.fwd.ops)
-    if tracks is None:
-        out.append((ops.track_refine(rt, frame, rec, 1, H, W, com_in, cube, ceng.out.buf, cam, fx, fy, dsz_final, com_out, com3d, rec_out,
-                                     status, M_out=M), False))
-    elif len(tracks) == 4:
-        out.append((ops.track_refine_src(rt, frame, rec, B, src, gate, table, com_in, cube, ceng.out.buf, dsz_final, com_out, com3d, rec_out,
-                                         status, M_out=M), False))
-    else:
-        out.append((ops.track_refine_ix(rt, frame, rec, B, src, gate, H, W, com_in, cube, ceng.out.buf, cam, fx, fy, dsz_final, com_out,
-                                        com3d, rec_out, status, M_out=M), False))
+    out.append((ops.track_refine(rt, frame, rec, B, H, W, com_in, cube, ceng.out.buf, cam, fx, fy, dsz_final, com_out, com3d, rec_out, status,
+                                 M_out=M, tracks=tracks), False))
     return out
+
+
+def valid_centre(com):
+    """A centre (image coordinates, z in mm) a track can start from: finite, with a depth that is not numpy.isclose to 0."""
+    return bool(np.all(np.isfinite(com))) and not np.isclose(com[2], 0.)
+
+
+def check_frame(frame, sensor, shape, who):
+    """`frame` as the array a tracker uploads: float32 without a sensor, else a raw frame of the sensor's dtype (taken as it is or not
+    at all: no silent conversion), of `shape`; `who` words the shape error ("expected", "source 1 delivers")."""
+    if sensor is None:
+        frame = np.asarray(frame, np.float32)
+    else:
+        frame = np.asarray(frame)
+        if frame.dtype != sensor[0]:
+            raise ValueError("frame dtype %s, the tracker's sensor delivers %s" % (frame.dtype, sensor[0]))
+    if frame.shape != shape:
+        raise ValueError("frame shape %s, %s %s" % (frame.shape, who, shape))
+    return frame
+
+
+class ResultBlock(object):
+    """Everything the host reads per frame as ONE float32 device allocation (`buf`): an ordered list of (name, shape, dtype) fields of
+    4-byte elements.  `offsets`: name -> first word; view(name): the field on the device; split(host): name -> the field of a
+    downloaded block, reshaped, an int32 field viewed as int32."""
+
+    def __init__(self, rt, fields):
+        self.fields, n = {}, 0                      # name -> (first word, one past the last, shape, dtype), in block order
+        for name, shape, dtype in fields:
+            assert np.dtype(dtype).itemsize == 4, (name, dtype)
+            self.fields[name] = (n, n + int(np.prod(shape)), tuple(shape), np.dtype(dtype))
+            n = self.fields[name][1]
+        self.offsets = dict((name, f[0]) for name, f in self.fields.items())
+        self.buf = rt.alloc(n, np.float32)
+
+    def view(self, name):
+        a, _, shape, dtype = self.fields[name]
+        return self.buf.view(a, shape, dtype)
+
+    def split(self, host):
+        return dict((name, host[a:b].view(dtype).reshape(shape)) for name, (a, b, shape, dtype) in self.fields.items())
+
+
+def track_fields(T, J):
+    """The fields every tracker's block starts with, over T tracks: pose (mm), pose in image coordinates, centres (= the state), com3D,
+    M, status -- and one detector's 8 words (seed, cube out, status: acquire)."""
+    f32 = np.float32
+    return [('pose', (T, J, 3), f32), ('pose_img', (T, J, 3), f32), ('com', (T, 3), f32), ('com3D', (T, 3), f32), ('M', (T, 3, 3), f32),
+            ('status', (T,), np.int32), ('det', (8,), f32)]
 
 
 class HandTracker(object):
@@ -129,7 +162,6 @@ class HandTracker(object):
             raise ValueError("the pose net takes one crop and regresses J x 3 coordinates")
         self.rs, self.ds, self.J = int(self.ceng.x_ins[0].shape[1]), int(self.peng.x_in.shape[1]), self.peng.out_dim // 3
         f32 = np.float32
-        J3 = self.J * 3
         self.frames = [rt.alloc((1, self.H, self.W), f32, zero=False) for _ in range(2)]      # t and t + 1 (process_sequence)
         self.sensor = None if sensor is None else ops.sensor_spec(sensor)                      # (dtype, median, mirror)
         # with a sensor the host uploads into `raw`, frame_ingest fills `frames`; without one `frames` IS what the host uploads into
@@ -139,10 +171,10 @@ class HandTracker(object):
         self.rec = rt.alloc(rt.lib.dpp_crop_record_bytes(), np.uint8)
         self.cube = rt.alloc((1, 3), f32)
         # everything the host reads per frame is ONE block: pose (mm), pose in image coordinates, centre (= the state), com3D, M, status
-        self.res = rt.alloc(2 * J3 + 16 + 8, f32)                              # (+ the detector's seed / cube / status words: acquire)
-        self.pose3d, self.pose_img = self.res.view(0, (1, self.J, 3)), self.res.view(J3, (1, self.J, 3))
-        self.com, self.com3d = self.res.view(2 * J3, (1, 3)), self.res.view(2 * J3 + 3, (1, 3))
-        self.M, self.status = self.res.view(2 * J3 + 6, (1, 9)), self.res.view(2 * J3 + 15, (1,), np.int32)
+        self.block = blk = ResultBlock(rt, track_fields(1, self.J))            # (+ the detector's seed / cube / status words: acquire)
+        self.res = blk.buf
+        self.pose3d, self.pose_img, self.com, self.com3d = blk.view('pose'), blk.view('pose_img'), blk.view('com'), blk.view('com3D')
+        self.M, self.status = blk.view('M'), blk.view('status')
         self.crop = self.peng.x_in.buf.reshape(1, self.ds, self.ds)          # the pose net's input IS the final crop
         self.flags = 0
         self.set_hand(hand_right)
@@ -158,7 +190,7 @@ class HandTracker(object):
     def reset(self, com):
         """Start (again) from the centre `com` (image coordinates, z in mm)."""
         com = np.asarray(com, np.float32).reshape(3)
-        if not np.all(np.isfinite(com)) or np.isclose(com[2], 0.):
+        if not valid_centre(com):
             raise ValueError("reset needs a centre with a depth: %r" % (com,))
         self.com.set(com)
         self.lost = False
@@ -169,8 +201,7 @@ class HandTracker(object):
         if self._detector is None:
             from .detect import FrameDetector
             self._detector = FrameDetector(self.rt, self.H, self.W, self.fx, self.fy, 1, frames=self.frames[0], partial=self.partial,
-                                           com=self.com, cube=self.cube, res=self.res.view(2 * self.J * 3 + 16, (8,)),
-                                           sensor=None if self.sensor is None else dict(zip(('dtype', 'median', 'mirror'), self.sensor)),
+                                           com=self.com, cube=self.cube, res=self.block.view('det'), sensor=self.sensor,
                                            raw=None if self.sensor is None else self.raw[0])
         return self._detector
 
@@ -185,9 +216,9 @@ class HandTracker(object):
         self._slot = 0
         det.plan(do_hand_size).run(self.rt)
         self.rt.synchronize()
-        res, J3 = self.res.get(), self.J * 3                                    # the tracker's block: centre and detector words together
-        coms, cubes, found, _, _ = det.parse(res[2 * J3 + 16:], res[2 * J3:2 * J3 + 3], None if do_hand_size else self.cube_host)
-        ok = bool(found[0]) and bool(np.all(np.isfinite(coms[0]))) and not np.isclose(coms[0][2], 0.)
+        res = self.block.split(self.res.get())                                  # the tracker's block: centre and detector words together
+        coms, cubes, found, _, _ = det.parse(res['det'], res['com'], None if do_hand_size else self.cube_host)
+        ok = bool(found[0]) and valid_centre(coms[0])
         self.lost = not ok
         return dict(com=coms[0], cube=cubes[0], found=ok)
 
@@ -239,10 +270,8 @@ class HandTracker(object):
         return self._plans[key]
 
     def _result(self, res, crop=None):
-        J3 = self.J * 3
-        st = int(res[2 * J3 + 15:2 * J3 + 16].view(np.int32)[0])
-        out = dict(pose=res[:J3].reshape(self.J, 3), pose_img=res[J3:2 * J3].reshape(self.J, 3), com=res[2 * J3:2 * J3 + 3],
-                   com3D=res[2 * J3 + 3:2 * J3 + 6], M=res[2 * J3 + 6:2 * J3 + 15].reshape(3, 3), status=st)
+        out = dict((k, v[0]) for k, v in self.block.split(res).items() if k != 'det')      # the one track's row of every field
+        out['status'] = int(out['status'])
         if crop is not None:
             out['crop'] = crop
         return out
@@ -253,15 +282,7 @@ class HandTracker(object):
         return self._frame(frame)
 
     def _frame(self, frame):
-        if self.sensor is None:
-            frame = np.asarray(frame, np.float32)
-        else:                                       # a raw frame is taken as it is or not at all: no silent conversion
-            frame = np.asarray(frame)
-            if frame.dtype != self.sensor[0]:
-                raise ValueError("frame dtype %s, the tracker's sensor delivers %s" % (frame.dtype, self.sensor[0]))
-        if frame.shape != (self.H, self.W):
-            raise ValueError("frame shape %s, expected %s" % (frame.shape, (self.H, self.W)))
-        return frame
+        return check_frame(frame, self.sensor, (self.H, self.W), 'expected')
 
     def process(self, frame, return_crop=False):
         """One frame, synchronously: one upload, one plan, one download.  Returns dict(pose [J][3] mm, pose_img [J][3], com [3] image

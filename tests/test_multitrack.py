@@ -79,12 +79,12 @@ def test_indexed_launches_equal_their_siblings_on_gathered_frames(backend, camna
         c3, M, st = rt.alloc((Tn, 3), zero=False), rt.alloc((Tn, 9), zero=False), rt.alloc((Tn,), np.int32)
         out = {}
         if ix:
-            ops.crop_prepare_ranged_ix(rt, partial, Tn, s, g, co, cu, fx, fy, rs, rec, None, stretch=True)(rt.stream)
+            ops.crop_prepare_ranged(rt, partial, Tn, co, cu, fx, fy, rs, rec, None, stretch=True, tracks=ops.TrackSet(Tn, s, g))(rt.stream)
             rt.synchronize()
             out['rec0'] = _records(rt, rec, Tn)
-            ops.crop_warp_ix(rt, fr, rec, Tn, s, H, W, rs, in0, normalize=True, nd_value=0.0)(rt.stream)
-            ops.track_refine_ix(rt, fr, rec, Tn, s, g, H, W, co, cu, no, camt, fx, fy, ds, co, c3, rec, st, M_out=M)(rt.stream)
-            ops.crop_warp_ex_ix(rt, fr, rec, Tn, s, tf, H, W, ds, crop, flags=ops.CROP_NORMALIZE, nd_value=0.0)(rt.stream)
+            ops.crop_warp(rt, fr, rec, Tn, H, W, rs, in0, normalize=True, nd_value=0.0, tracks=ops.TrackSet(Tn, s))(rt.stream)
+            ops.track_refine(rt, fr, rec, Tn, H, W, co, cu, no, camt, fx, fy, ds, co, c3, rec, st, M_out=M, tracks=ops.TrackSet(Tn, s, g))(rt.stream)
+            ops.crop_warp_ex(rt, fr, rec, Tn, H, W, ds, crop, flags=ops.CROP_NORMALIZE, nd_value=0.0, tracks=ops.TrackSet(Tn, s, tflags=tf))(rt.stream)
             rt.synchronize()
             out['crop'] = crop.get()
         else:
@@ -129,8 +129,8 @@ def test_indexed_launches_equal_their_siblings_on_gathered_frames(backend, camna
     co, cu, no = rt.upload(bad), rt.upload(cubes), rt.upload(net_out)
     s, g = _i32(rt, src), _i32(rt, [1, 0, 1])
     rec, c3, st = rt.alloc(Tn * nrec, np.uint8), rt.alloc((Tn, 3), zero=False), rt.alloc((Tn,), np.int32)
-    ops.crop_prepare_ranged_ix(rt, partial, Tn, s, g, co, cu, fx, fy, rs, rec, None, stretch=True)(rt.stream)
-    ops.track_refine_ix(rt, fr, rec, Tn, s, g, H, W, co, cu, no, camt, fx, fy, ds, co, c3, rec, st)(rt.stream)
+    ops.crop_prepare_ranged(rt, partial, Tn, co, cu, fx, fy, rs, rec, None, stretch=True, tracks=ops.TrackSet(Tn, s, g))(rt.stream)
+    ops.track_refine(rt, fr, rec, Tn, H, W, co, cu, no, camt, fx, fy, ds, co, c3, rec, st, tracks=ops.TrackSet(Tn, s, g))(rt.stream)
     rt.synchronize()
     assert st.get().tolist() == [0, IDLE, 0] and co.get()[1].tobytes() == bad[1].tobytes()
     # the entry points refuse missing index arrays and the per-track flag as a launch flag
@@ -154,7 +154,7 @@ def test_pose_finish_ix_carries_all_flag_values_in_one_launch(backend, camname):
     p3, pi = rt.alloc((Tn, J, 3), zero=False), rt.alloc((Tn, J, 3), zero=False)
     q3, qi = rt.alloc((Tn, J, 3), zero=False), rt.alloc((Tn, J, 3), zero=False)
     for perm in (np.arange(8), np.int32([5, 2, 7, 0, 3, 6, 1, 4])):
-        ops.pose_finish_ix(rt, no, Tn, J, _i32(rt, perm), cu, c3, camt, p3, pi)(rt.stream)
+        ops.pose_finish(rt, no, Tn, J, cu, c3, camt, None, p3, pi, tracks=ops.TrackSet(Tn, tflags=_i32(rt, perm)))(rt.stream)
         rt.synchronize()
         got3, goti = p3.get(), pi.get()
         for t in range(Tn):

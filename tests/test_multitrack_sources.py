@@ -113,23 +113,25 @@ def test_src_launches_equal_their_siblings_on_each_source_alone(backend):
         p3, pi = rt.alloc((n, J, 3), zero=False), rt.alloc((n, J, 3), zero=False)
         out = {}
         if which is None:
-            ops.frame_range_src(rt, fr, table, partial)(rt.stream)
-            ops.crop_prepare_ranged_src(rt, partial, n, s, g, table, co, cu, rs, rec, None, stretch=True)(rt.stream)
+            ops.frame_range(rt, fr, None, None, None, partial, table=table)(rt.stream)
+            ops.crop_prepare_ranged(rt, partial, n, co, cu, None, None, rs, rec, None, stretch=True, tracks=ops.TrackSet(n, s, g, table=table))(rt.stream)
             rt.synchronize()
             out['rec0'] = _records(rt, rec, n)
-            ops.crop_warp_src(rt, fr, rec, n, s, table, rs, in0, normalize=True, nd_value=0.0)(rt.stream)
-            ops.track_refine_src(rt, fr, rec, n, s, g, table, co, cu, no, ds, co, c3, rec, st, M_out=M)(rt.stream)
-            ops.crop_warp_ex_src(rt, fr, rec, n, s, tf, table, ds, crop, flags=ops.CROP_NORMALIZE, nd_value=0.0)(rt.stream)
-            ops.pose_finish_src(rt, po, n, J, s, tf, table, cu, c3, p3, pi)(rt.stream)
+            ops.crop_warp(rt, fr, rec, n, None, None, rs, in0, normalize=True, nd_value=0.0, tracks=ops.TrackSet(n, s, table=table))(rt.stream)
+            ops.track_refine(rt, fr, rec, n, None, None, co, cu, no, None, None, None, ds, co, c3, rec, st, M_out=M,
+                             tracks=ops.TrackSet(n, s, g, table=table))(rt.stream)
+            ops.crop_warp_ex(rt, fr, rec, n, None, None, ds, crop, flags=ops.CROP_NORMALIZE, nd_value=0.0,
+                             tracks=ops.TrackSet(n, s, tflags=tf, table=table))(rt.stream)
+            ops.pose_finish(rt, po, n, J, cu, c3, None, None, p3, pi, tracks=ops.TrackSet(n, s, tflags=tf, table=table))(rt.stream)
         else:
             ops.frame_range(rt, fr, 1, H, W, partial)(rt.stream)
-            ops.crop_prepare_ranged_ix(rt, partial, n, s, g, co, cu, fx, fy, rs, rec, None, stretch=True)(rt.stream)
+            ops.crop_prepare_ranged(rt, partial, n, co, cu, fx, fy, rs, rec, None, stretch=True, tracks=ops.TrackSet(n, s, g))(rt.stream)
             rt.synchronize()
             out['rec0'] = _records(rt, rec, n)
-            ops.crop_warp_ix(rt, fr, rec, n, s, H, W, rs, in0, normalize=True, nd_value=0.0)(rt.stream)
-            ops.track_refine_ix(rt, fr, rec, n, s, g, H, W, co, cu, no, camt, fx, fy, ds, co, c3, rec, st, M_out=M)(rt.stream)
-            ops.crop_warp_ex_ix(rt, fr, rec, n, s, tf, H, W, ds, crop, flags=ops.CROP_NORMALIZE, nd_value=0.0)(rt.stream)
-            ops.pose_finish_ix(rt, po, n, J, tf, cu, c3, camt, p3, pi)(rt.stream)
+            ops.crop_warp(rt, fr, rec, n, H, W, rs, in0, normalize=True, nd_value=0.0, tracks=ops.TrackSet(n, s))(rt.stream)
+            ops.track_refine(rt, fr, rec, n, H, W, co, cu, no, camt, fx, fy, ds, co, c3, rec, st, M_out=M, tracks=ops.TrackSet(n, s, g))(rt.stream)
+            ops.crop_warp_ex(rt, fr, rec, n, H, W, ds, crop, flags=ops.CROP_NORMALIZE, nd_value=0.0, tracks=ops.TrackSet(n, s, tflags=tf))(rt.stream)
+            ops.pose_finish(rt, po, n, J, cu, c3, camt, None, p3, pi, tracks=ops.TrackSet(n, tflags=tf))(rt.stream)
         rt.synchronize()
         out.update(partial=partial.get().reshape(nC, -1), in0=in0.get(), com=co.get(), com3D=c3.get(), M=M.get(), status=st.get(),
                    rec1=_records(rt, rec, n), crop=crop.get(), pose=p3.get(), pose_img=pi.get())
@@ -152,9 +154,9 @@ def test_src_launches_equal_their_siblings_on_each_source_alone(backend):
     s, g = _i32(rt, src), _i32(rt, gate)
     partial, rec = ops.frame_range_workspace(rt, C), rt.alloc(Tn * nrec, np.uint8)
     c3, st = rt.alloc((Tn, 3), zero=False), rt.alloc((Tn,), np.int32)
-    ops.frame_range_src(rt, fr, wrong, partial)(rt.stream)
-    ops.crop_prepare_ranged_src(rt, partial, Tn, s, g, wrong, co, cu, rs, rec, None, stretch=True)(rt.stream)
-    ops.track_refine_src(rt, fr, rec, Tn, s, g, wrong, co, cu, no, ds, co, c3, rec, st)(rt.stream)
+    ops.frame_range(rt, fr, None, None, None, partial, table=wrong)(rt.stream)
+    ops.crop_prepare_ranged(rt, partial, Tn, co, cu, None, None, rs, rec, None, stretch=True, tracks=ops.TrackSet(Tn, s, g, table=wrong))(rt.stream)
+    ops.track_refine(rt, fr, rec, Tn, None, None, co, cu, no, None, None, None, ds, co, c3, rec, st, tracks=ops.TrackSet(Tn, s, g, table=wrong))(rt.stream)
     rt.synchronize()
     assert not np.array_equal(co.get()[0], got['com'][0]) and np.array_equal(co.get()[1], got['com'][1])
 
@@ -174,7 +176,7 @@ def test_frame_ingest_src_equals_frame_ingest_on_each_source_alone(backend, dtyp
     raw, _ = _ragged(rt, table, raws, dt, raw=True)
     out, _ = _ragged(rt, table, [np.zeros(s, np.float32) for s in sizes], np.float32)
     partial = ops.frame_range_workspace(rt, 3)
-    ops.frame_ingest_src(rt, raw, table, out, partial, median=median, mirror=mirror)(rt.stream)
+    ops.frame_ingest(rt, raw, None, None, None, out, partial, median=median, mirror=mirror, table=table)(rt.stream)
     rt.synchronize()
     got, gp = out.get(), partial.get().reshape(3, -1)
     assert np.isnan(_pads(table, got)).all() and _pads(table, got).size == 6           # the pad elements: never written
