@@ -9,27 +9,12 @@
 // group's membership from there -- the median test, the inliers, the fused centre; the K lanes then form their member's peer centre and
 // the hand-over, and all lanes stride over the J joints.  The launch is bound by its launch, not by its work.
 #include "geom.h"
+#include "rigid.h"
 
 namespace {
 
 constexpr int TRACK_OK = 0, TRACK_LOST = 1;                         // dpp_track_refine's status word (crop.hip)
 constexpr int FUSE_MAX = DPP_FUSE_MAX_MEMBERS;
-
-// w = R p + t, row i as ((R_i0 x + R_i1 y) + R_i2 z) + t_i; e = [R row-major, t]
-__device__ __forceinline__ void to_world(const double* __restrict__ e, const double p[3], double w[3]) {
-    for (int i = 0; i < 3; ++i) w[i] = ((e[i * 3] * p[0] + e[i * 3 + 1] * p[1]) + e[i * 3 + 2] * p[2]) + e[9 + i];
-}
-
-// p = R^T (w - t), row i as (R_0i d0 + R_1i d1) + R_2i d2
-__device__ __forceinline__ void to_camera(const double* __restrict__ e, const double w[3], double p[3]) {
-    const double d[3] = {w[0] - e[9], w[1] - e[10], w[2] - e[11]};
-    for (int i = 0; i < 3; ++i) p[i] = (e[i] * d[0] + e[3 + i] * d[1]) + e[6 + i] * d[2];
-}
-
-__device__ __forceinline__ double dist3(const double a[3], const double b[3]) {
-    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-    return sqrt((dx * dx + dy * dy) + dz * dz);
-}
 
 __global__ __launch_bounds__(DPP_WAVE) void pose_fuse_kernel(const float* __restrict__ pose3d, const float* __restrict__ com3d,
                                                              const int* __restrict__ status, const int* __restrict__ src, int J,

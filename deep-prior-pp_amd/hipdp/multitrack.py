@@ -14,6 +14,7 @@ again.  Here every launch of that plan runs once per tick for all tracks:
     the pose net's forward plan, built for a batch of T
     pose_finish_ix                  at B = T       the sign rules per track from tflags[t]
     pose_fuse                       at G groups    only with `groups`: the tracks of one hand fused, lost tracks handed over (below)
+    extrinsics_accumulate           per source     in pose_fuse's place while a source's extrinsics are being calibrated (below)
 
 so the launch count is HandTracker's whatever T and C are (plus one with `groups`).  A track names its source (`src`), its hand side and invX / invY
 (`tflags`) and whether it takes part in this tick (`gate`) in three small int32 device arrays; the hand side is data, not a launch
@@ -48,8 +49,22 @@ the plan, one workgroup per group, then
 A track that is gated because it is lost (it lost the hand while no peer had it) is restarted by process() through reset(t, peer_com)
 in the first tick in which its peers have the hand: one small upload, as acquire makes.  Tracks in no group are left entirely alone, and
 without `groups` the tracker allocates, uploads, launches and returns exactly what it did before.  Confidence weighting, temporal
-filtering, triangulation from 2-D alone, calibrating the extrinsics, fusing the depth frames themselves, hand size for several hands
-and per-source sensor options are out of scope.
+filtering, triangulation from 2-D alone, fusing the depth frames themselves, hand size for several hands and per-source sensor options
+are out of scope.
+
+CALIBRATION (ABI v21; csrc/calib.hip, hipdp/calib.py; this project's own as well, restated by tests/calib_ref.py).  The (R, t) that fusion
+needs can come from the tracked hand itself: every tick gives the same J joints of one hand in each camera's frame, and a least-squares
+rigid fit needs only running sums over those pairs.  With calibrate=dict(anchor=, max_shape_dev=, min_cond=) entries of `extrinsics` may
+be None.  While such a source is pending (`calibrating`) the tick's last launch is extrinsics_accumulate in pose_fuse's place -- the same
+launch count -- which adds, per pending source c and per group with an OK track on both the anchor source and c, the J pairs (joint in
+c's frame, the anchor's joint in the world frame) to c's row of `acc`, a small float64 buffer of its own.  With max_shape_dev (mm) a pair
+of tracks whose two skeletons differ in shape by more than that -- joint distances from the centroid; rigid motions keep them -- stays
+out (a track that slid onto something else).  `fused` is [], nothing is handed over, the per-track results are the ungrouped tracker's
+plus 'group'; process_sequence works unchanged.  calibration_report() downloads the sums and fits (calib.solve_rigid: Kabsch on the
+host, with n, rms, cond = s2 / s1 and ok); finish_calibration() also installs the fits when all are ok and rebuilds the plan: from then
+on the tracker builds the launches of one constructed with these extrinsics.  reset_calibration() zeroes the sums.  Out of scope: time
+alignment of the cameras (the pairs are taken as simultaneous), intrinsics, chained calibration through a third camera (every pending
+source must share a group with the anchor), weighting by joint, drift monitoring after calibration, and re-solving on the device.
 
 acquire_source(c, frame) finds ALL hands of a source in one detector plan and starts the source's tracks from them; the detectors
 are built per source, at that source's size and focal lengths, on views of its frame slice.
@@ -70,7 +85,7 @@ from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, refine_s
 
 class MultiTracker(object):
     def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, tracks, sources=None, invX=False, invY=False, fx=None, fy=None,
-                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True):
+                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True, calibrate=None):
         """
         :param importer:   the dataset importer (the camera) of all sources, or a sequence of C importers, one per source
         :param poseNet, comrefNet: as for HandTracker, but built for a batch of T, the number of tracks: row t is track t
@@ -87,6 +102,8 @@ class MultiTracker(object):
                            (disjoint, 1 .. 16 members each; needs `extrinsics`).  None: no fusion, the tracker of before
         :param max_dev:    None, or the distance (mm) beyond which a member's world centre is an outlier / two members disagree
         :param handover:   a member that lost the hand (or is an outlier) goes on from its peers' centre; False: fusion reports only
+        :param calibrate:  None, or dict(anchor=0, max_shape_dev=None, min_cond=0.) (any subset): entries of `extrinsics` may then be
+                           None, and those sources are calibrated against the source `anchor` from the tracked hand (CALIBRATION above)
         """
         self.rt = rt
         tracks = [(int(s), bool(r)) for s, r in tracks]
@@ -102,6 +119,18 @@ class MultiTracker(object):
             raise ValueError("groups needs extrinsics: one (R, t) per source")
         if max_dev is not None and not (np.isfinite(max_dev) and max_dev > 0.):
             raise ValueError("max_dev is None or a distance > 0 (mm): %r" % (max_dev,))
+        cal = None
+        if calibrate is not None:
+            cal = dict(anchor=0, max_shape_dev=None, min_cond=0.)
+            if set(calibrate) - set(cal):
+                raise ValueError("calibrate takes anchor, max_shape_dev and min_cond, not %r" % sorted(set(calibrate) - set(cal)))
+            cal.update(calibrate)
+            if groups is None:
+                raise ValueError("calibrate needs groups: the pairs come from the tracks of one hand in two sources")
+            if cal['max_shape_dev'] is not None and not (np.isfinite(cal['max_shape_dev']) and cal['max_shape_dev'] > 0.):
+                raise ValueError("max_shape_dev is None or a distance > 0 (mm): %r" % (cal['max_shape_dev'],))
+            if not (np.isfinite(cal['min_cond']) and cal['min_cond'] >= 0.):
+                raise ValueError("min_cond is a ratio >= 0: %r" % (cal['min_cond'],))
         self.max_dev, self.handover = None if max_dev is None else float(max_dev), bool(handover)
         importers = self._per_source(importer, C, 'importer')
         Hs, Ws = self._per_source(H, C, 'H'), self._per_source(W, C, 'W')
@@ -145,7 +174,13 @@ class MultiTracker(object):
         self.trackset = ops.TrackSet(T, self.src, self.gate, self.tflags, self.table)    # what the plan's launches know about their rows
         # everything the host reads per tick is ONE block, every entry an array over the tracks (the launches write [T][...] arrays)
         fields = track_fields(T, self.J)
-        self.rig = None if groups is None else ops.FuseRig(rt, extrinsics, groups, self.src_host, C)   # validated there, uploaded once
+        self.rig = None if groups is None else ops.FuseRig(rt, extrinsics, groups, self.src_host, C,   # validated there, uploaded once
+                                                           anchor=None if cal is None else cal['anchor'])
+        self.cal_src, self.acc = [], None
+        if cal is not None and self.rig.pending:        # the sums are a buffer of their own: the per-tick download does not grow
+            self.anchor, self.max_shape_dev, self.min_cond = self.rig.anchor, cal['max_shape_dev'], float(cal['min_cond'])
+            self.cal_src = list(self.rig.pending)
+            self.acc = rt.alloc((len(self.cal_src), ops.CALIB_SLOTS), np.float64)
         if self.rig is not None:                                                   # the fused arrays follow: every offset above keeps its value
             G = self.rig.G
             fields += [('fused_pose', (G, self.J, 3), f32), ('fused_com', (G, 3), f32), ('spread', (G, self.J), f32), ('n', (G,), i32),
@@ -340,6 +375,40 @@ class MultiTracker(object):
                 out[t] = dict(com=np.zeros(3, np.float32), cube=self.cube_host[t].copy(), found=False)
         return [out[t] for t in ts]
 
+    # ---- calibration ------------------------------------------------------------------------------------------------------
+    @property
+    def calibrating(self):
+        """A source still waits for its (R, t): the tick ends in extrinsics_accumulate, nothing is fused or handed over."""
+        return self.rig is not None and bool(self.rig.pending)
+
+    def calibration_report(self):
+        """{source: calib.solve_rigid of its sums so far} for every source that is being calibrated: one download of
+        len(cal_src) x 160 bytes, one 3 x 3 SVD each.  Nothing changes."""
+        from .calib import solve_rigid
+        if not self.calibrating:
+            raise RuntimeError("no source is being calibrated")
+        self.rt.synchronize()
+        rows = self.acc.get()
+        return dict((c, solve_rigid(rows[k], self.min_cond)) for k, c in enumerate(self.cal_src))
+
+    def finish_calibration(self):
+        """calibration_report(), and where EVERY source's fit is ok: the fits become the rig's extrinsics (one small upload each) and the
+        plan is rebuilt -- from the next tick on this is the tracker that was constructed with them.  Otherwise nothing changes, and the
+        caller goes on feeding ticks (or reset_calibration()).  Returns the report."""
+        report = self.calibration_report()
+        if all(r['ok'] for r in report.values()):
+            for c in list(self.cal_src):
+                self.rig.set_extrinsics(c, report[c]['R'], report[c]['t'])
+            self._plans = {}
+        return report
+
+    def reset_calibration(self):
+        """Forget the pairs summed so far."""
+        if self.acc is None:
+            raise RuntimeError("no source is being calibrated")
+        self.rt.synchronize()
+        self.acc.set(np.zeros(self.acc.shape, np.float64))
+
     # ---- the per-tick plan --------------------------------------------------------------------------------------------------
     def _second_set(self):
         """process_sequence's second set of input buffers (and of gates): made the first time a sequence runs, so a tracker that only
@@ -379,7 +448,10 @@ class MultiTracker(object):
                 p.add(op, side)
             p.add(ops.pose_finish(rt, self.peng.out.buf, T, self.J, self.cube, self.com3d, self.cam, None, self.pose3d, self.pose_img,
                                   tracks=tracks))
-            if self.rig is not None:                    # the last launch of the main lane: the next tick's prepare is ordered behind it
+            if self.calibrating:                        # in the fusion launch's place: nothing can be fused or handed over yet
+                p.add(ops.extrinsics_accumulate(rt, self.pose3d, self.status, self.src, T, self.J, self.rig, self.anchor, self.cal_src,
+                                                self.max_shape_dev, self.acc))
+            elif self.rig is not None:                  # the last launch of the main lane: the next tick's prepare is ordered behind it
                 p.add(ops.pose_fuse(rt, self.pose3d, self.com3d, self.status, self.src, T, self.J, self.rig, self.table, H, W, self.cam,
                                     self.max_dev, self.handover, self.com, self.fused_pose, self.fused_com, self.spread, self.fused_n,
                                     self.peer_com, self.fstat))
@@ -399,7 +471,9 @@ class MultiTracker(object):
         st, pose, pimg, com, com3d, M = f['status'], f['pose'], f['pose_img'], f['com'], f['com3D'], f['M']
         self.com_host[:] = com
         rig = self.rig
-        if rig is not None:
+        fusing = rig is not None and not rig.pending
+        self.fused = []
+        if fusing:
             fstat, peer = f['fstat'], f['peer_com']
             self.fused = [dict(pose=f['fused_pose'][g], com=f['fused_com'][g], spread=f['spread'][g], n=int(f['n'][g])) for g in range(rig.G)]
             self._peer_ok = (fstat & ops.FUSE_PEER_OK) != 0
@@ -407,7 +481,7 @@ class MultiTracker(object):
         for t in range(self.T):
             status = int(st[t])
             grouped = rig is not None and rig.group_of[t] >= 0
-            handed = grouped and bool(fstat[t] & ops.FUSE_HANDED)
+            handed = grouped and fusing and bool(fstat[t] & ops.FUSE_HANDED)
             if not gate[t]:                          # gated because it is lost (or never started): LOST; because its source idles: IDLE
                 status = LOST if self.lost[t] else IDLE
             else:
@@ -415,7 +489,9 @@ class MultiTracker(object):
                 # process_sequence runs ungated behind a loss the host had not seen yet: that track is gated in a process() loop.)
                 self.lost[t] = status != OK and (bool(self.lost[t]) or not handed)
             d = dict(pose=pose[t], pose_img=pimg[t], com=com[t], com3D=com3d[t], M=M[t], status=status)
-            if grouped:
+            if grouped and not fusing:
+                d.update(group=int(rig.group_of[t]))
+            elif grouped:
                 d.update(group=int(rig.group_of[t]), outlier=bool(fstat[t] & ops.FUSE_OUTLIER), disagree=bool(fstat[t] & ops.FUSE_DISAGREE),
                          handed=handed, peer_com=peer[t])
             if crops is not None:
@@ -443,7 +519,7 @@ class MultiTracker(object):
         self.runs += 1
         self.rt.synchronize()
         out = self._results(self.res.get(), gate, self.crop.get() if return_crop else None)
-        if self.rig is not None and self.handover:
+        if self.rig is not None and self.handover and not self.calibrating:
             for t in np.flatnonzero(self.rig.group_of >= 0):
                 # gated BECAUSE it is lost, and its peers have the hand now: start it again from their centre (one small upload)
                 if not gate[t] and self.lost[t] and self._peer_ok[t]:

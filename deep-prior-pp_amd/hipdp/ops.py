@@ -950,21 +950,28 @@ FUSE_MAX_MEMBERS = 16
 class FuseRig(object):
     """What dpp_pose_fuse reads about the rig, validated here (the kernel trusts it) and uploaded ONCE: `extr` (float64 [C][12]: R
     row-major, then t in mm, per source: w = R p + t takes the source's camera frame to the world), `members` / `offsets` (int32: group
-    g is the tracks members[offsets[g]:offsets[g + 1]] in list order) and, on the host, `groups` and `group_of` (track -> group or -1)."""
+    g is the tracks members[offsets[g]:offsets[g + 1]] in list order) and, on the host, `groups` and `group_of` (track -> group or -1).
 
-    def __init__(self, rt, extrinsics, groups, src, C):
+    anchor (a source, or None): entries of `extrinsics` may then be None -- those sources are `pending`, to be calibrated against the
+    anchor (dpp_extrinsics_accumulate, hipdp/calib.py) and written later through set_extrinsics.  Their rows hold the identity until
+    then.  The anchor's own entry must be given, and every pending source must share a group with the anchor source."""
+
+    def __init__(self, rt, extrinsics, groups, src, C, anchor=None):
         src = np.asarray(src, np.int32).reshape(-1)
         T = src.size
         if extrinsics is None or len(extrinsics) != C:
             raise ValueError("one (R, t) per source: %s for %d sources" % ('none' if extrinsics is None else len(extrinsics), C))
+        if anchor is not None and (int(anchor) != anchor or not 0 <= anchor < C or extrinsics[int(anchor)] is None):
+            raise ValueError("the anchor is a source whose (R, t) is given: %r of %d sources" % (anchor, C))
         ext = np.zeros((C, 12), np.float64)
-        for c, (Rm, t) in enumerate(extrinsics):
-            Rm, t = np.asarray(Rm, np.float64), np.asarray(t, np.float64).reshape(-1)
-            if Rm.shape != (3, 3) or t.shape != (3,) or not np.isfinite(Rm).all() or not np.isfinite(t).all():
-                raise ValueError("source %d: R is a finite 3 x 3 rotation, t a finite 3-vector (mm)" % c)
-            if np.abs(Rm.T.dot(Rm) - np.eye(3)).max() > 1e-6 or not np.linalg.det(Rm) > 0.:
-                raise ValueError("source %d: R is not a rotation (max |R^T R - I| <= 1e-6 and det R > 0): %r" % (c, Rm))
-            ext[c, :9], ext[c, 9:] = Rm.ravel(), t
+        self.pending = []
+        for c, e in enumerate(extrinsics):
+            if e is None:
+                if anchor is None:
+                    raise ValueError("source %d has no (R, t): every source needs one (or calibrate= names an anchor to find it from)" % c)
+                self.pending.append(c)
+                e = (np.eye(3), np.zeros(3))
+            ext[c] = self._row(c, *e)
         groups = [[int(m) for m in g] for g in groups]
         group_of = np.full(T, -1, np.int32)
         if not groups:
@@ -979,10 +986,60 @@ class FuseRig(object):
             if len(set(int(src[m]) for m in ms)) != len(ms):
                 raise ValueError("the members of group %d read pairwise distinct sources: %r" % (g, [int(src[m]) for m in ms]))
             group_of[ms] = g
+        self.anchor = None if anchor is None else int(anchor)
+        for c in self.pending:
+            if not any(set((self.anchor, c)) <= set(int(src[m]) for m in ms) for ms in groups):
+                raise ValueError("source %d shares no group with the anchor source %d: it cannot be calibrated against it (chained "
+                                 "calibration through a third camera is out of scope)" % (c, self.anchor))
+        if len(self.pending) > CALIB_MAX_SOURCES:
+            raise ValueError("%d sources to calibrate at once: at most %d" % (len(self.pending), CALIB_MAX_SOURCES))
         self.G, self.C, self.T, self.groups, self.group_of, self.extr_host = len(groups), int(C), T, groups, group_of, ext
         self.members_host = np.int32([m for ms in groups for m in ms])
         self.offsets_host = np.int32(np.concatenate([[0], np.cumsum([len(ms) for ms in groups])]))
         self.extr, self.members, self.offsets = rt.upload(ext), rt.upload(self.members_host), rt.upload(self.offsets_host)
+
+    @staticmethod
+    def _row(c, Rm, t):
+        """Source c's row of `extr` from (R, t), or ValueError."""
+        Rm, t = np.asarray(Rm, np.float64), np.asarray(t, np.float64).reshape(-1)
+        if Rm.shape != (3, 3) or t.shape != (3,) or not np.isfinite(Rm).all() or not np.isfinite(t).all():
+            raise ValueError("source %d: R is a finite 3 x 3 rotation, t a finite 3-vector (mm)" % c)
+        if np.abs(Rm.T.dot(Rm) - np.eye(3)).max() > 1e-6 or not np.linalg.det(Rm) > 0.:
+            raise ValueError("source %d: R is not a rotation (max |R^T R - I| <= 1e-6 and det R > 0): %r" % (c, Rm))
+        return np.concatenate([Rm.ravel(), t])
+
+    def set_extrinsics(self, c, Rm, t):
+        """Write source c's (R, t), validated as the constructor validates: one upload of its 96 bytes.  A pending source stops being
+        pending."""
+        c = int(c)
+        if not 0 <= c < self.C:
+            raise IndexError("source %d of %d" % (c, self.C))
+        row = self._row(c, Rm, t)
+        self.extr_host[c] = row
+        self.extr.view(12 * c, (12,)).set(row)
+        if c in self.pending:
+            self.pending.remove(c)
+
+
+# ---- extrinsics from the tracked hand (include/dpp_hip.h, ABI v21; csrc/calib.hip) -------------------------------------------------------
+CALIB_MAX_SOURCES, CALIB_SLOTS = 32, 20                                                # DPP_CALIB_*
+
+
+def extrinsics_accumulate(rt, pose3d, status, src, T, J, rig, anchor, cal_src, max_shape_dev, acc, name='extrinsics_accumulate'):
+    """dpp_extrinsics_accumulate: one workgroup per source of `cal_src` (host ints), summing its joint pairs with the anchor source's into
+    acc [len(cal_src)][CALIB_SLOTS] float64.  max_shape_dev: None (no shape gate) or > 0 (mm)."""
+    if max_shape_dev is not None and not (np.isfinite(max_shape_dev) and max_shape_dev > 0.):
+        raise ValueError("max_shape_dev is None or a distance > 0 (mm): %r" % (max_shape_dev,))
+    cal = [int(c) for c in cal_src]
+    if not 1 <= len(cal) <= CALIB_MAX_SOURCES or int(anchor) in cal or any(not 0 <= c < rig.C for c in cal + [int(anchor)]):
+        raise ValueError("cal_src names 1 .. %d sources of %d other than the anchor %r: %r" % (CALIB_MAX_SOURCES, rig.C, anchor, cal))
+    if acc.size != len(cal) * CALIB_SLOTS or acc.dtype != np.float64:
+        raise ValueError("acc is float64 [%d][%d]" % (len(cal), CALIB_SLOTS))
+    host = (C.c_int * len(cal))(*cal)                                                  # read once per call of the entry point: kept alive
+    return Launch(rt.lib.dpp_extrinsics_accumulate,
+                  (pose3d.ptr, status.ptr, src.ptr, T, J, rig.extr.ptr, rig.C, rig.members.ptr, rig.offsets.ptr, rig.G, int(anchor),
+                   host, len(cal), 0.0 if max_shape_dev is None else float(max_shape_dev), acc.ptr),
+                  (pose3d, status, src, rig.extr, rig.members, rig.offsets, acc, host), name)
 
 
 def pose_fuse(rt, pose3d, com3d, status, src, T, J, rig, table, H, W, cam, max_dev, handover, com, fused_pose, fused_com, spread, n_out,

@@ -409,12 +409,16 @@ class MultiStreamPipeline(object):
     results carry MultiTracker's group / outlier / disagree / handed / peer_com per grouped track, `fused` holds the last tick's
     dict(pose, com, spread, n) per group, and processVideos leaves in `fused_poses` one (ticks, J, 3) array per group of the fused
     poses (world frame, mm) of the ticks in which at least one of its tracks was followed.  A grouped track that loses the hand is
-    handed its peers' centre instead of waiting for a detection."""
+    handed its peers' centre instead of waiting for a detection.
+
+    Calibration (hipdp/multitrack.py, CALIBRATION): with calibrate=dict(anchor=, max_shape_dev=, min_cond=) config['extrinsics'] may
+    hold None for devices whose pose nobody has measured; calibrateExtrinsics(ticks) finds them from the tracked hand itself.  Until
+    then nothing is fused: `fused` is []."""
 
     HAND_LEFT, HAND_RIGHT = RealtimeHandposePipeline.HAND_LEFT, RealtimeHandposePipeline.HAND_RIGHT
 
     def __init__(self, poseNet, config, di, devices, hands, comrefNet, init_com=None, seed_detect=False, sensor=None, verbose=False,
-                 max_extent=None, groups=None, max_dev=None, handover=True):
+                 max_extent=None, groups=None, max_dev=None, handover=True, calibrate=None):
         """
         :param poseNet, comrefNet: built nets or their parameters (as for RealtimeHandposePipeline), with batchSize == len(hands)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=]); fx / fy: one value, or a list with one per device
@@ -426,9 +430,10 @@ class MultiStreamPipeline(object):
         :param sensor:    as for RealtimeHandposePipeline, for all devices
         :param max_extent: None, or the largest metric width / height (mm) of a component that seed_detect may take for a hand
         :param groups, max_dev, handover: MultiTracker's, with config['extrinsics'] (one (R, t) per device)
+        :param calibrate: MultiTracker's: entries of config['extrinsics'] may then be None, to be found by calibrateExtrinsics
         """
         self.max_extent = max_extent
-        self.groups, self.max_dev, self.handover = groups, max_dev, handover
+        self.groups, self.max_dev, self.handover, self.calibrate = groups, max_dev, handover, calibrate
         self.fused, self.fused_poses = [], []
         self.config = copy.deepcopy(config)
         self.devices = list(devices)
@@ -475,7 +480,7 @@ class MultiStreamPipeline(object):
                                          cfg['cube'], [(d, h == self.HAND_RIGHT) for d, h in self.hands], sources=len(self.devices),
                                          invX=cfg.get('invX') is True, invY=cfg.get('invY') is True, fx=cfg['fx'], fy=cfg['fy'],
                                          sensor=self.sensor, extrinsics=cfg.get('extrinsics'), groups=self.groups, max_dev=self.max_dev,
-                                         handover=self.handover)
+                                         handover=self.handover, calibrate=self.calibrate)
             self._tracker_key = shapes
             self._seeded = [False] * len(self.hands)
         return self._tracker
@@ -513,6 +518,30 @@ class MultiStreamPipeline(object):
         res = mt.process(frames)
         self.fused = mt.fused
         return res
+
+    def calibrateExtrinsics(self, ticks):
+        """Find the extrinsics that config['extrinsics'] leaves open (None entries; calibrate=) from the hand the devices see: `ticks`
+        ticks from the devices through processFrames -- each adds its joint pairs to the sums on the device -- then
+        MultiTracker.finish_calibration().  Returns its report, {device: dict(R, t, n, pairs, refused, rms, cond, ok)}.  Where every fit
+        is ok the pipeline fuses from the next tick on (and config['extrinsics'] holds the fits); otherwise nothing has changed but
+        the sums, and calling this again goes on from them."""
+        self.initNets()
+        for dev in self.devices:
+            dev.start()
+        for _ in range(int(ticks)):
+            frames = self._read()
+            if frames is None:
+                break
+            self.processFrames(frames)
+        for dev in self.devices:
+            dev.stop()
+        if self._tracker is None or not self._tracker.calibrating:
+            raise RuntimeError("nothing to calibrate: no frame was read, or config['extrinsics'] leaves no device open")
+        report = self._tracker.finish_calibration()
+        if not self._tracker.calibrating:
+            ext = self._tracker.rig.extr_host
+            self.config['extrinsics'] = [(ext[c, :9].reshape(3, 3).copy(), ext[c, 9:].copy()) for c in range(len(self.devices))]
+        return report
 
     def _read(self):
         """One frame (or None) per device; None when a FileDevice has ended or no device delivered."""

@@ -25,6 +25,10 @@ mean distance of the fused pose from each camera's own -- sanity figures, not ba
 B - 1: its frames are all zero and the example marks its track lost (an empty frame moves no centre to depth 0, which is the tracker's
 only loss test; the application knows that its camera sees nothing).  In every covered tick the track is handed the centre camera 0
 sees, so it is followed again in the first tick in which the frames are back, without a detector plan; the ticks are printed.
+--calibrate-extrinsics N withholds camera 1's extrinsics from the tracker: the first N ticks add the hand's joints, as both cameras see
+them, to running sums on the device (MultiTracker calibrate=), then a rigid fit on the host gives camera 1 its (R, t) and the run goes on
+fusing with it.  Printed per calibrated camera: the joint pairs n, the fit's rms and cond, and how far (degrees, mm) the fit is from the
+withheld extrinsics.  The example prints what it gets: with untrained nets the two poses are unrelated and the figures mean nothing.
 
     python examples/realtime_multi.py --dataset icvl --data ../data/ICVL/ --seqs test_seq_1 test_seq_2
 """
@@ -88,13 +92,15 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
     H2, W2 = (H + 1) // 2, (W + 1) // 2
     di2 = upside_down_half_res_importer(di, H2, W2)
     Rz = numpy.diag([-1., -1., 1.])                                    # camera 1's frame -> world (= camera 0's frame): its own inverse
+    true_ext = [(numpy.eye(3), numpy.zeros(3)), (Rz, numpy.zeros(3))]
+    n_cal = args.calibrate_extrinsics or 0
     cfg = dict(config, fx=[config['fx'], config['fx'] / 2.], fy=[config['fy'], config['fy'] / 2.],
-               extrinsics=[(numpy.eye(3), numpy.zeros(3)), (Rz, numpy.zeros(3))])
+               extrinsics=[true_ext[0], None] if n_cal else true_ext)        # calibrating: camera 1's pose is withheld from the tracker
     c0 = numpy.asarray(seqs[0].data[0].gtorig[di.crop_joint_idx], numpy.float32)
     seeds = [c0, numpy.float32([(W2 - 1) - c0[0] / 2., (H2 - 1) - c0[1] / 2., c0[2]])]
     devices = [FileDevice(files, di), UpsideDownHalfResFileDevice(files, di)]
     msp = MultiStreamPipeline(poseNetParams, cfg, [di, di2], devices, hands, comrefNetParams, init_com=seeds, groups=[[0, 1]],
-                              max_dev=args.max_dev)
+                              max_dev=args.max_dev, calibrate=dict(anchor=0) if n_cal else None)
     drop = range(0)
     if args.drop_second:
         a, b = (int(v) for v in args.drop_second.split(':'))
@@ -102,7 +108,7 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
     msp.initNets()
     for dev in devices:
         dev.start()
-    status, spread, dist, fused = [], [], [[], []], []
+    status, spread, dist, fused, calibration = [], [], [[], []], [], []
     tick = 0
     while args.max_frames is None or tick < args.max_frames:
         frames = msp._read()
@@ -114,20 +120,34 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
                 msp._tracker.drop(1)
         res = msp.processFrames(frames)
         status.append([r['status'] for r in res])
+        tick += 1
+        mt = msp._tracker
+        if mt.calibrating:                                             # the tick added its joint pairs to the sums; nothing is fused yet
+            if tick >= n_cal:
+                for c, r in sorted(mt.finish_calibration().items()):
+                    Rt, tt = true_ext[c]
+                    cosa = (numpy.trace(r['R'].T.dot(Rt)) - 1.) / 2.
+                    r = dict(r, source=c, angle=float(numpy.degrees(numpy.arccos(numpy.clip(cosa, -1., 1.)))),
+                             shift=float(numpy.linalg.norm(r['t'] - tt)))
+                    calibration.append(r)
+                    print("camera {} after {} ticks: n {} joint pairs, rms {:.3f} mm, cond {:.4f}, ok {}; {:.3f} degrees and {:.3f} mm from "
+                          "the extrinsics it was given up with".format(c, tick, r['n'], r['rms'], r['cond'], r['ok'], r['angle'], r['shift']))
+            continue
         f = msp.fused[0]
         if f['n'] == 2:
             spread.append(float(f['spread'].mean()))
-            for t, (Rm, tv) in enumerate(cfg['extrinsics']):
+            ext = mt.rig.extr_host
+            for t in range(2):
+                Rm, tv = ext[t, :9].reshape(3, 3), ext[t, 9:]
                 world = res[t]['pose'].astype(numpy.float64).dot(Rm.T) + tv
                 dist[t].append(float(numpy.sqrt(((world - f['pose']) ** 2).sum(1)).mean()))
         if f['n'] > 0:
             fused.append(f['pose'].copy())
-        tick += 1
     for dev in devices:
         dev.stop()
     out = dict(status=status, spread=float(numpy.mean(spread)) if spread else float('nan'),
                dist=[float(numpy.mean(d)) if d else float('nan') for d in dist], fused=numpy.asarray(fused, numpy.float32), dropped=list(drop),
-               back=None)
+               back=None, calibration=calibration)
     print("{} ticks, both cameras followed in {}: mean spread {:.3f} mm, fused pose {:.3f} mm from camera 0's, {:.3f} mm from camera 1's"
           .format(tick, len(spread), out['spread'], out['dist'][0], out['dist'][1]))
     if len(drop):
@@ -156,6 +176,8 @@ def main(argv=None):
     ap.add_argument('--fuse', action='store_true', help='one sequence through two cameras, the two tracks of its hand fused in the world frame')
     ap.add_argument('--drop-second', default=None, metavar='A:B', help='with --fuse: camera 1 delivers all-zero frames in ticks A .. B - 1')
     ap.add_argument('--max-dev', type=float, default=None, help='with --fuse: MultiTracker max_dev (mm)')
+    ap.add_argument('--calibrate-extrinsics', type=int, default=None, metavar='N',
+                    help="with --fuse: camera 1's extrinsics are withheld and found again from the tracked hand in the first N ticks")
     ap.add_argument('--cache', default='./cache/')
     args = ap.parse_args(argv)
     Importer, seq_names, config = DATASETS[args.dataset]

@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 20
+#define DPP_ABI_VERSION 21
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -639,6 +639,38 @@ int dpp_pose_fuse(const float* pose3d, const float* com3d, const int* status, co
                   const int* members, const int* offsets, int G, const void* sources, int H, int W, double fx, double fy, double ux, double uy,
                   int flip_y, double max_dev, int flags, float* com, float* fused_pose, float* fused_com, float* spread, int* n_out,
                   float* peer_com, int* fstat, dpp_stream_t stream);
+
+/* ---- extrinsics of a camera from the tracked hand (ABI v21; csrc/calib.hip) ---------------------------------------------------------------
+ * dpp_pose_fuse needs an (R, t) per source.  The tracker already has the correspondences for a rigid fit: every tick the same J joints
+ * of the same hand in each camera's frame.  ONE launch at the end of a calibrating MultiTracker's tick (in place of dpp_pose_fuse) adds
+ * the tick's joint pairs to running sums; the fit itself -- Kabsch on a 3 x 3 matrix, once per calibration -- is host work
+ * (hipdp/calib.py: solve_rigid).  No counterpart in the reference: THIS PROJECT'S OWN semantics, restated in NumPy by tests/calib_ref.py
+ * and pinned to it bit for bit.  All arithmetic is float64 in the order given (no FMA contraction, no atomics).
+ *   pose3d, status, src, extrinsics, members, offsets: as for dpp_pose_fuse (read only).  Of `extrinsics` only the row of `anchor` is read.
+ *   anchor:    the source whose (R, t) is known; cal_src: n_cal sources to calibrate, a HOST array of 1 .. DPP_CALIB_MAX_SOURCES
+ *              entries that the entry point checks and copies into the launch's arguments.
+ *   acc [n_cal][DPP_CALIB_SLOTS] float64, device, updated in place: row k belongs to source c = cal_src[k].  Slots: 0 n; 1..3 sum p;
+ *              4..6 sum q; 7..15 S[d][e] = sum p_d q_e (d the row); 16 sum |p|^2; 17 sum |q|^2; 18 pairs; 19 refused.
+ * One workgroup of one wave (64 lanes) per k.  Every lane starts with all-zero private partials v[0..17].  The groups in ascending order:
+ *   a = the group's member with src == anchor, m = its member with src == c (at most one each).  The group takes part in this launch
+ *   only if both exist and status[a] == status[m] == DPP_TRACK_OK.  For joint j: p = (double) pose3d[m][j], q = R_a (double) pose3d[a][j]
+ *   + t_a by dpp_pose_fuse's row rule.  Lane l takes the joints j = l, l + 64, ... in ascending order.
+ *   Shape gate, only with max_shape_dev > 0 (0: off): lane partial sums of p and of q over its joints (from 0.0), each of the six reduced
+ *   by the butterfly below, divided by (double) J: the centroids pc, qc.  dev_j = |dist(p_j, pc) - dist(q_j, qc)| with dist =
+ *   sqrt((dx^2 + dy^2) + dz^2); per lane worst = fmax(worst, dev_j) from 0.0, over the wave v = fmax(v, shfl_xor(v, off)), off = 32 .. 1.
+ *   The pair is refused (refused += 1, nothing else changes) unless worst <= max_shape_dev.
+ *   A pair that takes part: pairs += 1, and per joint of the lane, in this order: v0 += 1; v[1 + d] += p_d; v[4 + d] += q_d;
+ *   v[7 + 3 d + e] += p_d * q_e; v16 += (p0 p0 + p1 p1) + p2 p2; v17 += (q0 q0 + q1 q1) + q2 q2.
+ * After the last group each of the 18 partials is reduced over the wave: off = 32, 16, 8, 4, 2, 1: v = v + shfl_xor(v, off) (both
+ * partners form the same sum, every lane ends with the same bits), then acc[k][i] = acc[k][i] + v_i once, acc[k][18] += pairs and
+ * acc[k][19] += refused (both counted in float64).  A source that shares no group with the anchor leaves its row as it was.
+ * DPP_E_BADARG (nothing launched): a NULL pointer, T / J / C / G below 1, G above T, n_cal outside 1 .. DPP_CALIB_MAX_SOURCES, anchor or
+ * an entry of cal_src outside [0, C), anchor in cal_src, max_shape_dev negative or not finite. */
+#define DPP_CALIB_MAX_SOURCES 32
+#define DPP_CALIB_SLOTS 20
+int dpp_extrinsics_accumulate(const float* pose3d, const int* status, const int* src, int T, int J, const double* extrinsics, int C,
+                              const int* members, const int* offsets, int G, int anchor, const int* cal_src, int n_cal, double max_shape_dev,
+                              double* acc, dpp_stream_t stream);
 
 /* ---- whole-frame hand detection by connected components (ABI v14) -------------------------------------------------------------
  * What HandDetector.detect / estimateHandsize (handdetector.py:569-632, :911-937) take from cv2.findContours, restated with

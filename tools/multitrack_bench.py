@@ -31,6 +31,13 @@ Further legs, same protocol (a child process per leg, the legs alternating, 2 pr
                                wall clock of the two ticks after the frames return by hand-over (tick: gated, restarted from its
                                peers' centre; tick: followed) against the same two ticks through acquire(t, frame) (the detector
                                plan) in the same process: the gap must exceed the larger spread.
+  --calibrate --parent DIR     the calibrating tick (calibrate=dict(anchor=0), the extrinsics of the anchor's group withheld: the plan ends in
+                               dpp_extrinsics_accumulate in dpp_pose_fuse's place) and the grouped tick after finish_calibration() at T = C =
+                               8 in two groups of four, against this tree's ungrouped tick and the PARENT's ungrouped and grouped ticks.
+                               Claims: (1) the ungrouped tick and the calibrated grouped tick are each within the larger spread of the
+                               parent's same tick; (2) the calibrating plan's device time minus the ungrouped plan's is no more than the
+                               grouped plan's minus the ungrouped plan's plus the larger spread: accumulating costs no more than the
+                               fusion launch it stands in for.  The wall clock of finish_calibration() is reported without a claim.
 --configs 1x1,8x8 overrides a leg's (T, C) list.
 
 As in tools/track_bench.py the refinement net's last layer is zeroed, so every track stays on its seed whatever the random weights
@@ -154,7 +161,45 @@ def child(args):
                 out['mixed_device_ms_' + _key(T, C)] = device_time(mt.plan())
                 out['mixed_launches_' + _key(T, C)] = len(mt.plan().launches())
             assert not mt.lost.any()
-    elif args.leg == 'fuse':
+    elif args.leg == 'calib':
+        from hipdp.multitrack import MultiTracker
+        eye = (np.eye(3), np.zeros(3))
+        for T, C in configs:
+            pnet, snet = nets(T)
+            tracks = [(t % C, bool(t // C)) for t in range(T)]
+            half = max(1, T // 2)
+            groups = [g for g in (list(range(half)), list(range(half, T))) if g]
+            # the sources of the anchor's group are withheld; the other group's cannot be found from this anchor and are given
+            withheld = sorted(set(tracks[t][0] for t in groups[0]) - {0})
+            mt = MultiTracker(rt, di, pnet, snet, 480, 640, cube, tracks, extrinsics=[None if c in withheld else eye for c in range(C)],
+                              groups=groups, max_dev=50., calibrate=dict(anchor=0))
+            for t in range(T):
+                mt.reset(t, com0)
+
+            # every camera plays the SAME frame here: the nets are untrained, and only equal views give pairs that a rigid motion fits
+            # (the identity), so that the calibrated tick fuses consistent tracks as the parent's grouped tick does; no time depends on it
+            def tick(i):
+                assert all(r['status'] == 0 for r in mt.process([frames[i % nfr]] * C))
+            for i in range(10):
+                tick(i)
+            assert mt.calibrating and mt.cal_src == withheld and mt.fused == []
+            out['calibrating_ms_' + _key(T, C)] = timed(tick)
+            out['calibrating_device_ms_' + _key(T, C)] = device_time(mt.plan())
+            out['calibrating_launches_' + _key(T, C)] = len(mt.plan().launches())
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            report = mt.finish_calibration()
+            torch.cuda.synchronize()
+            out['finish_ms_' + _key(T, C)] = [(time.perf_counter() - t0) * 1e3]
+            out['finish_pairs_' + _key(T, C)] = int(min(r['pairs'] for r in report.values()))
+            assert all(r['ok'] for r in report.values()) and not mt.calibrating, report
+            for i in range(10):
+                tick(i)
+            assert len(mt.fused) == len(groups)
+            out['calibrated_ms_' + _key(T, C)] = timed(tick)
+            out['calibrated_device_ms_' + _key(T, C)] = device_time(mt.plan())
+            out['calibrated_launches_' + _key(T, C)] = len(mt.plan().launches())
+    elif args.leg in ('fuse', 'fuse_tick'):
         from hipdp.multitrack import MultiTracker
         eye = (np.eye(3), np.zeros(3))
         for T, C in configs:
@@ -176,7 +221,7 @@ def child(args):
             out['fuse_ms_' + _key(T, C)] = timed(tick)
             out['fuse_device_ms_' + _key(T, C)] = device_time(mt.plan())
             out['fuse_launches_' + _key(T, C)] = len(mt.plan().launches())
-            if T < 2:
+            if T < 2 or args.leg == 'fuse_tick':
                 continue
             # recovery of track 0: the two ticks after the frames return, by hand-over and through the detector
             n_rec = max(1, N // 10)
@@ -249,7 +294,8 @@ def main():
     ap.add_argument('--sequence', action='store_true', help='process_sequence against the process() loop')
     ap.add_argument('--configs', default=None, help='T x C list of a leg, e.g. 1x1,8x8')
     ap.add_argument('--fuse', action='store_true', help="the grouped tick against this tree's and the parent's ungrouped tick; recovery (needs --parent)")
-    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse'], default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--calibrate', action='store_true', help="the calibrating and the calibrated tick against this tree's and the parent's ticks (needs --parent)")
+    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse', 'fuse_tick', 'calib'], default=None, help=argparse.SUPPRESS)
     ap.add_argument('--tree', default=ROOT, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.leg:
@@ -269,6 +315,8 @@ def main():
                 if p.returncode != 0 or not lines:
                     sys.stdout.write(p.stdout[-4000:])
                     raise SystemExit("%s leg in %s failed (exit %d)" % (leg, tree, p.returncode))
+                sys.stderr.write("round %d: %s leg in %s done\n" % (r, leg, tree))
+                sys.stderr.flush()
                 for k, v in json.loads(lines[-1][len('MULTITRACK_BENCH '):]).items():
                     if isinstance(v, list):
                         res.setdefault(prefix + k, []).extend(v)
@@ -333,6 +381,39 @@ def main():
                 print("recovery T = C = %d, the two ticks after the frames return: hand-over %.4f (%.4f), acquire + the same ticks %.4f (%.4f); gap "
                       "%.4f ms, larger spread %.4f ms -> %s" % ((T,) + h + a + (gap, max(h[1], a[1]), 'holds' if wins else 'DOES NOT hold')))
                 ok = wins and ok
+        return 0 if ok else 1
+    if args.calibrate:
+        if not args.parent:
+            raise SystemExit("--calibrate compares against --parent DIR")
+        cfgs = args.configs or '8x8'
+        res = run_legs([('multi', ytree, 'parent_'), ('fuse_tick', ytree, 'parent_'), ('multi', ROOT, ''), ('calib', ROOT, '')], cfgs)
+        print("the calibrating tick (dpp_extrinsics_accumulate in dpp_pose_fuse's place) and the grouped tick after finish_calibration(), two "
+              "groups of T / 2 tracks, against the ungrouped tick of this tree and the ungrouped and grouped ticks of the parent checkout; " + head)
+        print("all times in ms per tick: median (spread = max - min over the repetitions)")
+        ok = True
+        for c in cfgs.split(','):
+            T, C = (int(v) for v in c.split('x'))
+            k = _key(T, C)
+            m, y, fy = _stat(res['multi_ms_' + k]), _stat(res['parent_multi_ms_' + k]), _stat(res['parent_fuse_ms_' + k])
+            a, f = _stat(res['calibrating_ms_' + k]), _stat(res['calibrated_ms_' + k])
+            dm, dy, dfy = _stat(res['device_ms_' + k]), _stat(res['parent_device_ms_' + k]), _stat(res['parent_fuse_device_ms_' + k])
+            da, df = _stat(res['calibrating_device_ms_' + k]), _stat(res['calibrated_device_ms_' + k])
+            print("T = C = %d, wall clock: ungrouped %.4f (%.4f), parent %.4f (%.4f); calibrating %.4f (%.4f); calibrated grouped %.4f (%.4f), "
+                  "parent's grouped %.4f (%.4f)" % ((T,) + m + y + a + f + fy))
+            print("T = C = %d, plan device time: ungrouped %.4f (%.4f), parent %.4f (%.4f); calibrating %.4f (%.4f); calibrated grouped %.4f "
+                  "(%.4f), parent's grouped %.4f (%.4f); launches %d / %d / %d" % ((T,) + dm + dy + da + df + dfy + (
+                      res['launches_' + k], res['calibrating_launches_' + k], res['calibrated_launches_' + k])))
+            ok = two_sided('T = C = %d, claim 1, the ungrouped tick' % T, m, y, 'this tree', 'the parent') and ok
+            ok = two_sided('T = C = %d, claim 1, the calibrated grouped tick' % T, f, fy, 'this tree', "the parent's grouped tick") and ok
+            acc_us, fuse_us = (da[0] - dm[0]) * 1e3, (df[0] - dm[0]) * 1e3
+            bar = max(da[1], df[1], dm[1]) * 1e3
+            fits = acc_us <= fuse_us + bar
+            print("verdict T = C = %d, claim 2, plan device time over the ungrouped plan: accumulating %+.2f us, fusing %+.2f us, larger spread "
+                  "%.2f us -> %s" % (T, acc_us, fuse_us, bar, 'holds' if fits else 'DOES NOT hold'))
+            ok = fits and ok
+            fin = res['finish_ms_' + k]
+            print("finish_calibration() (one download of %d bytes per source, a 3 x 3 SVD each, one upload each, the plan dropped), wall clock: "
+                  "%s ms after %d pairs per source (no claim)" % (20 * 8, ', '.join('%.3f' % v for v in fin), res['finish_pairs_' + k]))
         return 0 if ok else 1
     if args.mixed:
         cfgs = args.configs or '8x8'
