@@ -15,8 +15,9 @@ again.  Here every launch of that plan runs once per tick for all tracks:
     pose_finish_ix                  at B = T       the sign rules per track from tflags[t]
     pose_fuse                       at G groups    only with `groups`: the tracks of one hand fused, lost tracks handed over (below)
     extrinsics_accumulate           per source     in pose_fuse's place while a source's extrinsics are being calibrated (below)
+    pose_smooth                     at T + G rows  only with `smooth`: the One-Euro filter over the tracked and the fused poses (below)
 
-so the launch count is HandTracker's whatever T and C are (plus one with `groups`).  A track names its source (`src`), its hand side and invX / invY
+so the launch count is HandTracker's whatever T and C are (plus one with `groups`, plus one with `smooth`).  A track names its source (`src`), its hand side and invX / invY
 (`tflags`) and whether it takes part in this tick (`gate`) in three small int32 device arrays; the hand side is data, not a launch
 argument, so there is one plan, not one per flag combination.  C cameras with one hand each is tracks = [(c, False) for c in
 range(C)]; both hands of one camera is tracks = [(0, False), (0, True)]; mixtures are allowed.
@@ -48,8 +49,8 @@ the plan, one workgroup per group, then
     not marked lost: it runs ungated in the next tick from its peers' centre -- one tick of outage, no detector plan, no upload.
 A track that is gated because it is lost (it lost the hand while no peer had it) is restarted by process() through reset(t, peer_com)
 in the first tick in which its peers have the hand: one small upload, as acquire makes.  Tracks in no group are left entirely alone, and
-without `groups` the tracker allocates, uploads, launches and returns exactly what it did before.  Confidence weighting, temporal
-filtering, triangulation from 2-D alone, fusing the depth frames themselves, hand size for several hands and per-source sensor options
+without `groups` the tracker allocates, uploads, launches and returns exactly what it did before.  Confidence weighting,
+triangulation from 2-D alone, fusing the depth frames themselves, hand size for several hands and per-source sensor options
 are out of scope.
 
 CALIBRATION (ABI v21; csrc/calib.hip, hipdp/calib.py; this project's own as well, restated by tests/calib_ref.py).  The (R, t) that fusion
@@ -66,6 +67,24 @@ on the tracker builds the launches of one constructed with these extrinsics.  re
 alignment of the cameras (the pairs are taken as simultaneous), intrinsics, chained calibration through a third camera (every pending
 source must share a group with the anchor), weighting by joint, drift monitoring after calibration, and re-solving on the device.
 
+SMOOTHING (ABI v22; csrc/smooth.hip; this project's own as well, restated by tests/smooth_ref.py).  The joints of a tick are what the
+pose net regressed from that tick's crop: a resting hand jitters, a fused pose jumps when a member drops out.  With
+smooth=dict(rate=, mincutoff=, beta=, dcutoff=1.0, max_hold=0) the LAST launch of the tick runs the One-Euro filter (Casiez et al., CHI
+2012: a low-pass whose cut-off mincutoff + beta * speed rises with the filtered speed) over every track's `pose` and, with `groups`,
+every group's fused pose: one workgroup per row, whatever T and G are.  Its state (ticks since the last valid sample, filtered value and
+derivative in float64) lives on the device apart from the result block and is never downloaded.  A track's sample is valid when its
+status on the device is OK; a LOST or IDLE tick is an invalid sample: the row returns its last filtered pose for up to max_hold ticks
+(`smooth` == ops.SMOOTH_HELD) and the next valid sample is filtered with Te = (ticks since the last one) / rate, so a source that
+delivers every second tick filters with 2 / rate; beyond max_hold the state is dropped (SMOOTH_EMPTY | SMOOTH_DROPPED, zeros) and the
+next valid sample starts it again (SMOOTH_INIT: pose_f == pose).  A group's sample is valid when n >= 1.  Per-track results gain pose_f,
+pose_img_f (pose_f through the track's own camera) and `smooth`, the row's word; fused[g] gains pose_f and `smooth`.  A restart from
+the host -- reset(t, com), and through it acquire, acquire_source and the automatic reset from peer_com -- and a set_hand(t, ...) that changes the hand clear
+the track's row (one 4-byte upload); a hand-over on the device does not: the hand is the same one.  While a source is being calibrated
+nothing is fused: the group rows are left out of the launch (their outputs read as zeros) and start empty after finish_calibration().
+`rate` is the tracker's one tick rate.  Out of scope: extrapolating a held pose by the filtered derivative, feeding the filtered centre
+back into the crop, per-source rates or timestamps, filtering com / com3D, and choosing mincutoff / beta for a dataset.  smooth=None:
+allocation, uploads, plan, result block and keys are those of before.
+
 acquire_source(c, frame) finds ALL hands of a source in one detector plan and starts the source's tracks from them; the detectors
 are built per source, at that source's size and focal lengths, on views of its frame slice.
 
@@ -80,12 +99,12 @@ import numpy as np
 
 from . import ops
 from .augmenter import camera_tuple
-from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, refine_stage, track_fields, valid_centre
+from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, refine_stage, smooth_fields, track_fields, valid_centre
 
 
 class MultiTracker(object):
     def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, tracks, sources=None, invX=False, invY=False, fx=None, fy=None,
-                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True, calibrate=None):
+                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None):
         """
         :param importer:   the dataset importer (the camera) of all sources, or a sequence of C importers, one per source
         :param poseNet, comrefNet: as for HandTracker, but built for a batch of T, the number of tracks: row t is track t
@@ -104,6 +123,8 @@ class MultiTracker(object):
         :param handover:   a member that lost the hand (or is an outlier) goes on from its peers' centre; False: fusion reports only
         :param calibrate:  None, or dict(anchor=0, max_shape_dev=None, min_cond=0.) (any subset): entries of `extrinsics` may then be
                            None, and those sources are calibrated against the source `anchor` from the tracked hand (CALIBRATION above)
+        :param smooth:     None, or dict(rate=, mincutoff=, beta=, dcutoff=1.0, max_hold=0): the One-Euro filter over the poses
+                           (SMOOTHING above); rate (ticks / s), mincutoff (Hz) and beta (Hz per mm / s) have no default
         """
         self.rt = rt
         tracks = [(int(s), bool(r)) for s, r in tracks]
@@ -132,6 +153,7 @@ class MultiTracker(object):
             if not (np.isfinite(cal['min_cond']) and cal['min_cond'] >= 0.):
                 raise ValueError("min_cond is a ratio >= 0: %r" % (cal['min_cond'],))
         self.max_dev, self.handover = None if max_dev is None else float(max_dev), bool(handover)
+        self.smooth = None if smooth is None else ops.smooth_spec(smooth)
         importers = self._per_source(importer, C, 'importer')
         Hs, Ws = self._per_source(H, C, 'H'), self._per_source(W, C, 'W')
         if any(int(h) != h or int(w) != w or h < 1 or w < 1 for h, w in zip(Hs, Ws)):
@@ -185,6 +207,11 @@ class MultiTracker(object):
             G = self.rig.G
             fields += [('fused_pose', (G, self.J, 3), f32), ('fused_com', (G, 3), f32), ('spread', (G, self.J), f32), ('n', (G,), i32),
                        ('peer_com', (T, 3), f32), ('fstat', (T,), i32)]
+        self.sstate = None
+        if self.smooth is not None:                                                # behind everything else; the state is a buffer of its own
+            G = 0 if self.rig is None else self.rig.G
+            fields += smooth_fields(T, self.J, G)
+            self.sstate = ops.SmoothState(rt, T + G, self.J)
         self.block = blk = ResultBlock(rt, fields)
         self.res, self._off = blk.buf, blk.offsets
         self.fused = []
@@ -251,6 +278,12 @@ class MultiTracker(object):
         self.com.view(3 * t, (1, 3)).set(com)
         self.com_host[t] = com
         self.lost[t] = False
+        self._clear_smooth(t)
+
+    def _clear_smooth(self, t):
+        """A restart or another hand: what track t follows now is not what was filtered (one 4-byte upload of since[t] = -1)."""
+        if self.sstate is not None:
+            self.sstate.clear(t)
 
     def drop(self, t):
         """Mark track t lost: the application knows what the tracker cannot see (the only loss test is a centre at depth 0) -- its
@@ -268,7 +301,10 @@ class MultiTracker(object):
     def set_hand(self, t, right):
         """HAND_RIGHT mirrors track t's pose-net input and the x coordinate of its output: a rewrite of tflags[t], not a new plan."""
         t = self._track(t)
-        self.flags_host[t] = (self.flags_host[t] & ~ops.POSE_HAND_RIGHT) | (ops.POSE_HAND_RIGHT if right else 0)
+        flags = (self.flags_host[t] & ~ops.POSE_HAND_RIGHT) | (ops.POSE_HAND_RIGHT if right else 0)
+        if flags != self.flags_host[t]:
+            self._clear_smooth(t)
+        self.flags_host[t] = flags
         self.tflags.set(self.flags_host)
 
     def detector(self, t):
@@ -303,6 +339,8 @@ class MultiTracker(object):
         ok = bool(found[0]) and valid_centre(coms[0])
         self.lost[t] = not ok
         self.com_host[t] = coms[0]
+        if ok:                                                                     # a restart, as reset(t, com) is
+            self._clear_smooth(t)
         return dict(com=coms[0], cube=cubes[0], found=ok)
 
     def source_detector(self, c, max_extent=None):
@@ -455,6 +493,14 @@ class MultiTracker(object):
                 p.add(ops.pose_fuse(rt, self.pose3d, self.com3d, self.status, self.src, T, self.J, self.rig, self.table, H, W, self.cam,
                                     self.max_dev, self.handover, self.com, self.fused_pose, self.fused_com, self.spread, self.fused_n,
                                     self.peer_com, self.fstat))
+            if self.smooth is not None:                 # the last launch of the main lane; both slots filter into the ONE state
+                blk, fusing = self.block, self.rig is not None and not self.calibrating
+                grp = {}
+                if fusing:
+                    grp = dict(fused_pose=self.fused_pose, n=self.fused_n, G=self.rig.G, fused_pose_f=blk.view('fused_pose_f'),
+                               gstat=blk.view('gstat'))
+                p.add(ops.pose_smooth(rt, self.pose3d, self.status, T, self.J, self.smooth, self.sstate, blk.view('pose_f'),
+                                      blk.view('pose_img_f'), blk.view('sstat'), cam=self.cam, src=self.src, table=self.table, **grp))
             self._plans[slot] = p
         return self._plans[slot]
 
@@ -476,6 +522,9 @@ class MultiTracker(object):
         if fusing:
             fstat, peer = f['fstat'], f['peer_com']
             self.fused = [dict(pose=f['fused_pose'][g], com=f['fused_com'][g], spread=f['spread'][g], n=int(f['n'][g])) for g in range(rig.G)]
+            if self.smooth is not None:
+                for g, d in enumerate(self.fused):
+                    d.update(pose_f=f['fused_pose_f'][g], smooth=int(f['gstat'][g]))
             self._peer_ok = (fstat & ops.FUSE_PEER_OK) != 0
         out = []
         for t in range(self.T):
@@ -494,6 +543,8 @@ class MultiTracker(object):
             elif grouped:
                 d.update(group=int(rig.group_of[t]), outlier=bool(fstat[t] & ops.FUSE_OUTLIER), disagree=bool(fstat[t] & ops.FUSE_DISAGREE),
                          handed=handed, peer_com=peer[t])
+            if self.smooth is not None:
+                d.update(pose_f=f['pose_f'][t], pose_img_f=f['pose_img_f'][t], smooth=int(f['sstat'][t]))
             if crops is not None:
                 d['crop'] = crops[t]
             out.append(d)

@@ -1058,6 +1058,70 @@ def pose_fuse(rt, pose3d, com3d, status, src, T, J, rig, table, H, W, cam, max_d
                    fused_com, spread, n_out, peer_com, fstat), name)
 
 
+# ---- tracked and fused poses smoothed over the ticks (include/dpp_hip.h, ABI v22; csrc/smooth.hip) --------------------------------------
+SMOOTH_OK, SMOOTH_INIT, SMOOTH_HELD, SMOOTH_EMPTY, SMOOTH_DROPPED = 1, 2, 4, 8, 16     # DPP_SMOOTH_*: dpp_pose_smooth's per-row word
+
+
+def smooth_spec(smooth):
+    """dict(rate=, mincutoff=, beta=, dcutoff=1.0, max_hold=0) checked on the host -> (rate, mincutoff, beta, dcutoff, max_hold).  rate
+    (ticks per second), mincutoff (Hz) and beta (Hz per mm / s) are required: there is no tuned default.  dcutoff: the paper's 1 Hz."""
+    s = dict(dcutoff=1.0, max_hold=0)
+    known = ('rate', 'mincutoff', 'beta', 'dcutoff', 'max_hold')
+    if not isinstance(smooth, dict) or set(smooth) - set(known):
+        raise ValueError("smooth takes rate, mincutoff, beta, dcutoff and max_hold, not %r" %
+                         (sorted(set(smooth) - set(known)) if isinstance(smooth, dict) else smooth,))
+    s.update(smooth)
+    missing = [k for k in known if k not in s]
+    if missing:
+        raise ValueError("smooth needs %s: no tuned default exists" % ', '.join(missing))
+    try:
+        vals = [float(s[k]) for k in known[:4]]
+        hold = int(s['max_hold'])
+    except (TypeError, ValueError):
+        raise ValueError("smooth takes numbers: %r" % (smooth,))
+    if any(not (np.isfinite(v) and v > 0.) for v in (vals[0], vals[1], vals[3])):
+        raise ValueError("rate (ticks / s), mincutoff and dcutoff (Hz) are finite and > 0: %r" % (smooth,))
+    if not (np.isfinite(vals[2]) and vals[2] >= 0.):
+        raise ValueError("beta (Hz per mm / s) is finite and >= 0: %r" % (smooth,))
+    if hold != s['max_hold'] or not 0 <= hold < 2 ** 31:
+        raise ValueError("max_hold is a number of ticks >= 0: %r" % (s['max_hold'],))
+    return tuple(vals) + (hold,)
+
+
+class SmoothState(object):
+    """dpp_pose_smooth's device state over R = T + G rows of J joints, allocated apart from anything the host downloads: `since` (int32
+    [R], -1: the row is empty), `xh` and `dxh` (float64 [R][J][3]; unread while since < 0).  clear(r): one 4-byte upload."""
+
+    def __init__(self, rt, R, J):
+        self.R, self.J = int(R), int(J)
+        self.since = rt.upload(np.full(self.R, -1, np.int32))
+        self.xh, self.dxh = rt.alloc((self.R, self.J, 3), np.float64), rt.alloc((self.R, self.J, 3), np.float64)
+        self._empty = np.full(1, -1, np.int32)
+
+    def clear(self, r):
+        self.since.view(int(r), (1,)).set(self._empty)
+
+
+def pose_smooth(rt, pose3d, status, T, J, spec, state, pose_f, pose_img_f, sstat, cam=None, src=None, table=None, fused_pose=None, n=None,
+                G=0, fused_pose_f=None, gstat=None, name='pose_smooth'):
+    """dpp_pose_smooth: one workgroup per row of `state` -- T tracks, then G groups (G = 0: no group rows, the four group buffers go
+    unread).  spec: smooth_spec's tuple.  table: an ops.SourceTable with `src`, or None with `cam` for every track."""
+    rate, mincutoff, beta, dcutoff, hold = spec
+    if state.R < T + G or state.J != J:
+        raise ValueError("the state has %d rows of %d joints, the launch %d of %d" % (state.R, state.J, T + G, J))
+    if table is not None and src is None:
+        raise ValueError("a source table needs src")
+    fx, fy, ux, uy, flip = (0., 0., 0., 0., 0) if table is not None else cam
+    grp = (fused_pose, n, fused_pose_f, gstat) if G else (None,) * 4
+    if G and any(b is None for b in grp):
+        raise ValueError("G = %d groups need fused_pose, n, fused_pose_f and gstat" % G)
+    return Launch(rt.lib.dpp_pose_smooth,
+                  (pose3d.ptr, status.ptr, _p(src), T, J, _p(grp[0]), _p(grp[1]), int(G), None if table is None else table.dev.ptr, float(fx),
+                   float(fy), float(ux), float(uy), int(flip), rate, mincutoff, beta, dcutoff, hold, state.since.ptr, state.xh.ptr,
+                   state.dxh.ptr, pose_f.ptr, pose_img_f.ptr, sstat.ptr, _p(grp[2]), _p(grp[3])),
+                  (pose3d, status, src, None if table is None else table.dev, state, pose_f, pose_img_f, sstat) + grp, name)
+
+
 def refine_com_iterative(rt, frames, partial, B, H, W, com_in, cube, fx, fy, num_iter, com_out, status, name='refine_com_iterative'):
     """dpp_refine_com_iterative: refineCoMIterative of B frames, all iterations in one launch."""
     return Launch(rt.lib.dpp_refine_com_iterative, (frames.ptr, partial.ptr, B, H, W, com_in.ptr, cube.ptr, float(fx), float(fy), int(num_iter),

@@ -138,8 +138,19 @@ def track_fields(T, J):
             ('status', (T,), np.int32), ('det', (8,), f32)]
 
 
+def smooth_fields(T, J, G=0):
+    """What a tracker with `smooth` appends to its block, behind every other field: the filtered poses, their projections and
+    dpp_pose_smooth's word per track, and per group where the tracker has groups."""
+    f32, i32 = np.float32, np.int32
+    f = [('pose_f', (T, J, 3), f32), ('pose_img_f', (T, J, 3), f32), ('sstat', (T,), i32)]
+    if G:
+        f += [('fused_pose_f', (G, J, 3), f32), ('gstat', (G,), i32)]
+    return f
+
+
 class HandTracker(object):
-    def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, hand_right=False, invX=False, invY=False, fx=None, fy=None, sensor=None):
+    def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, hand_right=False, invX=False, invY=False, fx=None, fy=None, sensor=None,
+                 smooth=None):
         """
         :param importer:   the dataset importer (camera; NYU / MSRA flip the y axis)
         :param poseNet:    the pose regressor, built for a batch of one; its output is J x 3 normalised joints
@@ -150,6 +161,8 @@ class HandTracker(object):
         :param fx, fy:     what the reference hands to HandDetector (config['fx'], config['fy']); default: the importer's
         :param sensor:     None: frames are float32 millimetres, prepared by the host.  dict(dtype='uint16' | 'float32', median=bool,
                            mirror=bool): frames are RAW sensor frames of that dtype, converted (mirrored, median-filtered) on the device
+        :param smooth:     None, or dict(rate=, mincutoff=, beta=, dcutoff=1.0, max_hold=0): the One-Euro filter over the pose as the last
+                           launch of the plan (hipdp/multitrack.py, SMOOTHING): the result gains pose_f, pose_img_f and `smooth`
         """
         self.rt, self.H, self.W = rt, int(H), int(W)
         self.importer = importer
@@ -171,7 +184,10 @@ class HandTracker(object):
         self.rec = rt.alloc(rt.lib.dpp_crop_record_bytes(), np.uint8)
         self.cube = rt.alloc((1, 3), f32)
         # everything the host reads per frame is ONE block: pose (mm), pose in image coordinates, centre (= the state), com3D, M, status
-        self.block = blk = ResultBlock(rt, track_fields(1, self.J))            # (+ the detector's seed / cube / status words: acquire)
+        self.smooth = None if smooth is None else ops.smooth_spec(smooth)
+        self.sstate = None if smooth is None else ops.SmoothState(rt, 1, self.J)   # the filter's state: never downloaded
+        # (+ the detector's seed / cube / status words: acquire; with `smooth` the filtered pose, its projection and the filter's word follow)
+        self.block = blk = ResultBlock(rt, track_fields(1, self.J) + (smooth_fields(1, self.J) if smooth is not None else []))
         self.res = blk.buf
         self.pose3d, self.pose_img, self.com, self.com3d = blk.view('pose'), blk.view('pose_img'), blk.view('com'), blk.view('com3D')
         self.M, self.status = blk.view('M'), blk.view('status')
@@ -194,6 +210,12 @@ class HandTracker(object):
             raise ValueError("reset needs a centre with a depth: %r" % (com,))
         self.com.set(com)
         self.lost = False
+        self._clear_smooth()
+
+    def _clear_smooth(self):
+        """A restart or another hand: what is followed now is not what was filtered (one 4-byte upload)."""
+        if self.sstate is not None:
+            self.sstate.clear(0)
 
     def detector(self):
         """The whole-frame detector on this tracker's buffers: frame slot 0 (and its raw buffer, with a sensor), the depth-range partials,
@@ -220,6 +242,8 @@ class HandTracker(object):
         coms, cubes, found, _, _ = det.parse(res['det'], res['com'], None if do_hand_size else self.cube_host)
         ok = bool(found[0]) and valid_centre(coms[0])
         self.lost = not ok
+        if ok:                                                                 # a restart, as reset(com) is
+            self._clear_smooth()
         return dict(com=coms[0], cube=cubes[0], found=ok)
 
     def hand_size(self, tol=0.0):
@@ -242,7 +266,10 @@ class HandTracker(object):
     def set_hand(self, right):
         """HAND_RIGHT mirrors the pose net's input and the x coordinate of its output.  (The mirroring is an argument of two
         launches, so each combination of hand / invX / invY has a plan of its own, recorded the first time it is used.)"""
-        self.flags = (self.flags & ~ops.POSE_HAND_RIGHT) | (ops.POSE_HAND_RIGHT if right else 0)
+        flags = (self.flags & ~ops.POSE_HAND_RIGHT) | (ops.POSE_HAND_RIGHT if right else 0)
+        if flags != self.flags:                                                # the other hand: not what was filtered
+            self._clear_smooth()
+        self.flags = flags
 
     def set_inv(self, invX, invY):
         self.flags = (self.flags & ~(ops.POSE_INV_X | ops.POSE_INV_Y)) | (ops.POSE_INV_X if invX else 0) | (ops.POSE_INV_Y if invY else 0)
@@ -266,12 +293,18 @@ class HandTracker(object):
             for op, side in self.peng.fwd.ops:
                 p.add(op, side)
             p.add(ops.pose_finish(rt, self.peng.out.buf, 1, self.J, self.cube, self.com3d, self.cam, self.flags, self.pose3d, self.pose_img))
+            if self.smooth is not None:
+                blk = self.block
+                p.add(ops.pose_smooth(rt, self.pose3d, self.status, 1, self.J, self.smooth, self.sstate, blk.view('pose_f'),
+                                      blk.view('pose_img_f'), blk.view('sstat'), cam=self.cam))
             self._plans[key] = p
         return self._plans[key]
 
     def _result(self, res, crop=None):
         out = dict((k, v[0]) for k, v in self.block.split(res).items() if k != 'det')      # the one track's row of every field
         out['status'] = int(out['status'])
+        if self.smooth is not None:
+            out['smooth'] = int(out.pop('sstat'))
         if crop is not None:
             out['crop'] = crop
         return out

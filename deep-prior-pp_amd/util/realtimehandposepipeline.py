@@ -57,6 +57,18 @@ class _NoHand(Exception):
     """seed_detect looked at a frame and found no hand (and there is no other seed): the frame is treated like a lost one."""
 
 
+def smoothing_figures(raw, filtered):
+    """Sanity figures of a filtered pose sequence against the raw one, both (ticks, J, 3) over the same ticks, in mm: the mean
+    frame-to-frame displacement of the raw joints, that of the filtered joints, and the mean raw-to-filtered distance (NaN where
+    there are too few ticks).  No accuracy claim: with untrained nets they only show that the filter ran."""
+    raw, filtered = numpy.asarray(raw, numpy.float64), numpy.asarray(filtered, numpy.float64)
+
+    def step(p):
+        return float(numpy.sqrt((numpy.diff(p, axis=0) ** 2).sum(-1)).mean()) if len(p) > 1 else float('nan')
+    dist = float(numpy.sqrt(((raw - filtered) ** 2).sum(-1)).mean()) if len(raw) else float('nan')
+    return dict(raw_step=step(raw), filtered_step=step(filtered), distance=dist)
+
+
 class RealtimeHandposePipeline(object):
     """Realtime pipeline for handpose estimation"""
 
@@ -72,7 +84,8 @@ class RealtimeHandposePipeline(object):
     # different detectors
     DETECTOR_COM = 0
 
-    def __init__(self, poseNet, config, di, verbose=False, comrefNet=None, init_com=None, seed_com=False, seed_detect=False, sensor=None):
+    def __init__(self, poseNet, config, di, verbose=False, comrefNet=None, init_com=None, seed_com=False, seed_detect=False, sensor=None,
+                 smooth=None):
         """
         :param poseNet:   network for pose estimation (a built net, or PoseRegNetParams / ResNetParams, with loadFile or not)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=])
@@ -84,6 +97,9 @@ class RealtimeHandposePipeline(object):
                           takes precedence over seed_com)
         :param sensor:    None (frames are float32 mm), or dict(dtype='uint16' | 'float32', median=bool, mirror=bool): frames are raw
                           sensor frames, converted / mirrored / median-filtered on the device (module docstring)
+        :param smooth:    None, or HandTracker's dict(rate=, mincutoff=, beta=[, dcutoff=, max_hold=]): processFrame's result gains the
+                          One-Euro-filtered pose_f / pose_img_f and the filter's word `smooth` beside the raw keys, and processVideo
+                          leaves the filtered poses of the frames it returns in `poses_f`
         """
         self.importer = di
         self.poseNet = poseNet
@@ -107,6 +123,8 @@ class RealtimeHandposePipeline(object):
         self.show_crop = False
         self._tracker = None
         self.sensor = None if sensor is None else dict(sensor)
+        self.smooth = None if smooth is None else dict(smooth)
+        self.poses_f = None
 
     def initNets(self):
         """Build the nets from their parameters (loading loadFile where set) and compile their forward plans (:118-141)."""
@@ -247,7 +265,7 @@ class RealtimeHandposePipeline(object):
         t = self._tracker
         if t is None or (t.H, t.W) != (H, W) or (t.fx, t.fy) != (abs(float(cfg['fx'])), abs(float(cfg['fy']))):
             t = self._tracker = HandTracker(default_runtime(), self.importer, self.poseNet, self.comrefNet, H, W, cfg['cube'],
-                                            fx=cfg['fx'], fy=cfg['fy'], sensor=self.sensor)
+                                            fx=cfg['fx'], fy=cfg['fy'], sensor=self.sensor, smooth=self.smooth)
         if tuple(numpy.float32(cfg['cube'])) != tuple(t.cube_host):
             t.set_cube(cfg['cube'])
         t.set_hand(self.hand.value == self.HAND_RIGHT)
@@ -257,13 +275,17 @@ class RealtimeHandposePipeline(object):
     def _no_hand_result(self):
         """What processFrame answers for a frame in which seed_detect finds no hand: the shape of a LOST frame's result (status 1,
         zeros, M = identity); the pipeline keeps no centre, so the next frame is searched again."""
+        from hipdp import ops
         J = self.poseNet.cfgParams.outputDim[1] // 3
         self.lastcom = (0, 0, 0)
         self._devcom = self.lastcom
         z3 = numpy.zeros(3, numpy.float32)
         self.sync.update(fid=self.sync['fid'] + 1, com3D=z3, M=numpy.eye(3, dtype=numpy.float32))
-        return dict(pose=numpy.zeros((J, 3), numpy.float32), pose_img=numpy.zeros((J, 3), numpy.float32), com=z3.copy(), com3D=z3.copy(),
-                    M=numpy.eye(3, dtype=numpy.float32), status=1)
+        res = dict(pose=numpy.zeros((J, 3), numpy.float32), pose_img=numpy.zeros((J, 3), numpy.float32), com=z3.copy(), com3D=z3.copy(),
+                   M=numpy.eye(3, dtype=numpy.float32), status=1)
+        if self.smooth is not None:                    # nothing ran: nothing was filtered
+            res.update(pose_f=numpy.zeros((J, 3), numpy.float32), pose_img_f=numpy.zeros((J, 3), numpy.float32), smooth=ops.SMOOTH_EMPTY)
+        return res
 
     def processFrame(self, frame):
         """detect + estimatePose + the de-normalisation of one frame as ONE device plan: the tracker's result dict (pose in mm)."""
@@ -293,7 +315,7 @@ class RealtimeHandposePipeline(object):
         a lost frame, or one in which no hand is found, is skipped instead and the next frame is searched again."""
         self.initNets()
         device.start()
-        poses = []
+        poses, poses_f = [], []
         times = []
         while not self.stop.value and (max_frames is None or len(poses) < max_frames):
             try:
@@ -312,11 +334,14 @@ class RealtimeHandposePipeline(object):
                     continue
                 break
             poses.append(res['pose'].copy())
+            if self.smooth is not None:
+                poses_f.append(res['pose_f'].copy())
             if self.verbose is True:
                 print("{}ms frame".format(times[-1] * 1000.))
         device.stop()
         self.frame_times = times
         J = self.poseNet.cfgParams.outputDim[1] // 3
+        self.poses_f = None if self.smooth is None else numpy.asarray(poses_f, numpy.float32).reshape(-1, J, 3)
         return numpy.asarray(poses, numpy.float32).reshape(-1, J, 3)
 
     def calibrateHandsize(self, device, num_frames=None):
@@ -413,12 +438,16 @@ class MultiStreamPipeline(object):
 
     Calibration (hipdp/multitrack.py, CALIBRATION): with calibrate=dict(anchor=, max_shape_dev=, min_cond=) config['extrinsics'] may
     hold None for devices whose pose nobody has measured; calibrateExtrinsics(ticks) finds them from the tracked hand itself.  Until
-    then nothing is fused: `fused` is []."""
+    then nothing is fused: `fused` is [].
+
+    Smoothing (hipdp/multitrack.py, SMOOTHING): smooth=dict(rate=, mincutoff=, beta=[, dcutoff=, max_hold=]) goes to MultiTracker: the
+    results carry pose_f / pose_img_f / smooth beside the raw keys, `fused` pose_f / smooth, and processVideos leaves in `poses_f` /
+    `fused_poses_f` the filtered poses of exactly the ticks that its return value / `fused_poses` hold."""
 
     HAND_LEFT, HAND_RIGHT = RealtimeHandposePipeline.HAND_LEFT, RealtimeHandposePipeline.HAND_RIGHT
 
     def __init__(self, poseNet, config, di, devices, hands, comrefNet, init_com=None, seed_detect=False, sensor=None, verbose=False,
-                 max_extent=None, groups=None, max_dev=None, handover=True, calibrate=None):
+                 max_extent=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None):
         """
         :param poseNet, comrefNet: built nets or their parameters (as for RealtimeHandposePipeline), with batchSize == len(hands)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=]); fx / fy: one value, or a list with one per device
@@ -431,7 +460,10 @@ class MultiStreamPipeline(object):
         :param max_extent: None, or the largest metric width / height (mm) of a component that seed_detect may take for a hand
         :param groups, max_dev, handover: MultiTracker's, with config['extrinsics'] (one (R, t) per device)
         :param calibrate: MultiTracker's: entries of config['extrinsics'] may then be None, to be found by calibrateExtrinsics
+        :param smooth:    MultiTracker's: the One-Euro filter over the tracked and the fused poses
         """
+        self.smooth = None if smooth is None else dict(smooth)
+        self.poses_f, self.fused_poses_f = None, None
         self.max_extent = max_extent
         self.groups, self.max_dev, self.handover, self.calibrate = groups, max_dev, handover, calibrate
         self.fused, self.fused_poses = [], []
@@ -480,7 +512,7 @@ class MultiStreamPipeline(object):
                                          cfg['cube'], [(d, h == self.HAND_RIGHT) for d, h in self.hands], sources=len(self.devices),
                                          invX=cfg.get('invX') is True, invY=cfg.get('invY') is True, fx=cfg['fx'], fy=cfg['fy'],
                                          sensor=self.sensor, extrinsics=cfg.get('extrinsics'), groups=self.groups, max_dev=self.max_dev,
-                                         handover=self.handover, calibrate=self.calibrate)
+                                         handover=self.handover, calibrate=self.calibrate, smooth=self.smooth)
             self._tracker_key = shapes
             self._seeded = [False] * len(self.hands)
         return self._tracker
@@ -577,14 +609,19 @@ class MultiStreamPipeline(object):
             return not self.stop.value and (max_frames is None or state['ticks'] < max_frames) and not state['ended']
 
         fused_poses = [[] for _ in (self.groups or [])]
+        poses_f, fused_poses_f = [[] for _ in self.hands], [[] for _ in (self.groups or [])]
 
         def collect(res, tick, fused):
             for g, f in enumerate(fused):
                 if f['n'] > 0:
                     fused_poses[g].append(f['pose'].copy())
+                    if self.smooth is not None:
+                        fused_poses_f[g].append(f['pose_f'].copy())
             for t, r in enumerate(res):
                 if r['status'] == 0:
                     poses[t].append(r['pose'].copy())
+                    if self.smooth is not None:
+                        poses_f[t].append(r['pose_f'].copy())
                 elif r['status'] == 1:
                     print("Track {} lost (or no hand) in tick {}.".format(t, tick))
 
@@ -630,4 +667,7 @@ class MultiStreamPipeline(object):
         self.frame_times = times
         J = self.poseNet.cfgParams.outputDim[1] // 3
         self.fused_poses = [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in fused_poses]
+        if self.smooth is not None:
+            self.poses_f = [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in poses_f]
+            self.fused_poses_f = [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in fused_poses_f]
         return [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in poses]

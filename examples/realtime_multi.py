@@ -30,6 +30,11 @@ them, to running sums on the device (MultiTracker calibrate=), then a rigid fit 
 fusing with it.  Printed per calibrated camera: the joint pairs n, the fit's rms and cond, and how far (degrees, mm) the fit is from the
 withheld extrinsics.  The example prints what it gets: with untrained nets the two poses are unrelated and the figures mean nothing.
 
+--smooth RATE MINCUTOFF BETA [--hold N] runs the One-Euro filter over every track's joints (with --fuse: over the fused joints too) as
+the plan's last launch (MultiTracker smooth=, this project's own) and prints two sanity figures, not bars: the mean frame-to-frame
+displacement of the raw and of the filtered joints, and the mean raw-to-filtered distance -- of the fused pose with --fuse, else of
+every track.
+
     python examples/realtime_multi.py --dataset icvl --data ../data/ICVL/ --seqs test_seq_1 test_seq_2
 """
 import argparse
@@ -47,7 +52,7 @@ from net.resnet import ResNetParams  # noqa: E402
 from net.scalenet import ScaleNetParams  # noqa: E402
 from util.cameradevice import FileDevice  # noqa: E402
 from util.handpose_evaluation import HandposeEvaluation  # noqa: E402
-from util.realtimehandposepipeline import MultiStreamPipeline  # noqa: E402
+from util.realtimehandposepipeline import MultiStreamPipeline, smoothing_figures  # noqa: E402
 
 DATASETS = {'icvl': (ICVLImporter, ('test_seq_1', 'test_seq_2'), {'fx': 241.42, 'fy': 241.42, 'cube': (250, 250, 250)}),
             'nyu': (NYUImporter, ('test_1', 'test_2'), {'fx': 588., 'fy': 587., 'cube': (300, 300, 300)}),
@@ -85,6 +90,18 @@ def upside_down_half_res_importer(di, H2, W2):
     return half
 
 
+def smooth_arg(args):
+    """{} without --smooth, else the smooth= keyword of the pipeline."""
+    if args.smooth is None:
+        return {}
+    return dict(smooth=dict(rate=args.smooth[0], mincutoff=args.smooth[1], beta=args.smooth[2], max_hold=args.hold))
+
+
+def print_smoothing(what, fig):
+    print("{}, smoothing (sanity figures): mean frame-to-frame displacement {raw_step:.3f} mm raw, {filtered_step:.3f} mm filtered; "
+          "mean raw-to-filtered distance {distance:.3f} mm".format(what, **fig))
+
+
 def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
     """--fuse: one sequence through two cameras, the two tracks of its hand fused; returns a dict of what is printed."""
     files = [f.fileName for f in seqs[0].data]
@@ -100,7 +117,7 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
     seeds = [c0, numpy.float32([(W2 - 1) - c0[0] / 2., (H2 - 1) - c0[1] / 2., c0[2]])]
     devices = [FileDevice(files, di), UpsideDownHalfResFileDevice(files, di)]
     msp = MultiStreamPipeline(poseNetParams, cfg, [di, di2], devices, hands, comrefNetParams, init_com=seeds, groups=[[0, 1]],
-                              max_dev=args.max_dev, calibrate=dict(anchor=0) if n_cal else None)
+                              max_dev=args.max_dev, calibrate=dict(anchor=0) if n_cal else None, **smooth_arg(args))
     drop = range(0)
     if args.drop_second:
         a, b = (int(v) for v in args.drop_second.split(':'))
@@ -108,7 +125,7 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
     msp.initNets()
     for dev in devices:
         dev.start()
-    status, spread, dist, fused, calibration = [], [], [[], []], [], []
+    status, spread, dist, fused, calibration, fused_f = [], [], [[], []], [], [], []
     tick = 0
     while args.max_frames is None or tick < args.max_frames:
         frames = msp._read()
@@ -143,6 +160,8 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
                 dist[t].append(float(numpy.sqrt(((world - f['pose']) ** 2).sum(1)).mean()))
         if f['n'] > 0:
             fused.append(f['pose'].copy())
+            if args.smooth is not None:
+                fused_f.append(f['pose_f'].copy())
     for dev in devices:
         dev.stop()
     out = dict(status=status, spread=float(numpy.mean(spread)) if spread else float('nan'),
@@ -155,6 +174,9 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
         out['back'] = after[0] if after else None
         print("camera 1 covered in ticks {} .. {}; its track is followed again in tick {} (expected: {}, the tick after the last covered one)"
               .format(drop[0], drop[-1], out['back'], drop[-1] + 1))
+    if args.smooth is not None:
+        out['smooth'] = smoothing_figures(fused, fused_f)
+        print_smoothing("fused pose", out['smooth'])
     return out
 
 
@@ -178,6 +200,9 @@ def main(argv=None):
     ap.add_argument('--max-dev', type=float, default=None, help='with --fuse: MultiTracker max_dev (mm)')
     ap.add_argument('--calibrate-extrinsics', type=int, default=None, metavar='N',
                     help="with --fuse: camera 1's extrinsics are withheld and found again from the tracked hand in the first N ticks")
+    ap.add_argument('--smooth', nargs=3, type=float, default=None, metavar=('RATE', 'MINCUTOFF', 'BETA'),
+                    help='One-Euro filter over the joints: ticks per second, Hz, Hz per mm/s')
+    ap.add_argument('--hold', type=int, default=0, metavar='N', help='with --smooth: ticks a lost track keeps its last filtered pose (max_hold)')
     ap.add_argument('--cache', default='./cache/')
     args = ap.parse_args(argv)
     Importer, seq_names, config = DATASETS[args.dataset]
@@ -217,7 +242,7 @@ def main(argv=None):
         else:
             dis, cfg, devices, seeds = di, config, [FileDevice(f, di) for f in files], init
         msp = MultiStreamPipeline(poseNetParams, cfg, dis, devices, hands, comrefNetParams, init_com=seeds, seed_detect=args.seed != 'gt',
-                                  max_extent=args.max_extent)
+                                  max_extent=args.max_extent, **smooth_arg(args))
         return msp, msp.processVideos(max_frames=args.max_frames, overlapped=args.overlapped)
     msp, poses = run(args.half_res_second)
     t = numpy.asarray(msp.frame_times[1:] or msp.frame_times)         # the first tick records the plan
@@ -235,6 +260,11 @@ def main(argv=None):
         diff = float(numpy.abs(full[2][:n] - poses[2][:n]).mean()) if n else float('nan')
         print("camera 1 at half resolution against full resolution, mean difference over {} ticks: {:.3f} mm".format(n, diff))
         return poses, errs, diff
+    if args.smooth is not None:
+        figs = [smoothing_figures(p, pf) for p, pf in zip(poses, msp.poses_f)]
+        for t, fig in enumerate(figs):
+            print_smoothing("track {}".format(t), fig)
+        return poses, errs, figs
     return poses, errs
 
 

@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 21
+#define DPP_ABI_VERSION 22
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -671,6 +671,49 @@ int dpp_pose_fuse(const float* pose3d, const float* com3d, const int* status, co
 int dpp_extrinsics_accumulate(const float* pose3d, const int* status, const int* src, int T, int J, const double* extrinsics, int C,
                               const int* members, const int* offsets, int G, int anchor, const int* cal_src, int n_cal, double max_shape_dev,
                               double* acc, dpp_stream_t stream);
+
+/* ---- tracked and fused poses smoothed over the ticks (ABI v22; csrc/smooth.hip) ----------------------------------------------------------
+ * The trackers return every tick's joints as the pose net regressed them from that tick's crop; nothing connects one tick to the next.
+ * ONE launch at the very end of a tracker's tick (behind dpp_pose_fuse / dpp_extrinsics_accumulate where the plan has one) runs the
+ * One-Euro filter (Casiez, Roussel, Vogel, CHI 2012: a first-order low-pass whose cut-off rises with the filtered speed) over every
+ * track's pose and every group's fused pose.  Its state lives on the device and is never downloaded.  The reference has no counterpart
+ * (it draws what the net returns): these semantics are THIS PROJECT'S OWN, restated in NumPy float64 by tests/smooth_ref.py and pinned
+ * to it bit for bit.  All arithmetic is float64 in the order given (+ - * / sqrt, no FMA contraction); every output is rounded to
+ * float32 once.
+ * Rows.  R = T + G rows of J x 3 values.  Row r < T is track r: its sample x is pose3d[r] (float32, camera frame, mm), VALID iff
+ *   status[r] == DPP_TRACK_OK.  Row T + g is group g: its sample is fused_pose[g] (float32, world frame), VALID iff n[g] >= 1.  G may be
+ *   0: fused_pose, n, fused_pose_f and gstat may then be NULL.
+ * State, device memory, updated in place: since [R] int32 -- the ticks since the row's last valid sample, -1: the row is empty (what a
+ *   fresh state holds, and what the host writes to clear a row); xh [R][J][3] float64, the filtered value; dxh [R][J][3] float64, the
+ *   filtered derivative (mm / s).  xh / dxh are not read while since < 0, so only `since` needs initialising.
+ * Parameters, launch scalars: rate (ticks per second), mincutoff (Hz), beta (Hz per mm / s), dcutoff (Hz), max_hold (ticks).
+ * alpha(fc, Te) = r / (r + 1.0) with r = (6.283185307179586 * fc) * Te.  Per row:
+ *   valid, since < 0:   xh = x, dxh = 0, since = 0; word DPP_SMOOTH_INIT.
+ *   valid, since >= 0:  Te = (double)(since + 1) / rate, ad = alpha(dcutoff, Te).  Per joint and coordinate d = (x - xh) / Te, then
+ *                       dxh = ad * d + (1.0 - ad) * dxh.  Per joint speed = sqrt((dxh0^2 + dxh1^2) + dxh2^2), fc = mincutoff + beta * speed,
+ *                       a = alpha(fc, Te); per coordinate xh = a * x + (1.0 - a) * xh.  Then since = 0; word DPP_SMOOTH_OK.
+ *   not valid, since < 0:                       word DPP_SMOOTH_EMPTY, all outputs of the row zero.
+ *   not valid, since >= 0, since + 1 > max_hold: since = -1 (the state is dropped; xh / dxh keep their bits, unread); word
+ *                       DPP_SMOOTH_EMPTY | DPP_SMOOTH_DROPPED, all outputs of the row zero.
+ *   not valid, since >= 0, otherwise:           since += 1; word DPP_SMOOTH_HELD, the outputs are those of the unchanged xh.
+ * Outputs: pose_f [T][J][3] = (float) xh; pose_img_f [T][J][3] = that float32 joint projected by the track's own camera with
+ *   joint3DToImg on a float32 array, exactly as dpp_pose_finish projects pose3d (an EMPTY row is all zeros: it is not projected);
+ *   sstat [T] the track's word; fused_pose_f [G][J][3] and gstat [G] the same for the group rows, which have no projection.
+ * Camera: sources == NULL (src may then be NULL too: every track has the camera of the launch scalars) or the ABI v19 table with src [T].
+ * One workgroup of one wave per row; lanes stride over the joints, a joint's three coordinates in one lane; vector loads and stores
+ * only, no atomics.  Ticks on one state must be stream-ordered.
+ * DPP_E_BADARG (nothing launched): a NULL required pointer (the four group pointers may be NULL only with G == 0; sources and src may
+ * be NULL together, a table needs src); T / J below 1, G or max_hold below 0; rate, mincutoff or dcutoff not finite or <= 0; beta not
+ * finite or < 0; without a table a zero focal length. */
+#define DPP_SMOOTH_OK 1
+#define DPP_SMOOTH_INIT 2
+#define DPP_SMOOTH_HELD 4
+#define DPP_SMOOTH_EMPTY 8
+#define DPP_SMOOTH_DROPPED 16
+int dpp_pose_smooth(const float* pose3d, const int* status, const int* src, int T, int J, const float* fused_pose, const int* n, int G,
+                    const void* sources, double fx, double fy, double ux, double uy, int flip_y, double rate, double mincutoff, double beta,
+                    double dcutoff, int max_hold, int* since, double* xh, double* dxh, float* pose_f, float* pose_img_f, int* sstat,
+                    float* fused_pose_f, int* gstat, dpp_stream_t stream);
 
 /* ---- whole-frame hand detection by connected components (ABI v14) -------------------------------------------------------------
  * What HandDetector.detect / estimateHandsize (handdetector.py:569-632, :911-937) take from cv2.findContours, restated with

@@ -38,6 +38,13 @@ Further legs, same protocol (a child process per leg, the legs alternating, 2 pr
                                parent's same tick; (2) the calibrating plan's device time minus the ungrouped plan's is no more than the
                                grouped plan's minus the ungrouped plan's plus the larger spread: accumulating costs no more than the
                                fusion launch it stands in for.  The wall clock of finish_calibration() is reported without a claim.
+  --smooth --parent DIR        the grouped tick with smooth=dict(rate=30, mincutoff=1, beta=0.007, max_hold=2) (one more launch,
+                               dpp_pose_smooth, over T + 2 rows) at T = C = 8 in two groups of four, against this tree's grouped tick
+                               without `smooth` and the PARENT's grouped tick.  Claims: (1) without `smooth` the tick and the plan's
+                               back-to-back device time are each within the larger spread of the parent's; (2) the plan with `smooth`
+                               costs at most ONE launch more in device time than the plan without: the bar is the average launch of the
+                               smoothing plan (its device time over its launch count, from the same job) plus the larger spread of the
+                               two device-time legs.
 --configs 1x1,8x8 overrides a leg's (T, C) list.
 
 As in tools/track_bench.py the refinement net's last layer is zeroed, so every track stays on its seed whatever the random weights
@@ -199,6 +206,31 @@ def child(args):
             out['calibrated_ms_' + _key(T, C)] = timed(tick)
             out['calibrated_device_ms_' + _key(T, C)] = device_time(mt.plan())
             out['calibrated_launches_' + _key(T, C)] = len(mt.plan().launches())
+    elif args.leg == 'smooth':
+        from hipdp import ops
+        from hipdp.multitrack import MultiTracker
+        eye = (np.eye(3), np.zeros(3))
+        for T, C in configs:
+            pnet, snet = nets(T)
+            tracks = [(t % C, bool(t // C)) for t in range(T)]
+            half = max(1, T // 2)
+            groups = [g for g in (list(range(half)), list(range(half, T))) if g]
+            mt = MultiTracker(rt, di, pnet, snet, 480, 640, cube, tracks, extrinsics=[eye] * C, groups=groups, max_dev=50.,
+                              smooth=dict(rate=30., mincutoff=1., beta=0.007, max_hold=2))
+            for t in range(T):
+                mt.reset(t, com0)
+
+            def tick(i):
+                res = mt.process(tick_frames(i, C))
+                assert all(r['status'] == 0 and r['smooth'] == ops.SMOOTH_OK for r in res) and all(f['smooth'] == ops.SMOOTH_OK for f in mt.fused)
+            mt.process(tick_frames(0, C))                               # the tick that starts every row
+            for i in range(10):
+                tick(i)
+            assert mt.plan().launches()[-1].name == 'pose_smooth'
+            out['smooth_ms_' + _key(T, C)] = timed(tick)
+            out['smooth_device_ms_' + _key(T, C)] = device_time(mt.plan())
+            out['smooth_launches_' + _key(T, C)] = len(mt.plan().launches())
+            out['smooth_block_bytes_' + _key(T, C)] = 4 * int(mt.res.size)
     elif args.leg in ('fuse', 'fuse_tick'):
         from hipdp.multitrack import MultiTracker
         eye = (np.eye(3), np.zeros(3))
@@ -221,6 +253,7 @@ def child(args):
             out['fuse_ms_' + _key(T, C)] = timed(tick)
             out['fuse_device_ms_' + _key(T, C)] = device_time(mt.plan())
             out['fuse_launches_' + _key(T, C)] = len(mt.plan().launches())
+            out['fuse_block_bytes_' + _key(T, C)] = 4 * int(mt.res.size)
             if T < 2 or args.leg == 'fuse_tick':
                 continue
             # recovery of track 0: the two ticks after the frames return, by hand-over and through the detector
@@ -295,7 +328,8 @@ def main():
     ap.add_argument('--configs', default=None, help='T x C list of a leg, e.g. 1x1,8x8')
     ap.add_argument('--fuse', action='store_true', help="the grouped tick against this tree's and the parent's ungrouped tick; recovery (needs --parent)")
     ap.add_argument('--calibrate', action='store_true', help="the calibrating and the calibrated tick against this tree's and the parent's ticks (needs --parent)")
-    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse', 'fuse_tick', 'calib'], default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--smooth', action='store_true', help="the grouped tick with the One-Euro filter against this tree's and the parent's grouped tick (needs --parent)")
+    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse', 'fuse_tick', 'calib', 'smooth'], default=None, help=argparse.SUPPRESS)
     ap.add_argument('--tree', default=ROOT, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.leg:
@@ -381,6 +415,36 @@ def main():
                 print("recovery T = C = %d, the two ticks after the frames return: hand-over %.4f (%.4f), acquire + the same ticks %.4f (%.4f); gap "
                       "%.4f ms, larger spread %.4f ms -> %s" % ((T,) + h + a + (gap, max(h[1], a[1]), 'holds' if wins else 'DOES NOT hold')))
                 ok = wins and ok
+        return 0 if ok else 1
+    if args.smooth:
+        if not args.parent:
+            raise SystemExit("--smooth compares against --parent DIR")
+        cfgs = args.configs or '8x8'
+        res = run_legs([('fuse_tick', ytree, 'parent_'), ('fuse_tick', ROOT, ''), ('smooth', ROOT, '')], cfgs)
+        print("the grouped tick with smooth= (two groups of T / 2 tracks; one more launch, dpp_pose_smooth, over T + 2 rows) against the grouped "
+              "tick without it of this tree and of the parent checkout; " + head)
+        print("all times in ms per tick: median (spread = max - min over the repetitions)")
+        ok = True
+        for c in cfgs.split(','):
+            T, C = (int(v) for v in c.split('x'))
+            k = _key(T, C)
+            s, f, y = _stat(res['smooth_ms_' + k]), _stat(res['fuse_ms_' + k]), _stat(res['parent_fuse_ms_' + k])
+            ds, df, dy = _stat(res['smooth_device_ms_' + k]), _stat(res['fuse_device_ms_' + k]), _stat(res['parent_fuse_device_ms_' + k])
+            nl = res['smooth_launches_' + k]
+            per = ds[0] / nl
+            print("T = C = %d, wall clock: with smooth %.4f (%.4f), without %.4f (%.4f), parent %.4f (%.4f)" % ((T,) + s + f + y))
+            print("T = C = %d, plan device time: with smooth %.4f (%.4f), without %.4f (%.4f), parent %.4f (%.4f); launches %d / %d / %d; device "
+                  "time per launch of the smoothing plan %.2f us" % ((T,) + ds + df + dy + (nl, res['fuse_launches_' + k], res['parent_fuse_launches_' + k], per * 1e3)))
+            ok = two_sided('T = C = %d, claim 1, the tick without smooth' % T, f, y, 'this tree', 'the parent') and ok
+            ok = two_sided('T = C = %d, claim 1, the plan device time without smooth' % T, df, dy, 'this tree', 'the parent') and ok
+            extra, bar = (ds[0] - df[0]) * 1e3, (per + max(ds[1], df[1])) * 1e3
+            fits = extra <= bar
+            print("verdict T = C = %d, claim 2, plan device time with smooth over the plan without: %+.2f us; one average launch %.2f us + larger "
+                  "spread %.2f us = %.2f us -> %s" % (T, extra, per * 1e3, max(ds[1], df[1]) * 1e3, bar, 'holds' if fits else 'DOES NOT hold'))
+            if not fits:
+                print("  claim 2 is missed by %.2f us" % (extra - bar))
+            print("  wall clock with smooth over without: %+.4f ms (no claim: the download grows by %d bytes)" % (s[0] - f[0], res['smooth_block_bytes_' + k] - res['fuse_block_bytes_' + k]))
+            ok = fits and ok
         return 0 if ok else 1
     if args.calibrate:
         if not args.parent:
