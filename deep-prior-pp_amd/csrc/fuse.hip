@@ -1,4 +1,5 @@
-// fuse.hip -- tracks of ONE hand seen by several calibrated cameras, fused at the end of MultiTracker's tick (ABI v20).
+// fuse.hip -- tracks of ONE hand seen by several calibrated cameras, fused at the end of MultiTracker's tick (ABI v20; per-joint weights:
+// ABI v23, dpp_pose_fuse_w -- the same kernel, whose unweighted arithmetic is untouched: `weight` is null for dpp_pose_fuse).
 //
 // THIS PROJECT'S OWN semantics: the reference has one device and one camera and nothing to compare against.  They are
 // stated in include/dpp_hip.h and restated in NumPy by tests/fuse_ref.py, to which every output is pinned bit for bit: all
@@ -23,7 +24,8 @@ __global__ __launch_bounds__(DPP_WAVE) void pose_fuse_kernel(const float* __rest
                                                              int W, AugCam cam0, double max_dev, int flags, float* com,
                                                              float* __restrict__ fused_pose, float* __restrict__ fused_com,
                                                              float* __restrict__ spread, int* __restrict__ n_out,
-                                                             float* __restrict__ peer_com, int* __restrict__ fstat) {
+                                                             float* __restrict__ peer_com, int* __restrict__ fstat,
+                                                             const float* __restrict__ weight, float* __restrict__ fused_weight) {
     __shared__ double s_w[FUSE_MAX][3];          // world centre of member k (contributors only)
     __shared__ double s_sort[FUSE_MAX];
     __shared__ int s_use[FUSE_MAX];              // member k is an inlier: it takes part in the fused outputs
@@ -130,7 +132,8 @@ __global__ __launch_bounds__(DPP_WAVE) void pose_fuse_kernel(const float* __rest
     }
     const int n = s_n;
     for (int j = tid; j < J; j += DPP_WAVE) {
-        double sum[3] = {0.0, 0.0, 0.0};
+        double sum[3] = {0.0, 0.0, 0.0}, wsum[3] = {0.0, 0.0, 0.0}, sw = 0.0;
+        float wmax = 0.0f;
         for (int k = 0; k < K; ++k) {
             if (!s_use[k]) continue;
             const int m = mem[k];
@@ -139,13 +142,21 @@ __global__ __launch_bounds__(DPP_WAVE) void pose_fuse_kernel(const float* __rest
             double w[3];
             to_world(extr + (size_t)src[m] * 12, p, w);
             for (int d = 0; d < 3; ++d) sum[d] = sum[d] + w[d];
+            if (weight) {                                                      // a product, then an add: the unit has no FMA contraction
+                const float wm = weight[(size_t)m * J + j];
+                sw = sw + (double)wm;
+                for (int d = 0; d < 3; ++d) wsum[d] = wsum[d] + (double)wm * w[d];
+                if (wm > wmax) wmax = wm;
+            }
         }
+        const bool weighted = weight && sw > 0.0;                              // somebody sees the joint; else: the plain mean, as without weights
         double mean[3] = {0.0, 0.0, 0.0}, worst = 0.0;
         if (n) {
-            for (int d = 0; d < 3; ++d) mean[d] = sum[d] / (double)n;
+            for (int d = 0; d < 3; ++d) mean[d] = weighted ? wsum[d] / sw : sum[d] / (double)n;
             for (int k = 0; k < K; ++k) {                                      // (the world joints again: cheaper than keeping K x J of them)
                 if (!s_use[k]) continue;
                 const int m = mem[k];
+                if (weighted && !(weight[(size_t)m * J + j] > 0.0f)) continue;  // the spread of those that took part
                 const float* q = pose3d + ((size_t)m * J + j) * 3;
                 const double p[3] = {(double)q[0], (double)q[1], (double)q[2]};
                 double w[3];
@@ -157,15 +168,18 @@ __global__ __launch_bounds__(DPP_WAVE) void pose_fuse_kernel(const float* __rest
         float* fp = fused_pose + ((size_t)g * J + j) * 3;
         for (int d = 0; d < 3; ++d) fp[d] = (float)mean[d];
         spread[(size_t)g * J + j] = (float)worst;
+        if (weight) fused_weight[(size_t)g * J + j] = (n && weighted) ? wmax : 0.0f;
     }
 }
 
 }  // namespace
 
-extern "C" int dpp_pose_fuse(const float* pose3d, const float* com3d, const int* status, const int* src, int T, int J, const double* extrinsics,
-                             int C, const int* members, const int* offsets, int G, const void* sources, int H, int W, double fx, double fy,
-                             double ux, double uy, int flip_y, double max_dev, int flags, float* com, float* fused_pose, float* fused_com,
-                             float* spread, int* n_out, float* peer_com, int* fstat, dpp_stream_t stream) {
+// The argument checks and the one launch of both entry points.  weight == nullptr: dpp_pose_fuse, whose bytes the weighted form leaves alone.
+static int launch_pose_fuse(const float* pose3d, const float* com3d, const int* status, const int* src, int T, int J, const double* extrinsics,
+                            int C, const int* members, const int* offsets, int G, const void* sources, int H, int W, double fx, double fy,
+                            double ux, double uy, int flip_y, double max_dev, int flags, float* com, float* fused_pose, float* fused_com,
+                            float* spread, int* n_out, float* peer_com, int* fstat, const float* weight, float* fused_weight,
+                            dpp_stream_t stream) {
     if (!pose3d || !com3d || !status || !src || !extrinsics || !members || !offsets || !com || !fused_pose || !fused_com || !spread || !n_out ||
         !peer_com || !fstat)
         return DPP_E_BADARG;
@@ -175,6 +189,25 @@ extern "C" int dpp_pose_fuse(const float* pose3d, const float* com3d, const int*
     cam.fx = fx; cam.fy = fy; cam.ux = ux; cam.uy = uy; cam.flip_y = flip_y;
     DPP_LAUNCH(pose_fuse_kernel, dim3(G), dim3(DPP_WAVE), 0, static_cast<hipStream_t>(stream), pose3d, com3d, status, src, J, extrinsics, members,
                offsets, static_cast<const SourceRec*>(sources), H, W, cam, max_dev, flags, com, fused_pose, fused_com, spread, n_out, peer_com,
-               fstat);
+               fstat, weight, fused_weight);
     return dpp_launch_status();
+}
+
+extern "C" int dpp_pose_fuse(const float* pose3d, const float* com3d, const int* status, const int* src, int T, int J, const double* extrinsics,
+                             int C, const int* members, const int* offsets, int G, const void* sources, int H, int W, double fx, double fy,
+                             double ux, double uy, int flip_y, double max_dev, int flags, float* com, float* fused_pose, float* fused_com,
+                             float* spread, int* n_out, float* peer_com, int* fstat, dpp_stream_t stream) {
+    return launch_pose_fuse(pose3d, com3d, status, src, T, J, extrinsics, C, members, offsets, G, sources, H, W, fx, fy, ux, uy, flip_y, max_dev,
+                            flags, com, fused_pose, fused_com, spread, n_out, peer_com, fstat, nullptr, nullptr, stream);
+}
+
+// ABI v23: the same with a weight per track and joint (dpp_joint_visibility's), and the largest weight that went into each fused joint
+extern "C" int dpp_pose_fuse_w(const float* pose3d, const float* com3d, const int* status, const int* src, int T, int J, const double* extrinsics,
+                               int C, const int* members, const int* offsets, int G, const void* sources, int H, int W, double fx, double fy,
+                               double ux, double uy, int flip_y, double max_dev, int flags, float* com, float* fused_pose, float* fused_com,
+                               float* spread, int* n_out, float* peer_com, int* fstat, const float* weight, float* fused_weight,
+                               dpp_stream_t stream) {
+    if (!weight || !fused_weight) return DPP_E_BADARG;
+    return launch_pose_fuse(pose3d, com3d, status, src, T, J, extrinsics, C, members, offsets, G, sources, H, W, fx, fy, ux, uy, flip_y, max_dev,
+                            flags, com, fused_pose, fused_com, spread, n_out, peer_com, fstat, weight, fused_weight, stream);
 }

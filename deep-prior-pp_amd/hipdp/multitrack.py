@@ -13,11 +13,12 @@ again.  Here every launch of that plan runs once per tick for all tracks:
     crop_warp_ex_ix                 at B = T       the final crop, mirrored where tflags[t] has POSE_HAND_RIGHT
     the pose net's forward plan, built for a batch of T
     pose_finish_ix                  at B = T       the sign rules per track from tflags[t]
+    joint_visibility                at T x J       only with `visibility`: every joint classified by the frame's depths around its pixel (below)
     pose_fuse                       at G groups    only with `groups`: the tracks of one hand fused, lost tracks handed over (below)
     extrinsics_accumulate           per source     in pose_fuse's place while a source's extrinsics are being calibrated (below)
     pose_smooth                     at T + G rows  only with `smooth`: the One-Euro filter over the tracked and the fused poses (below)
 
-so the launch count is HandTracker's whatever T and C are (plus one with `groups`, plus one with `smooth`).  A track names its source (`src`), its hand side and invX / invY
+so the launch count is HandTracker's whatever T and C are (plus one with `groups`, plus one with `smooth`, plus one with `visibility`).  A track names its source (`src`), its hand side and invX / invY
 (`tflags`) and whether it takes part in this tick (`gate`) in three small int32 device arrays; the hand side is data, not a launch
 argument, so there is one plan, not one per flag combination.  C cameras with one hand each is tracks = [(c, False) for c in
 range(C)]; both hands of one camera is tracks = [(0, False), (0, True)]; mixtures are allowed.
@@ -49,8 +50,8 @@ the plan, one workgroup per group, then
     not marked lost: it runs ungated in the next tick from its peers' centre -- one tick of outage, no detector plan, no upload.
 A track that is gated because it is lost (it lost the hand while no peer had it) is restarted by process() through reset(t, peer_com)
 in the first tick in which its peers have the hand: one small upload, as acquire makes.  Tracks in no group are left entirely alone, and
-without `groups` the tracker allocates, uploads, launches and returns exactly what it did before.  Confidence weighting,
-triangulation from 2-D alone, fusing the depth frames themselves, hand size for several hands and per-source sensor options
+without `groups` the tracker allocates, uploads, launches and returns exactly what it did before.  (Confidence weighting stood in
+this list when fusion was written: see VISIBILITY below.)  Triangulation from 2-D alone, fusing the depth frames themselves, hand size for several hands and per-source sensor options
 are out of scope.
 
 CALIBRATION (ABI v21; csrc/calib.hip, hipdp/calib.py; this project's own as well, restated by tests/calib_ref.py).  The (R, t) that fusion
@@ -85,6 +86,23 @@ nothing is fused: the group rows are left out of the launch (their outputs read 
 back into the crop, per-source rates or timestamps, filtering com / com3D, and choosing mincutoff / beta for a dataset.  smooth=None:
 allocation, uploads, plan, result block and keys are those of before.
 
+VISIBILITY (ABI v23; csrc/visibility.hip, dpp_pose_fuse_w in csrc/fuse.hip; this project's own as well, restated by
+tests/visibility_ref.py).  A second camera is pointed at a hand because the first does not see all of it, and a camera whose view of a
+finger is blocked still regresses a joint there.  With visibility=dict(radius=, margin=, min_support=, hidden_weight=0.0) ONE launch behind
+pose_finish looks, for every joint (u, v, z) of every OK track, at the frame's pixels within `radius` of the joint's pixel: a pixel within
+`margin` mm of z is ON the joint, one more than `margin` nearer is in FRONT of it, a 0 is empty.  `vis` [J] is the share of ON pixels;
+`vis_class` [J] is ops.VIS_VISIBLE with at least min_support ON pixels, else VIS_OCCLUDED with at least min_support in FRONT, else
+VIS_UNSUPPORTED (guessed onto background or into a hole), or VIS_OFFFRAME for a joint outside its frame or without a depth.  A track that
+is not OK on the device has zeros.  With `groups` the fusion launch becomes dpp_pose_fuse_w: a VISIBLE joint weighs 1, any other
+hidden_weight, the fused joint is the weighted mean of the inliers' joints (the plain mean where nobody sees it), `spread` is taken over
+those with a weight > 0, and fused[g] gains `weight` [J], the largest weight that went in (0: nobody saw the joint).  Membership, the
+median test, fused `com`, peer_com and the hand-over do not read the weights; pose_smooth is untouched and filters the weighted fused
+pose.  While a source is being calibrated the launch still runs and nothing is fused.  The new fields stand behind every other field of
+the block, smooth's included.  radius, margin and min_support have no default: none has been chosen for a dataset.  Out of scope: a
+per-joint hold in the smoother, weighting the calibration pairs by visibility, weighting fused `com`, gating the hand-over by visibility,
+continuous weights from `vis`, and choosing `margin` for a dataset.  visibility=None: allocation, uploads, plan, result block and keys
+are those of before.
+
 acquire_source(c, frame) finds ALL hands of a source in one detector plan and starts the source's tracks from them; the detectors
 are built per source, at that source's size and focal lengths, on views of its frame slice.
 
@@ -99,12 +117,12 @@ import numpy as np
 
 from . import ops
 from .augmenter import camera_tuple
-from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, refine_stage, smooth_fields, track_fields, valid_centre
+from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, refine_stage, smooth_fields, track_fields, valid_centre, visibility_fields
 
 
 class MultiTracker(object):
     def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, tracks, sources=None, invX=False, invY=False, fx=None, fy=None,
-                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None):
+                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None, visibility=None):
         """
         :param importer:   the dataset importer (the camera) of all sources, or a sequence of C importers, one per source
         :param poseNet, comrefNet: as for HandTracker, but built for a batch of T, the number of tracks: row t is track t
@@ -125,6 +143,9 @@ class MultiTracker(object):
                            None, and those sources are calibrated against the source `anchor` from the tracked hand (CALIBRATION above)
         :param smooth:     None, or dict(rate=, mincutoff=, beta=, dcutoff=1.0, max_hold=0): the One-Euro filter over the poses
                            (SMOOTHING above); rate (ticks / s), mincutoff (Hz) and beta (Hz per mm / s) have no default
+        :param visibility: None, or dict(radius=, margin=, min_support=, hidden_weight=0.0): every joint classified by the frame's depths
+                           around its pixel, and with `groups` the fusion weighted by it (VISIBILITY above); radius (pixels), margin (mm)
+                           and min_support (pixels) have no default
         """
         self.rt = rt
         tracks = [(int(s), bool(r)) for s, r in tracks]
@@ -154,6 +175,7 @@ class MultiTracker(object):
                 raise ValueError("min_cond is a ratio >= 0: %r" % (cal['min_cond'],))
         self.max_dev, self.handover = None if max_dev is None else float(max_dev), bool(handover)
         self.smooth = None if smooth is None else ops.smooth_spec(smooth)
+        self.visibility = None if visibility is None else ops.visibility_spec(visibility)
         importers = self._per_source(importer, C, 'importer')
         Hs, Ws = self._per_source(H, C, 'H'), self._per_source(W, C, 'W')
         if any(int(h) != h or int(w) != w or h < 1 or w < 1 for h, w in zip(Hs, Ws)):
@@ -212,6 +234,8 @@ class MultiTracker(object):
             G = 0 if self.rig is None else self.rig.G
             fields += smooth_fields(T, self.J, G)
             self.sstate = ops.SmoothState(rt, T + G, self.J)
+        if self.visibility is not None:                                            # behind smooth's as well
+            fields += visibility_fields(T, self.J, 0 if self.rig is None else self.rig.G)
         self.block = blk = ResultBlock(rt, fields)
         self.res, self._off = blk.buf, blk.offsets
         self.fused = []
@@ -486,13 +510,20 @@ class MultiTracker(object):
                 p.add(op, side)
             p.add(ops.pose_finish(rt, self.peng.out.buf, T, self.J, self.cube, self.com3d, self.cam, None, self.pose3d, self.pose_img,
                                   tracks=tracks))
+            weighted = {}
+            if self.visibility is not None:             # reads the slot's float32 frames, which nothing in the plan writes behind the first launch
+                blk = self.block
+                p.add(ops.joint_visibility(rt, self.pose_img, self.status, self.src, T, self.J, fr, C, self.visibility, blk.view('vis'),
+                                           blk.view('vis_weight'), blk.view('vis_class'), table=self.table, H=H, W=W))
+                if self.rig is not None:
+                    weighted = dict(weight=blk.view('vis_weight'), fused_weight=blk.view('fused_weight'), name='pose_fuse_w')
             if self.calibrating:                        # in the fusion launch's place: nothing can be fused or handed over yet
                 p.add(ops.extrinsics_accumulate(rt, self.pose3d, self.status, self.src, T, self.J, self.rig, self.anchor, self.cal_src,
                                                 self.max_shape_dev, self.acc))
             elif self.rig is not None:                  # the last launch of the main lane: the next tick's prepare is ordered behind it
                 p.add(ops.pose_fuse(rt, self.pose3d, self.com3d, self.status, self.src, T, self.J, self.rig, self.table, H, W, self.cam,
                                     self.max_dev, self.handover, self.com, self.fused_pose, self.fused_com, self.spread, self.fused_n,
-                                    self.peer_com, self.fstat))
+                                    self.peer_com, self.fstat, **weighted))
             if self.smooth is not None:                 # the last launch of the main lane; both slots filter into the ONE state
                 blk, fusing = self.block, self.rig is not None and not self.calibrating
                 grp = {}
@@ -525,6 +556,9 @@ class MultiTracker(object):
             if self.smooth is not None:
                 for g, d in enumerate(self.fused):
                     d.update(pose_f=f['fused_pose_f'][g], smooth=int(f['gstat'][g]))
+            if self.visibility is not None:
+                for g, d in enumerate(self.fused):
+                    d.update(weight=f['fused_weight'][g])
             self._peer_ok = (fstat & ops.FUSE_PEER_OK) != 0
         out = []
         for t in range(self.T):
@@ -545,6 +579,8 @@ class MultiTracker(object):
                          handed=handed, peer_com=peer[t])
             if self.smooth is not None:
                 d.update(pose_f=f['pose_f'][t], pose_img_f=f['pose_img_f'][t], smooth=int(f['sstat'][t]))
+            if self.visibility is not None:
+                d.update(vis=f['vis'][t], vis_class=f['vis_class'][t])
             if crops is not None:
                 d['crop'] = crops[t]
             out.append(d)

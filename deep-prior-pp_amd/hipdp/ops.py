@@ -1043,19 +1043,68 @@ def extrinsics_accumulate(rt, pose3d, status, src, T, J, rig, anchor, cal_src, m
 
 
 def pose_fuse(rt, pose3d, com3d, status, src, T, J, rig, table, H, W, cam, max_dev, handover, com, fused_pose, fused_com, spread, n_out,
-              peer_com, fstat, name='pose_fuse'):
+              peer_com, fstat, name='pose_fuse', weight=None, fused_weight=None):
     """dpp_pose_fuse: one workgroup per group of `rig`.  table: an ops.SourceTable, or None with (H, W, cam) for every source; max_dev:
-    None (no consistency test) or > 0 (mm)."""
+    None (no consistency test) or > 0 (mm).  weight [T][J] with fused_weight [G][J] (both or neither): dpp_pose_fuse_w, the joints
+    averaged with joint_visibility's weights."""
     if max_dev is not None and not (np.isfinite(max_dev) and max_dev > 0.):
         raise ValueError("max_dev is None or a distance > 0 (mm): %r" % (max_dev,))
+    if (weight is None) != (fused_weight is None):
+        raise ValueError("weight [T][J] and fused_weight [G][J] go together")
     fx, fy, ux, uy, flip = (0., 0., 0., 0., 0) if table is not None else cam
-    return Launch(rt.lib.dpp_pose_fuse,
+    weighted = () if weight is None else (weight, fused_weight)
+    return Launch(rt.lib.dpp_pose_fuse if weight is None else rt.lib.dpp_pose_fuse_w,
                   (pose3d.ptr, com3d.ptr, status.ptr, src.ptr, T, J, rig.extr.ptr, rig.C, rig.members.ptr, rig.offsets.ptr, rig.G,
                    None if table is None else table.dev.ptr, 0 if table is not None else int(H), 0 if table is not None else int(W), float(fx),
                    float(fy), float(ux), float(uy), int(flip), 0.0 if max_dev is None else float(max_dev), FUSE_HANDOVER if handover else 0,
-                   com.ptr, fused_pose.ptr, fused_com.ptr, spread.ptr, n_out.ptr, peer_com.ptr, fstat.ptr),
+                   com.ptr, fused_pose.ptr, fused_com.ptr, spread.ptr, n_out.ptr, peer_com.ptr, fstat.ptr) + tuple(b.ptr for b in weighted),
                   (pose3d, com3d, status, src, rig.extr, rig.members, rig.offsets, None if table is None else table.dev, com, fused_pose,
-                   fused_com, spread, n_out, peer_com, fstat), name)
+                   fused_com, spread, n_out, peer_com, fstat) + weighted, name)
+
+
+# ---- which joints of a tracked pose the frame shows (include/dpp_hip.h, ABI v23; csrc/visibility.hip) ------------------------------------
+VIS_VISIBLE, VIS_OCCLUDED, VIS_UNSUPPORTED, VIS_OFFFRAME = 1, 2, 4, 8                   # DPP_VIS_*: dpp_joint_visibility's class per joint
+VIS_MAX_RADIUS = 8
+
+
+def visibility_spec(visibility):
+    """dict(radius=, margin=, min_support=, hidden_weight=0.0) checked on the host -> (radius, margin, min_support, hidden_weight).
+    radius (pixels, 0 .. 8), margin (mm) and min_support (pixels of the window, 1 .. (2 radius + 1)^2) are required: none has been
+    chosen for a dataset.  hidden_weight: what a joint that is not VISIBLE weighs in the fusion, in [0, 1]."""
+    s = dict(hidden_weight=0.0)
+    known = ('radius', 'margin', 'min_support', 'hidden_weight')
+    if not isinstance(visibility, dict) or set(visibility) - set(known):
+        raise ValueError("visibility takes radius, margin, min_support and hidden_weight, not %r" %
+                         (sorted(set(visibility) - set(known)) if isinstance(visibility, dict) else visibility,))
+    s.update(visibility)
+    missing = [k for k in known if k not in s]
+    if missing:
+        raise ValueError("visibility needs %s: no tuned default exists" % ', '.join(missing))
+    try:
+        radius, support = int(s['radius']), int(s['min_support'])
+        margin, hidden = float(s['margin']), float(s['hidden_weight'])
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("visibility takes numbers: %r" % (visibility,))
+    if radius != s['radius'] or not 0 <= radius <= VIS_MAX_RADIUS:
+        raise ValueError("radius is a number of pixels, 0 .. %d: %r" % (VIS_MAX_RADIUS, s['radius']))
+    if support != s['min_support'] or not 1 <= support <= (2 * radius + 1) ** 2:
+        raise ValueError("min_support is a number of the window's %d pixels, 1 or more: %r" % ((2 * radius + 1) ** 2, s['min_support']))
+    if not (np.isfinite(margin) and margin > 0.):
+        raise ValueError("margin (mm) is finite and > 0: %r" % (s['margin'],))
+    if not 0. <= hidden <= 1.:
+        raise ValueError("hidden_weight is a weight in [0, 1]: %r" % (s['hidden_weight'],))
+    return radius, margin, support, hidden
+
+
+def joint_visibility(rt, pose_img, status, src, T, J, frames, C, spec, vis, weight, vword, table=None, H=0, W=0, name='joint_visibility'):
+    """dpp_joint_visibility: one workgroup per (track, joint).  spec: visibility_spec's tuple.  frames: the float32 frame buffer --
+    [C][H][W] with H, W, or the ragged one of `table` (an ops.SourceTable); src: int32 [T], every track's source."""
+    radius, margin, support, hidden = spec
+    return Launch(rt.lib.dpp_joint_visibility,
+                  (pose_img.ptr, status.ptr, src.ptr, T, J, frames.ptr, int(C), None if table is None else table.dev.ptr,
+                   0 if table is not None else int(H), 0 if table is not None else int(W), radius, margin, support, hidden, vis.ptr, weight.ptr,
+                   vword.ptr),
+                  (pose_img, status, src, frames, None if table is None else table.dev, vis, weight, vword), name)
 
 
 # ---- tracked and fused poses smoothed over the ticks (include/dpp_hip.h, ABI v22; csrc/smooth.hip) --------------------------------------

@@ -148,9 +148,19 @@ def smooth_fields(T, J, G=0):
     return f
 
 
+def visibility_fields(T, J, G=0):
+    """What a tracker with `visibility` appends to its block, behind every other field (smooth's included): dpp_joint_visibility's
+    share of supporting pixels, weight and class per track and joint, and per group the largest weight that went into each fused joint."""
+    f32 = np.float32
+    f = [('vis', (T, J), f32), ('vis_weight', (T, J), f32), ('vis_class', (T, J), np.int32)]
+    if G:
+        f += [('fused_weight', (G, J), f32)]
+    return f
+
+
 class HandTracker(object):
     def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, hand_right=False, invX=False, invY=False, fx=None, fy=None, sensor=None,
-                 smooth=None):
+                 smooth=None, visibility=None):
         """
         :param importer:   the dataset importer (camera; NYU / MSRA flip the y axis)
         :param poseNet:    the pose regressor, built for a batch of one; its output is J x 3 normalised joints
@@ -163,6 +173,9 @@ class HandTracker(object):
                            mirror=bool): frames are RAW sensor frames of that dtype, converted (mirrored, median-filtered) on the device
         :param smooth:     None, or dict(rate=, mincutoff=, beta=, dcutoff=1.0, max_hold=0): the One-Euro filter over the pose as the last
                            launch of the plan (hipdp/multitrack.py, SMOOTHING): the result gains pose_f, pose_img_f and `smooth`
+        :param visibility: None, or dict(radius=, margin=, min_support=, hidden_weight=0.0): one launch behind pose_finish classifies every
+                           joint by the frame's depths around its pixel (hipdp/multitrack.py, VISIBILITY): the result gains `vis`
+                           and `vis_class`
         """
         self.rt, self.H, self.W = rt, int(H), int(W)
         self.importer = importer
@@ -187,7 +200,10 @@ class HandTracker(object):
         self.smooth = None if smooth is None else ops.smooth_spec(smooth)
         self.sstate = None if smooth is None else ops.SmoothState(rt, 1, self.J)   # the filter's state: never downloaded
         # (+ the detector's seed / cube / status words: acquire; with `smooth` the filtered pose, its projection and the filter's word follow)
-        self.block = blk = ResultBlock(rt, track_fields(1, self.J) + (smooth_fields(1, self.J) if smooth is not None else []))
+        self.visibility = None if visibility is None else ops.visibility_spec(visibility)
+        self.vsrc = None if visibility is None else rt.alloc((1,), np.int32)      # the one track's source: 0
+        self.block = blk = ResultBlock(rt, track_fields(1, self.J) + (smooth_fields(1, self.J) if smooth is not None else []) +
+                                       (visibility_fields(1, self.J) if visibility is not None else []))
         self.res = blk.buf
         self.pose3d, self.pose_img, self.com, self.com3d = blk.view('pose'), blk.view('pose_img'), blk.view('com'), blk.view('com3D')
         self.M, self.status = blk.view('M'), blk.view('status')
@@ -293,6 +309,10 @@ class HandTracker(object):
             for op, side in self.peng.fwd.ops:
                 p.add(op, side)
             p.add(ops.pose_finish(rt, self.peng.out.buf, 1, self.J, self.cube, self.com3d, self.cam, self.flags, self.pose3d, self.pose_img))
+            if self.visibility is not None:         # reads the float32 frame of this slot, which the whole plan leaves as it is
+                blk = self.block
+                p.add(ops.joint_visibility(rt, self.pose_img, self.status, self.vsrc, 1, self.J, fr, 1, self.visibility, blk.view('vis'),
+                                           blk.view('vis_weight'), blk.view('vis_class'), H=H, W=W))
             if self.smooth is not None:
                 blk = self.block
                 p.add(ops.pose_smooth(rt, self.pose3d, self.status, 1, self.J, self.smooth, self.sstate, blk.view('pose_f'),
@@ -305,6 +325,8 @@ class HandTracker(object):
         out['status'] = int(out['status'])
         if self.smooth is not None:
             out['smooth'] = int(out.pop('sstat'))
+        if self.visibility is not None:
+            del out['vis_weight']                                              # 1 where vis_class is VISIBLE, else hidden_weight
         if crop is not None:
             out['crop'] = crop
         return out

@@ -85,7 +85,7 @@ class RealtimeHandposePipeline(object):
     DETECTOR_COM = 0
 
     def __init__(self, poseNet, config, di, verbose=False, comrefNet=None, init_com=None, seed_com=False, seed_detect=False, sensor=None,
-                 smooth=None):
+                 smooth=None, visibility=None):
         """
         :param poseNet:   network for pose estimation (a built net, or PoseRegNetParams / ResNetParams, with loadFile or not)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=])
@@ -100,6 +100,9 @@ class RealtimeHandposePipeline(object):
         :param smooth:    None, or HandTracker's dict(rate=, mincutoff=, beta=[, dcutoff=, max_hold=]): processFrame's result gains the
                           One-Euro-filtered pose_f / pose_img_f and the filter's word `smooth` beside the raw keys, and processVideo
                           leaves the filtered poses of the frames it returns in `poses_f`
+        :param visibility: None, or HandTracker's dict(radius=, margin=, min_support=[, hidden_weight=]): processFrame's result gains
+                          `vis` (the share of the pixels around each joint that lie at its depth) and `vis_class` (ops.VIS_* per joint),
+                          and processVideo leaves the classes of the frames it returns in `vis_classes`
         """
         self.importer = di
         self.poseNet = poseNet
@@ -125,6 +128,8 @@ class RealtimeHandposePipeline(object):
         self.sensor = None if sensor is None else dict(sensor)
         self.smooth = None if smooth is None else dict(smooth)
         self.poses_f = None
+        self.visibility = None if visibility is None else dict(visibility)
+        self.vis_classes = None
 
     def initNets(self):
         """Build the nets from their parameters (loading loadFile where set) and compile their forward plans (:118-141)."""
@@ -265,7 +270,8 @@ class RealtimeHandposePipeline(object):
         t = self._tracker
         if t is None or (t.H, t.W) != (H, W) or (t.fx, t.fy) != (abs(float(cfg['fx'])), abs(float(cfg['fy']))):
             t = self._tracker = HandTracker(default_runtime(), self.importer, self.poseNet, self.comrefNet, H, W, cfg['cube'],
-                                            fx=cfg['fx'], fy=cfg['fy'], sensor=self.sensor, smooth=self.smooth)
+                                            fx=cfg['fx'], fy=cfg['fy'], sensor=self.sensor, smooth=self.smooth,
+                                            visibility=self.visibility)
         if tuple(numpy.float32(cfg['cube'])) != tuple(t.cube_host):
             t.set_cube(cfg['cube'])
         t.set_hand(self.hand.value == self.HAND_RIGHT)
@@ -285,6 +291,8 @@ class RealtimeHandposePipeline(object):
                    M=numpy.eye(3, dtype=numpy.float32), status=1)
         if self.smooth is not None:                    # nothing ran: nothing was filtered
             res.update(pose_f=numpy.zeros((J, 3), numpy.float32), pose_img_f=numpy.zeros((J, 3), numpy.float32), smooth=ops.SMOOTH_EMPTY)
+        if self.visibility is not None:                # nothing ran: the zeros of a row that is not OK
+            res.update(vis=numpy.zeros(J, numpy.float32), vis_class=numpy.zeros(J, numpy.int32))
         return res
 
     def processFrame(self, frame):
@@ -315,7 +323,7 @@ class RealtimeHandposePipeline(object):
         a lost frame, or one in which no hand is found, is skipped instead and the next frame is searched again."""
         self.initNets()
         device.start()
-        poses, poses_f = [], []
+        poses, poses_f, vis_classes = [], [], []
         times = []
         while not self.stop.value and (max_frames is None or len(poses) < max_frames):
             try:
@@ -336,12 +344,15 @@ class RealtimeHandposePipeline(object):
             poses.append(res['pose'].copy())
             if self.smooth is not None:
                 poses_f.append(res['pose_f'].copy())
+            if self.visibility is not None:
+                vis_classes.append(res['vis_class'].copy())
             if self.verbose is True:
                 print("{}ms frame".format(times[-1] * 1000.))
         device.stop()
         self.frame_times = times
         J = self.poseNet.cfgParams.outputDim[1] // 3
         self.poses_f = None if self.smooth is None else numpy.asarray(poses_f, numpy.float32).reshape(-1, J, 3)
+        self.vis_classes = None if self.visibility is None else numpy.asarray(vis_classes, numpy.int32).reshape(-1, J)
         return numpy.asarray(poses, numpy.float32).reshape(-1, J, 3)
 
     def calibrateHandsize(self, device, num_frames=None):
@@ -442,12 +453,16 @@ class MultiStreamPipeline(object):
 
     Smoothing (hipdp/multitrack.py, SMOOTHING): smooth=dict(rate=, mincutoff=, beta=[, dcutoff=, max_hold=]) goes to MultiTracker: the
     results carry pose_f / pose_img_f / smooth beside the raw keys, `fused` pose_f / smooth, and processVideos leaves in `poses_f` /
-    `fused_poses_f` the filtered poses of exactly the ticks that its return value / `fused_poses` hold."""
+    `fused_poses_f` the filtered poses of exactly the ticks that its return value / `fused_poses` hold.
+
+    Visibility (hipdp/multitrack.py, VISIBILITY): visibility=dict(radius=, margin=, min_support=[, hidden_weight=]) goes to MultiTracker:
+    the results carry vis / vis_class per joint, the fusion is weighted by them, `fused` carries `weight`, and processVideos leaves
+    in `vis_classes` the classes of exactly the ticks that its return value holds."""
 
     HAND_LEFT, HAND_RIGHT = RealtimeHandposePipeline.HAND_LEFT, RealtimeHandposePipeline.HAND_RIGHT
 
     def __init__(self, poseNet, config, di, devices, hands, comrefNet, init_com=None, seed_detect=False, sensor=None, verbose=False,
-                 max_extent=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None):
+                 max_extent=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None, visibility=None):
         """
         :param poseNet, comrefNet: built nets or their parameters (as for RealtimeHandposePipeline), with batchSize == len(hands)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=]); fx / fy: one value, or a list with one per device
@@ -461,7 +476,10 @@ class MultiStreamPipeline(object):
         :param groups, max_dev, handover: MultiTracker's, with config['extrinsics'] (one (R, t) per device)
         :param calibrate: MultiTracker's: entries of config['extrinsics'] may then be None, to be found by calibrateExtrinsics
         :param smooth:    MultiTracker's: the One-Euro filter over the tracked and the fused poses
+        :param visibility: MultiTracker's: every joint classified by the frame around it, the fusion weighted by that
         """
+        self.visibility = None if visibility is None else dict(visibility)
+        self.vis_classes = None
         self.smooth = None if smooth is None else dict(smooth)
         self.poses_f, self.fused_poses_f = None, None
         self.max_extent = max_extent
@@ -512,7 +530,8 @@ class MultiStreamPipeline(object):
                                          cfg['cube'], [(d, h == self.HAND_RIGHT) for d, h in self.hands], sources=len(self.devices),
                                          invX=cfg.get('invX') is True, invY=cfg.get('invY') is True, fx=cfg['fx'], fy=cfg['fy'],
                                          sensor=self.sensor, extrinsics=cfg.get('extrinsics'), groups=self.groups, max_dev=self.max_dev,
-                                         handover=self.handover, calibrate=self.calibrate, smooth=self.smooth)
+                                         handover=self.handover, calibrate=self.calibrate, smooth=self.smooth,
+                                         visibility=self.visibility)
             self._tracker_key = shapes
             self._seeded = [False] * len(self.hands)
         return self._tracker
@@ -610,6 +629,7 @@ class MultiStreamPipeline(object):
 
         fused_poses = [[] for _ in (self.groups or [])]
         poses_f, fused_poses_f = [[] for _ in self.hands], [[] for _ in (self.groups or [])]
+        vis_classes = [[] for _ in self.hands]
 
         def collect(res, tick, fused):
             for g, f in enumerate(fused):
@@ -622,6 +642,8 @@ class MultiStreamPipeline(object):
                     poses[t].append(r['pose'].copy())
                     if self.smooth is not None:
                         poses_f[t].append(r['pose_f'].copy())
+                    if self.visibility is not None:
+                        vis_classes[t].append(r['vis_class'].copy())
                 elif r['status'] == 1:
                     print("Track {} lost (or no hand) in tick {}.".format(t, tick))
 
@@ -670,4 +692,6 @@ class MultiStreamPipeline(object):
         if self.smooth is not None:
             self.poses_f = [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in poses_f]
             self.fused_poses_f = [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in fused_poses_f]
+        if self.visibility is not None:
+            self.vis_classes = [numpy.asarray(c, numpy.int32).reshape(-1, J) for c in vis_classes]
         return [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in poses]

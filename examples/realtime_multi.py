@@ -35,6 +35,14 @@ the plan's last launch (MultiTracker smooth=, this project's own) and prints two
 displacement of the raw and of the filtered joints, and the mean raw-to-filtered distance -- of the fused pose with --fuse, else of
 every track.
 
+--visibility RADIUS MARGIN MIN_SUPPORT [--hidden-weight W] classifies every joint of every track by the frame's depths within RADIUS
+pixels of it (MultiTracker visibility=, this project's own: at least MIN_SUPPORT pixels within MARGIN mm of the joint's depth: visible;
+else that many nearer ones: occluded; else unsupported; outside the frame: off-frame) and prints the share of joints per class per
+track; with --fuse the fusion is weighted by it (a joint that is not visible weighs W, default 0).  With --fuse and --visibility,
+--occlude-second X0:Y0:X1:Y1:DEPTH writes a rectangle of DEPTH mm -- something nearer than the hand -- into camera 1's frames (its own
+pixel coordinates) and makes two more runs without output, the unoccluded one and the occluded one without --visibility, to print the
+mean distance of the fused joints from the unoccluded run's, weighted and unweighted: sanity figures, not bars.
+
     python examples/realtime_multi.py --dataset icvl --data ../data/ICVL/ --seqs test_seq_1 test_seq_2
 """
 import argparse
@@ -102,8 +110,30 @@ def print_smoothing(what, fig):
           "mean raw-to-filtered distance {distance:.3f} mm".format(what, **fig))
 
 
-def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
-    """--fuse: one sequence through two cameras, the two tracks of its hand fused; returns a dict of what is printed."""
+CLASSES = (('visible', 1), ('occluded', 2), ('unsupported', 4), ('off-frame', 8))          # ops.VIS_*
+
+
+def visibility_arg(args):
+    """{} without --visibility, else the visibility= keyword of the pipeline."""
+    if args.visibility is None:
+        return {}
+    r, margin, support = args.visibility
+    return dict(visibility=dict(radius=int(r), margin=margin, min_support=int(support), hidden_weight=args.hidden_weight))
+
+
+def class_shares(classes):
+    """{class name: share} of the joints of one track over its followed ticks: classes is (ticks, J) of ops.VIS_* words."""
+    c = numpy.asarray(classes, numpy.int32).reshape(-1)
+    return dict((name, float((c == v).mean()) if c.size else float('nan')) for name, v in CLASSES)
+
+
+def print_visibility(t, shares):
+    print("track {}, visibility: ".format(t) + ', '.join("{} {:.3f}".format(name, shares[name]) for name, _ in CLASSES))
+
+
+def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands, occlude=None, visibility=True):
+    """--fuse: one sequence through two cameras, the two tracks of its hand fused; returns a dict of what is printed.  occlude: None or
+    (x0, y0, x1, y1, depth), the rectangle written into camera 1's frames; visibility False: without --visibility whatever args say."""
     files = [f.fileName for f in seqs[0].data]
     H, W = numpy.asarray(di.loadDepthMap(files[0])).shape
     H2, W2 = (H + 1) // 2, (W + 1) // 2
@@ -111,13 +141,14 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
     Rz = numpy.diag([-1., -1., 1.])                                    # camera 1's frame -> world (= camera 0's frame): its own inverse
     true_ext = [(numpy.eye(3), numpy.zeros(3)), (Rz, numpy.zeros(3))]
     n_cal = args.calibrate_extrinsics or 0
+    vis_kw = visibility_arg(args) if visibility else {}
     cfg = dict(config, fx=[config['fx'], config['fx'] / 2.], fy=[config['fy'], config['fy'] / 2.],
                extrinsics=[true_ext[0], None] if n_cal else true_ext)        # calibrating: camera 1's pose is withheld from the tracker
     c0 = numpy.asarray(seqs[0].data[0].gtorig[di.crop_joint_idx], numpy.float32)
     seeds = [c0, numpy.float32([(W2 - 1) - c0[0] / 2., (H2 - 1) - c0[1] / 2., c0[2]])]
     devices = [FileDevice(files, di), UpsideDownHalfResFileDevice(files, di)]
     msp = MultiStreamPipeline(poseNetParams, cfg, [di, di2], devices, hands, comrefNetParams, init_com=seeds, groups=[[0, 1]],
-                              max_dev=args.max_dev, calibrate=dict(anchor=0) if n_cal else None, **smooth_arg(args))
+                              max_dev=args.max_dev, calibrate=dict(anchor=0) if n_cal else None, **dict(smooth_arg(args), **vis_kw))
     drop = range(0)
     if args.drop_second:
         a, b = (int(v) for v in args.drop_second.split(':'))
@@ -126,6 +157,7 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
     for dev in devices:
         dev.start()
     status, spread, dist, fused, calibration, fused_f = [], [], [[], []], [], [], []
+    classes, fused_at = [[], []], []
     tick = 0
     while args.max_frames is None or tick < args.max_frames:
         frames = msp._read()
@@ -135,8 +167,16 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
             frames[1] = numpy.zeros_like(frames[1])
             if msp._tracker is not None:
                 msp._tracker.drop(1)
+        if occlude is not None:                                        # something nearer than the hand in front of camera 1
+            x0, y0, x1, y1, depth = occlude
+            frames[1] = numpy.array(frames[1])
+            frames[1][int(y0):int(y1), int(x0):int(x1)] = depth
         res = msp.processFrames(frames)
         status.append([r['status'] for r in res])
+        if vis_kw:
+            for t, r in enumerate(res):
+                if r['status'] == 0:
+                    classes[t].append(r['vis_class'].copy())
         tick += 1
         mt = msp._tracker
         if mt.calibrating:                                             # the tick added its joint pairs to the sums; nothing is fused yet
@@ -160,13 +200,14 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
                 dist[t].append(float(numpy.sqrt(((world - f['pose']) ** 2).sum(1)).mean()))
         if f['n'] > 0:
             fused.append(f['pose'].copy())
+            fused_at.append(tick - 1)
             if args.smooth is not None:
                 fused_f.append(f['pose_f'].copy())
     for dev in devices:
         dev.stop()
     out = dict(status=status, spread=float(numpy.mean(spread)) if spread else float('nan'),
                dist=[float(numpy.mean(d)) if d else float('nan') for d in dist], fused=numpy.asarray(fused, numpy.float32), dropped=list(drop),
-               back=None, calibration=calibration)
+               back=None, calibration=calibration, fused_at=fused_at)
     print("{} ticks, both cameras followed in {}: mean spread {:.3f} mm, fused pose {:.3f} mm from camera 0's, {:.3f} mm from camera 1's"
           .format(tick, len(spread), out['spread'], out['dist'][0], out['dist'][1]))
     if len(drop):
@@ -177,7 +218,20 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands):
     if args.smooth is not None:
         out['smooth'] = smoothing_figures(fused, fused_f)
         print_smoothing("fused pose", out['smooth'])
+    if vis_kw:
+        out['visibility'] = [class_shares(c) for c in classes]
+        for t, shares in enumerate(out['visibility']):
+            print_visibility(t, shares)
     return out
+
+
+def fused_distance(a, b):
+    """Mean distance (mm) of the fused joints of run a from those of run b over the ticks in which both have a fused pose."""
+    ia, ib = dict(zip(a['fused_at'], a['fused'])), dict(zip(b['fused_at'], b['fused']))
+    both = sorted(set(ia) & set(ib))
+    if not both:
+        return float('nan')
+    return float(numpy.mean([numpy.sqrt(((ia[i].astype(numpy.float64) - ib[i]) ** 2).sum(1)).mean() for i in both]))
 
 
 def main(argv=None):
@@ -203,6 +257,11 @@ def main(argv=None):
     ap.add_argument('--smooth', nargs=3, type=float, default=None, metavar=('RATE', 'MINCUTOFF', 'BETA'),
                     help='One-Euro filter over the joints: ticks per second, Hz, Hz per mm/s')
     ap.add_argument('--hold', type=int, default=0, metavar='N', help='with --smooth: ticks a lost track keeps its last filtered pose (max_hold)')
+    ap.add_argument('--visibility', nargs=3, type=float, default=None, metavar=('RADIUS', 'MARGIN', 'MIN_SUPPORT'),
+                    help="classify every joint by the frame's depths around it: pixels, mm, pixels; with --fuse the fusion is weighted by it")
+    ap.add_argument('--hidden-weight', type=float, default=0., metavar='W', help='with --visibility: what a joint that is not visible weighs in the fusion')
+    ap.add_argument('--occlude-second', default=None, metavar='X0:Y0:X1:Y1:DEPTH',
+                    help="with --fuse --visibility: a rectangle of DEPTH mm written into camera 1's frames")
     ap.add_argument('--cache', default='./cache/')
     args = ap.parse_args(argv)
     Importer, seq_names, config = DATASETS[args.dataset]
@@ -225,8 +284,24 @@ def main(argv=None):
     comrefNetParams = ScaleNetParams(type=1, nChan=1, wIn=128, hIn=128, batchSize=T, resizeFactor=2, numJoints=1, nDims=3)
     comrefNetParams.loadFile = args.comref_net
     config = dict(config, cube=tuple(seqs[0].config['cube']))
+    if args.occlude_second and not (args.fuse and args.visibility is not None):
+        raise SystemExit("--occlude-second compares the weighted with the unweighted fusion: it needs --fuse and --visibility")
     if args.fuse:
-        return fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands)
+        demo = (args, di, seqs, config, poseNetParams, comrefNetParams, hands)
+        if not args.occlude_second:
+            return fuse_demo(*demo)
+        import contextlib
+        import io
+        occlude = tuple(float(v) for v in args.occlude_second.split(':'))
+        if len(occlude) != 5:
+            raise SystemExit("--occlude-second takes X0:Y0:X1:Y1:DEPTH")
+        out = fuse_demo(*demo, occlude=occlude)
+        with contextlib.redirect_stdout(io.StringIO()):                # the two runs to compare with: their own output is not repeated
+            clear, plain = fuse_demo(*demo, visibility=False), fuse_demo(*demo, occlude=occlude, visibility=False)
+        out['occluded'] = dict(weighted=fused_distance(out, clear), unweighted=fused_distance(plain, clear))
+        print("camera 1 occluded (sanity figures): fused joints {weighted:.3f} mm from the unoccluded run's with the weights, "
+              "{unweighted:.3f} mm without".format(**out['occluded']))
+        return out
     init = [seqs[d].data[0].gtorig[di.crop_joint_idx] for d, _ in hands]
     if args.seed == 'detect':
         init[2] = None                                                 # alone on its camera: found by the detector
@@ -242,7 +317,7 @@ def main(argv=None):
         else:
             dis, cfg, devices, seeds = di, config, [FileDevice(f, di) for f in files], init
         msp = MultiStreamPipeline(poseNetParams, cfg, dis, devices, hands, comrefNetParams, init_com=seeds, seed_detect=args.seed != 'gt',
-                                  max_extent=args.max_extent, **smooth_arg(args))
+                                  max_extent=args.max_extent, **dict(smooth_arg(args), **visibility_arg(args)))
         return msp, msp.processVideos(max_frames=args.max_frames, overlapped=args.overlapped)
     msp, poses = run(args.half_res_second)
     t = numpy.asarray(msp.frame_times[1:] or msp.frame_times)         # the first tick records the plan
@@ -265,6 +340,11 @@ def main(argv=None):
         for t, fig in enumerate(figs):
             print_smoothing("track {}".format(t), fig)
         return poses, errs, figs
+    if args.visibility is not None:
+        shares = [class_shares(c) for c in msp.vis_classes]
+        for t, sh in enumerate(shares):
+            print_visibility(t, sh)
+        return poses, errs, shares
     return poses, errs
 
 

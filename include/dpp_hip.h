@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 22
+#define DPP_ABI_VERSION 23
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -639,6 +639,22 @@ int dpp_pose_fuse(const float* pose3d, const float* com3d, const int* status, co
                   const int* members, const int* offsets, int G, const void* sources, int H, int W, double fx, double fy, double ux, double uy,
                   int flip_y, double max_dev, int flags, float* com, float* fused_pose, float* fused_com, float* spread, int* n_out,
                   float* peer_com, int* fstat, dpp_stream_t stream);
+/* The same launch with a weight per track and joint (ABI v23; the weights that dpp_joint_visibility writes, or any finite weights >= 0):
+ * weight [T][J] float32 (read only), fused_weight [G][J] float32.  Contributors, the median test, outliers, n, fused_com, peer_com,
+ * the hand-over and fstat are those of dpp_pose_fuse and do not read the weights.  Per joint j, over the inliers m in list order, sums
+ * starting from 0.0, W_mj = R pose3d[m][j] + t and w_m = weight[m][j]: sw = sw + (double) w_m; per coordinate
+ * sum = sum + (double) w_m * W_mj (a product, then an add: no contraction).
+ *   sw > 0:  fused_pose[g][j] = sum / sw; spread[g][j] = the largest distance from that (unrounded) joint of the W_mj of an inlier with
+ *            w_m > 0; fused_weight[g][j] = the largest w_m.
+ *   sw == 0 (nobody sees the joint): fused_pose and spread are dpp_pose_fuse's -- the unweighted mean, the spread over all inliers --
+ *            and fused_weight[g][j] = 0.
+ *   n == 0:  all zeros, fused_weight included.
+ * So weights that are all 1.0f (1.0 * x is exact, sw == n) and weights that are all 0 both give dpp_pose_fuse's bytes in every output.
+ * DPP_E_BADARG: dpp_pose_fuse's cases, and a NULL weight or fused_weight.  The weights themselves are not checked. */
+int dpp_pose_fuse_w(const float* pose3d, const float* com3d, const int* status, const int* src, int T, int J, const double* extrinsics, int C,
+                    const int* members, const int* offsets, int G, const void* sources, int H, int W, double fx, double fy, double ux,
+                    double uy, int flip_y, double max_dev, int flags, float* com, float* fused_pose, float* fused_com, float* spread,
+                    int* n_out, float* peer_com, int* fstat, const float* weight, float* fused_weight, dpp_stream_t stream);
 
 /* ---- extrinsics of a camera from the tracked hand (ABI v21; csrc/calib.hip) ---------------------------------------------------------------
  * dpp_pose_fuse needs an (R, t) per source.  The tracker already has the correspondences for a rigid fit: every tick the same J joints
@@ -714,6 +730,43 @@ int dpp_pose_smooth(const float* pose3d, const int* status, const int* src, int 
                     const void* sources, double fx, double fy, double ux, double uy, int flip_y, double rate, double mincutoff, double beta,
                     double dcutoff, int max_hold, int* since, double* xh, double* dxh, float* pose_f, float* pose_img_f, int* sstat,
                     float* fused_pose_f, int* gstat, dpp_stream_t stream);
+
+/* ---- which joints of a tracked pose the frame shows (ABI v23; csrc/visibility.hip) --------------------------------------------------------
+ * The reason to point a second camera at a hand is that the first does not see all of it; the evidence is on the device at the end of
+ * every tick: dpp_pose_finish writes each joint as (u, v, z) in its source's frame, and the float32 frame is still in the frame buffer.
+ * ONE launch behind dpp_pose_finish (before dpp_pose_fuse_w / dpp_extrinsics_accumulate / dpp_pose_smooth where the plan has them)
+ * classifies every joint of all T tracks by the depths around its pixel.  The reference has no counterpart: these semantics are THIS
+ * PROJECT'S OWN, restated in NumPy float64 by tests/visibility_ref.py and pinned to it bit for bit.  Comparisons are float64 in the
+ * order given (no FMA contraction); every float output is rounded to float32 once.
+ * Inputs (read only): pose_img [T][J][3] float32; status [T], src [T] int32; frames, the float32 frame buffer: [C][H][W] with the
+ *   launch's H, W (sources == NULL), or the ragged buffer of the ABI v19 table `sources`, whose record src[t] gives track t's H, W and
+ *   offset.  The frames must be free of NaN, as for dpp_frame_ingest.  The kernel trusts src[] as every tracking launch does.
+ * Parameters: radius (0 .. DPP_VIS_MAX_RADIUS), margin (mm, > 0 and finite), min_support (1 .. (2 radius + 1)^2), hidden_weight
+ *   (in [0, 1]).
+ * Per track t and joint j with (u, v, z) = pose_img[t][j]:
+ *   status[t] != DPP_TRACK_OK: the whole row is WRITTEN as zeros (vis 0, weight 0, vword 0).
+ *   px = floor((double) u + 0.5), py = floor((double) v + 0.5), compared as doubles before any conversion to int.
+ *   DPP_VIS_OFFFRAME: any of u, v, z not finite, or z <= 0, or px outside [0, W), or py outside [0, H) of the track's source: vis = 0,
+ *     weight = 0.
+ *   Otherwise the window is the pixels (px + dx, py + dy), |dx|, |dy| <= radius, that lie inside the frame: n_in >= 1 of them.  With d
+ *     the pixel's value as double: d == 0 is EMPTY; else d - z < -margin is FRONT; else d - z > margin is BEHIND; else ON.
+ *   vis [T][J] = (float) ((double) n_on / (double) n_in).
+ *   vword [T][J], exactly one class: DPP_VIS_VISIBLE if n_on >= min_support, else DPP_VIS_OCCLUDED if n_front >= min_support, else
+ *     DPP_VIS_UNSUPPORTED (guessed onto background or into a hole).
+ *   weight [T][J] = 1.0f when VISIBLE, else (float) hidden_weight.
+ * One workgroup of one wave per (track, joint), lanes over the window's pixels; the counts are integers, so the order of their
+ * reduction is free.  Vector loads and stores only, no atomics.
+ * DPP_E_BADARG (nothing launched): a NULL pointer (sources may be NULL); T / J / C below 1; radius outside 0 .. DPP_VIS_MAX_RADIUS;
+ * min_support outside 1 .. (2 radius + 1)^2; margin not finite or <= 0; hidden_weight outside [0, 1] (NaN included); without a table
+ * H or W below 1. */
+#define DPP_VIS_MAX_RADIUS 8
+#define DPP_VIS_VISIBLE 1
+#define DPP_VIS_OCCLUDED 2
+#define DPP_VIS_UNSUPPORTED 4
+#define DPP_VIS_OFFFRAME 8
+int dpp_joint_visibility(const float* pose_img, const int* status, const int* src, int T, int J, const float* frames, int C,
+                         const void* sources, int H, int W, int radius, double margin, int min_support, double hidden_weight, float* vis,
+                         float* weight, int* vword, dpp_stream_t stream);
 
 /* ---- whole-frame hand detection by connected components (ABI v14) -------------------------------------------------------------
  * What HandDetector.detect / estimateHandsize (handdetector.py:569-632, :911-937) take from cv2.findContours, restated with
