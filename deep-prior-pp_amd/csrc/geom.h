@@ -1,4 +1,4 @@
-// geom.h -- the camera, crop-bounds and warp-coordinate arithmetic that augment.hip, crop.hip, components.hip, prior.hip, fuse.hip, smooth.hip and visibility.hip share,
+// geom.h -- the camera, crop-bounds and warp-coordinate arithmetic that augment.hip, crop.hip, components.hip, prior.hip, fuse.hip, smooth.hip, visibility.hip and align.hip share,
 // and the workgroup reductions of the whole-frame kernels (crop.hip, components.hip, ingest.hip).
 //
 // Everything here restates NumPy / OpenCV 2.4 arithmetic that rounds after every operation and is pinned bit for bit to the reference,

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(os.path.dirname(_HERE), 'lib', 'libdpp_hip.so')
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 ST_A, ST_B, ST_C, ST_BNX = 1, 2, 4, 8      # DPP_ST_*: which pointers of a call address bf16-stored activation tensors
 c_float_p = C.c_void_p      # device pointers travel as integers
 stream_t = C.c_void_p
@@ -224,6 +224,10 @@ SIGNATURES = {
                                   C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 9 + [stream_t]),
     'dpp_joint_visibility': (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.c_double, C.c_int, C.c_double] + [C.c_void_p] * 3 + [stream_t]),
+    'dpp_pose_align': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_double] * 4 + [C.c_int] +
+                       [C.c_double] * 2 + [C.c_void_p] * 9 + [stream_t]),
+    'dpp_pose_smooth_t': (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_double] * 4 +
+                          [C.c_int, C.c_void_p, C.c_int] + [C.c_double] * 3 + [C.c_int] + [C.c_void_p] * 9 + [stream_t]),
     'dpp_label_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'dpp_component_stats_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'dpp_detect_state_bytes': (C.c_size_t, [C.c_int]),

@@ -14,11 +14,12 @@ again.  Here every launch of that plan runs once per tick for all tracks:
     the pose net's forward plan, built for a batch of T
     pose_finish_ix                  at B = T       the sign rules per track from tflags[t]
     joint_visibility                at T x J       only with `visibility`: every joint classified by the frame's depths around its pixel (below)
+    pose_align                      at B = T       only with `timing`: every track brought to the tick's one instant (below)
     pose_fuse                       at G groups    only with `groups`: the tracks of one hand fused, lost tracks handed over (below)
     extrinsics_accumulate           per source     in pose_fuse's place while a source's extrinsics are being calibrated (below)
     pose_smooth                     at T + G rows  only with `smooth`: the One-Euro filter over the tracked and the fused poses (below)
 
-so the launch count is HandTracker's whatever T and C are (plus one with `groups`, plus one with `smooth`, plus one with `visibility`).  A track names its source (`src`), its hand side and invX / invY
+so the launch count is HandTracker's whatever T and C are (plus one with `groups`, plus one with `smooth`, plus one with `visibility`, plus one with `timing`).  A track names its source (`src`), its hand side and invX / invY
 (`tflags`) and whether it takes part in this tick (`gate`) in three small int32 device arrays; the hand side is data, not a launch
 argument, so there is one plan, not one per flag combination.  C cameras with one hand each is tracks = [(c, False) for c in
 range(C)]; both hands of one camera is tracks = [(0, False), (0, True)]; mixtures are allowed.
@@ -64,8 +65,8 @@ of tracks whose two skeletons differ in shape by more than that -- joint distanc
 out (a track that slid onto something else).  `fused` is [], nothing is handed over, the per-track results are the ungrouped tracker's
 plus 'group'; process_sequence works unchanged.  calibration_report() downloads the sums and fits (calib.solve_rigid: Kabsch on the
 host, with n, rms, cond = s2 / s1 and ok); finish_calibration() also installs the fits when all are ok and rebuilds the plan: from then
-on the tracker builds the launches of one constructed with these extrinsics.  reset_calibration() zeroes the sums.  Out of scope: time
-alignment of the cameras (the pairs are taken as simultaneous), intrinsics, chained calibration through a third camera (every pending
+on the tracker builds the launches of one constructed with these extrinsics.  reset_calibration() zeroes the sums.  Without `timing` the pairs are taken as
+simultaneous; with it they are the aligned poses of one instant (TIMING below).  Out of scope: intrinsics, chained calibration through a third camera (every pending
 source must share a group with the anchor), weighting by joint, drift monitoring after calibration, and re-solving on the device.
 
 SMOOTHING (ABI v22; csrc/smooth.hip; this project's own as well, restated by tests/smooth_ref.py).  The joints of a tick are what the
@@ -82,8 +83,9 @@ pose_img_f (pose_f through the track's own camera) and `smooth`, the row's word;
 the host -- reset(t, com), and through it acquire, acquire_source and the automatic reset from peer_com -- and a set_hand(t, ...) that changes the hand clear
 the track's row (one 4-byte upload); a hand-over on the device does not: the hand is the same one.  While a source is being calibrated
 nothing is fused: the group rows are left out of the launch (their outputs read as zeros) and start empty after finish_calibration().
-`rate` is the tracker's one tick rate.  Out of scope: extrapolating a held pose by the filtered derivative, feeding the filtered centre
-back into the crop, per-source rates or timestamps, filtering com / com3D, and choosing mincutoff / beta for a dataset.  smooth=None:
+`rate` is the tracker's one tick rate; with `timing` the elapsed time comes from the sources' stamps instead and `rate` goes unread
+(TIMING below).  Out of scope: extrapolating a held pose by the filtered derivative, feeding the filtered centre
+back into the crop, filtering com / com3D, and choosing mincutoff / beta for a dataset.  smooth=None:
 allocation, uploads, plan, result block and keys are those of before.
 
 VISIBILITY (ABI v23; csrc/visibility.hip, dpp_pose_fuse_w in csrc/fuse.hip; this project's own as well, restated by
@@ -103,6 +105,29 @@ per-joint hold in the smoother, weighting the calibration pairs by visibility, w
 continuous weights from `vis`, and choosing `margin` for a dataset.  visibility=None: allocation, uploads, plan, result block and keys
 are those of before.
 
+TIMING (ABI v24; csrc/align.hip, dpp_pose_smooth_t in csrc/smooth.hip; this project's own as well, restated by tests/align_ref.py).
+Everything above that combines tracks takes the cameras of a tick as simultaneous and the ticks as a clock.  Depth cameras without a
+sync line are neither: two 30 Hz cameras are up to 17 ms apart, which a hand at 1 m / s turns into 17 mm between the two views -- a
+systematic error of the size of the pose error itself, straight into `fused`, `spread`, the max_dev test and the calibration sums.  With
+timing=dict(max_gap=, max_lead=) (seconds; no defaults: none has been chosen for a rig) process(frames, stamps=, now=) takes one stamp
+per source that delivers a frame -- all on ONE clock -- and the instant `now` the tick's combined outputs refer to (default: the largest
+stamp of the fresh frames; kept in `self.now`); the C + 1 doubles are the tick's one new upload.  ONE launch behind pose_finish (and
+behind joint_visibility, which compares a joint with its own frame and keeps reading the unaligned pose_img) moves every OK track's pose
+and centre from its stamp ts to `now` along the velocity between its previous sample and this one: y = x + (x - x_prev) / (ts - t_prev)
+* (now - ts), when there is a previous sample no older than max_gap and |now - ts| <= max_lead; otherwise the sample goes through as it
+is (`align` == ops.ALIGN_ASIS | NOPREV, GAP or FAR).  The state (the previous stamp, pose and centre per track) lives on the device apart
+from the result block.  pose_fuse / pose_fuse_w and extrinsics_accumulate then read the aligned arrays -- the same kernels, other
+pointers -- so fused[g], spread, the outlier test, peer_com, the centre of a hand-over and the calibration sums all refer to `now`.
+With `smooth` the last launch is dpp_pose_smooth_t: the tracks' rows filter the UNALIGNED pose over the time between their own stamps,
+the groups' rows the fused pose over the time between the ticks' instants; a sample whose stamp is not later than the row's last one is
+refused (ops.SMOOTH_STALE beside HELD / DROPPED); smooth['rate'] is still validated but goes unread.  Per-track results gain pose_t,
+pose_img_t, com3D_t, `lead` (now - ts, s) and `align`, behind every other field of the block.  reset(t, com) -- and through it acquire,
+acquire_source and the automatic reset from peer_com -- and a set_hand that changes the hand clear the track's row (one 4-byte upload
+beside smooth's); a hand-over on the device does not.  process_sequence takes (frames, stamps) or (frames, stamps, now) per tick and keeps
+one stamps buffer per input set, uploaded with that set's frames.  Out of scope: estimating an unknown clock offset between cameras (the
+stamps are taken as one clock), letting an IDLE track coast into the fusion, using the filtered derivative as the velocity, and per-source
+sensor options.  timing=None: allocation, uploads, plans, result block and keys are those of before.
+
 acquire_source(c, frame) finds ALL hands of a source in one detector plan and starts the source's tracks from them; the detectors
 are built per source, at that source's size and focal lengths, on views of its frame slice.
 
@@ -117,12 +142,12 @@ import numpy as np
 
 from . import ops
 from .augmenter import camera_tuple
-from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, refine_stage, smooth_fields, track_fields, valid_centre, visibility_fields
+from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, refine_stage, smooth_fields, timing_fields, track_fields, valid_centre, visibility_fields
 
 
 class MultiTracker(object):
     def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, tracks, sources=None, invX=False, invY=False, fx=None, fy=None,
-                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None, visibility=None):
+                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None, visibility=None, timing=None):
         """
         :param importer:   the dataset importer (the camera) of all sources, or a sequence of C importers, one per source
         :param poseNet, comrefNet: as for HandTracker, but built for a batch of T, the number of tracks: row t is track t
@@ -146,6 +171,9 @@ class MultiTracker(object):
         :param visibility: None, or dict(radius=, margin=, min_support=, hidden_weight=0.0): every joint classified by the frame's depths
                            around its pixel, and with `groups` the fusion weighted by it (VISIBILITY above); radius (pixels), margin (mm)
                            and min_support (pixels) have no default
+        :param timing:     None, or dict(max_gap=, max_lead=) (seconds; neither has a default): every tick carries one stamp per source and
+                           an instant `now`; every track is brought to `now` before tracks are combined, and `smooth` filters over the
+                           stamps -- its `rate` is still validated but goes unread (TIMING above)
         """
         self.rt = rt
         tracks = [(int(s), bool(r)) for s, r in tracks]
@@ -176,6 +204,7 @@ class MultiTracker(object):
         self.max_dev, self.handover = None if max_dev is None else float(max_dev), bool(handover)
         self.smooth = None if smooth is None else ops.smooth_spec(smooth)
         self.visibility = None if visibility is None else ops.visibility_spec(visibility)
+        self.timing = None if timing is None else ops.timing_spec(timing)
         importers = self._per_source(importer, C, 'importer')
         Hs, Ws = self._per_source(H, C, 'H'), self._per_source(W, C, 'W')
         if any(int(h) != h or int(w) != w or h < 1 or w < 1 for h, w in zip(Hs, Ws)):
@@ -233,9 +262,14 @@ class MultiTracker(object):
         if self.smooth is not None:                                                # behind everything else; the state is a buffer of its own
             G = 0 if self.rig is None else self.rig.G
             fields += smooth_fields(T, self.J, G)
-            self.sstate = ops.SmoothState(rt, T + G, self.J)
+            self.sstate = ops.SmoothState(rt, T + G, self.J, timed=self.timing is not None)
         if self.visibility is not None:                                            # behind smooth's as well
             fields += visibility_fields(T, self.J, 0 if self.rig is None else self.rig.G)
+        self.astate = self.stamps = self._stamps2 = self.now = None
+        if self.timing is not None:                                                # behind visibility's as well; the state is a buffer of its own
+            fields += timing_fields(T, self.J)
+            self.astate = ops.AlignState(rt, T, self.J)
+            self.stamps = rt.alloc((C + 1,), np.float64)                           # one stamp per source, then `now`: the tick's one new upload
         self.block = blk = ResultBlock(rt, fields)
         self.res, self._off = blk.buf, blk.offsets
         self.fused = []
@@ -302,12 +336,15 @@ class MultiTracker(object):
         self.com.view(3 * t, (1, 3)).set(com)
         self.com_host[t] = com
         self.lost[t] = False
-        self._clear_smooth(t)
+        self._clear_row(t)
 
-    def _clear_smooth(self, t):
-        """A restart or another hand: what track t follows now is not what was filtered (one 4-byte upload of since[t] = -1)."""
+    def _clear_row(self, t):
+        """A restart or another hand: what track t follows now is not what was filtered (one 4-byte upload of since[t] = -1) nor what
+        its velocity was taken from (with `timing`, one of have[t] = 0)."""
         if self.sstate is not None:
             self.sstate.clear(t)
+        if self.astate is not None:
+            self.astate.clear(t)
 
     def drop(self, t):
         """Mark track t lost: the application knows what the tracker cannot see (the only loss test is a centre at depth 0) -- its
@@ -327,7 +364,7 @@ class MultiTracker(object):
         t = self._track(t)
         flags = (self.flags_host[t] & ~ops.POSE_HAND_RIGHT) | (ops.POSE_HAND_RIGHT if right else 0)
         if flags != self.flags_host[t]:
-            self._clear_smooth(t)
+            self._clear_row(t)
         self.flags_host[t] = flags
         self.tflags.set(self.flags_host)
 
@@ -364,7 +401,7 @@ class MultiTracker(object):
         self.lost[t] = not ok
         self.com_host[t] = coms[0]
         if ok:                                                                     # a restart, as reset(t, com) is
-            self._clear_smooth(t)
+            self._clear_row(t)
         return dict(com=coms[0], cube=cubes[0], found=ok)
 
     def source_detector(self, c, max_extent=None):
@@ -484,6 +521,8 @@ class MultiTracker(object):
             self._gate2 = self.rt.alloc((self.T,), np.int32)
             self._gate2_host = np.zeros(self.T, np.int32)
             self._trackset2 = ops.TrackSet(self.T, self.src, self._gate2, self.tflags, self.table)
+            if self.timing is not None:                                            # the set's own stamps, uploaded with its frames
+                self._stamps2 = self.rt.alloc((self.C + 1,), np.float64)
 
     def plan(self, slot=0):
         """The plan of one tick on input set `slot` (1: process_sequence's second set; without a sensor the second set IS a second
@@ -517,11 +556,18 @@ class MultiTracker(object):
                                            blk.view('vis_weight'), blk.view('vis_class'), table=self.table, H=H, W=W))
                 if self.rig is not None:
                     weighted = dict(weight=blk.view('vis_weight'), fused_weight=blk.view('fused_weight'), name='pose_fuse_w')
+            pose3d, com3d, timed = self.pose3d, self.com3d, {}      # what the launches that COMBINE tracks read
+            if self.timing is not None:                 # every track at the tick's instant; both slots move on the ONE state
+                blk, stamps = self.block, self._stamps2 if slot else self.stamps
+                pose3d, com3d, timed = blk.view('pose_t'), blk.view('com3D_t'), dict(stamps=stamps, C=C)
+                p.add(ops.pose_align(rt, self.pose3d, self.com3d, self.status, self.src, T, self.J, stamps, C, self.timing, self.astate,
+                                     pose3d, blk.view('pose_img_t'), com3d, blk.view('lead'), blk.view('astat'), cam=self.cam,
+                                     table=self.table))
             if self.calibrating:                        # in the fusion launch's place: nothing can be fused or handed over yet
-                p.add(ops.extrinsics_accumulate(rt, self.pose3d, self.status, self.src, T, self.J, self.rig, self.anchor, self.cal_src,
+                p.add(ops.extrinsics_accumulate(rt, pose3d, self.status, self.src, T, self.J, self.rig, self.anchor, self.cal_src,
                                                 self.max_shape_dev, self.acc))
             elif self.rig is not None:                  # the last launch of the main lane: the next tick's prepare is ordered behind it
-                p.add(ops.pose_fuse(rt, self.pose3d, self.com3d, self.status, self.src, T, self.J, self.rig, self.table, H, W, self.cam,
+                p.add(ops.pose_fuse(rt, pose3d, com3d, self.status, self.src, T, self.J, self.rig, self.table, H, W, self.cam,
                                     self.max_dev, self.handover, self.com, self.fused_pose, self.fused_com, self.spread, self.fused_n,
                                     self.peer_com, self.fstat, **weighted))
             if self.smooth is not None:                 # the last launch of the main lane; both slots filter into the ONE state
@@ -531,7 +577,8 @@ class MultiTracker(object):
                     grp = dict(fused_pose=self.fused_pose, n=self.fused_n, G=self.rig.G, fused_pose_f=blk.view('fused_pose_f'),
                                gstat=blk.view('gstat'))
                 p.add(ops.pose_smooth(rt, self.pose3d, self.status, T, self.J, self.smooth, self.sstate, blk.view('pose_f'),
-                                      blk.view('pose_img_f'), blk.view('sstat'), cam=self.cam, src=self.src, table=self.table, **grp))
+                                      blk.view('pose_img_f'), blk.view('sstat'), cam=self.cam, src=self.src, table=self.table,
+                                      **dict(grp, **timed)))  # the tracks' rows filter the UNALIGNED pose at their own stamps
             self._plans[slot] = p
         return self._plans[slot]
 
@@ -581,24 +628,40 @@ class MultiTracker(object):
                 d.update(pose_f=f['pose_f'][t], pose_img_f=f['pose_img_f'][t], smooth=int(f['sstat'][t]))
             if self.visibility is not None:
                 d.update(vis=f['vis'][t], vis_class=f['vis_class'][t])
+            if self.timing is not None:
+                d.update(pose_t=f['pose_t'][t], pose_img_t=f['pose_img_t'][t], com3D_t=f['com3D_t'][t], lead=f['lead'][t], align=int(f['astat'][t]))
             if crops is not None:
                 d['crop'] = crops[t]
             out.append(d)
         return out
 
-    def process(self, frames, return_crop=False):
+    def _stamps(self, stamps, now, fresh):
+        """The tick's stamps checked: None without `timing` (where passing any raises), else the float64 [C + 1] array to upload."""
+        if self.timing is None:
+            if stamps is not None or now is not None:
+                raise ValueError("stamps need a tracker with timing=dict(max_gap=, max_lead=)")
+            return None
+        return ops.tick_stamps(stamps, now, fresh, self.C)
+
+    def process(self, frames, return_crop=False, stamps=None, now=None):
         """One tick: `frames` has one entry per source, None where that source has no new frame.  The fresh frames are uploaded (one
         upload each; `gate` too, only when it differs from the last tick's), ONE plan runs, ONE block is downloaded.  Returns one
         dict per track with HandTracker.process's keys.  status OK: the track was followed.  IDLE: its source had no frame, its
         centre is unchanged.  LOST: it lost the hand in this tick, or is refused (lost before, or never started) until reset(t,
-        com) / acquire(t, frame).  For IDLE and LOST the other entries are finite but meaningless."""
+        com) / acquire(t, frame).  For IDLE and LOST the other entries are finite but meaningless.  With `timing`: `stamps` has one
+        finite time (s) per source that delivers a frame, `now` is the instant the combined outputs refer to (default: the largest
+        stamp of the fresh frames; kept in self.now), and the C + 1 doubles are the tick's one additional upload."""
         if len(frames) != self.C:
             raise ValueError("%d frames for %d sources" % (len(frames), self.C))
         fresh = [None if f is None else self._frame(f, c) for c, f in enumerate(frames)]
+        when = self._stamps(stamps, now, fresh)
         gate = self._gates(fresh)
         for c, f in enumerate(fresh):
             if f is not None:
                 self._input(c).set(f)
+        if when is not None:
+            self.stamps.set(when)
+            self.now = float(when[self.C])
         if not np.array_equal(gate, self.gate_host):
             self.gate.set(gate)
             self.gate_host = gate
@@ -614,7 +677,8 @@ class MultiTracker(object):
         return out
 
     def process_sequence(self, ticks, return_crops=False):
-        """A sequence of ticks (an iterable of per-source frame lists, None for "no frame", as process takes them): the uploads of
+        """A sequence of ticks (an iterable of per-source frame lists, None for "no frame", as process takes them; with `timing` an
+        iterable of (frames, stamps) or (frames, stamps, now), each set's stamps uploaded with its frames): the uploads of
         tick n + 1 run on the copy stream under the plan of tick n (two sets of input buffers, one plan and one `gate` array per
         set, so a plan in flight never sees the next tick's frames or gates), and the result block of tick n is read while tick
         n + 1 is in flight.  Returns one list of per-track dicts per tick, as a process() loop would.
@@ -644,9 +708,15 @@ class MultiTracker(object):
         last = None
         self.fused_ticks = []                           # MultiTracker.fused of every tick of this sequence (empty lists without groups)
         for n, frames in enumerate(ticks):
+            stamps = now = None
+            if self.timing is not None:
+                if not isinstance(frames, tuple) or len(frames) not in (2, 3):
+                    raise ValueError("a timed sequence's ticks are (frames, stamps) or (frames, stamps, now)")
+                frames, stamps, now = frames if len(frames) == 3 else frames + (None,)
             if len(frames) != self.C:
                 raise ValueError("%d frames for %d sources" % (len(frames), self.C))
             fresh = [None if f is None else self._frame(f, c) for c, f in enumerate(frames)]
+            when = self._stamps(stamps, now, fresh)
             k = n & 1
             # self.lost is what the host knows: the results up to tick n - 2
             gate = self._gates(fresh)
@@ -657,6 +727,12 @@ class MultiTracker(object):
                         events.append(rt.staged_upload(self._input(c, k), f[None], free[k]))
                     else:
                         self._input(c, k).set(f)
+            if when is not None:
+                if staged:
+                    events.append(rt.staged_upload(self._stamps2 if k else self.stamps, when, free[k]))
+                else:
+                    (self._stamps2 if k else self.stamps).set(when)
+                self.now = float(when[self.C])
             if not np.array_equal(gate, self._gate2_host if k else self.gate_host):   # the set's own gates: its last plan is behind us
                 gates[k].set(gate)
                 if k:

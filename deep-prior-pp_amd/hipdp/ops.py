@@ -1139,12 +1139,15 @@ def smooth_spec(smooth):
 
 class SmoothState(object):
     """dpp_pose_smooth's device state over R = T + G rows of J joints, allocated apart from anything the host downloads: `since` (int32
-    [R], -1: the row is empty), `xh` and `dxh` (float64 [R][J][3]; unread while since < 0).  clear(r): one 4-byte upload."""
+    [R], -1: the row is empty), `xh` and `dxh` (float64 [R][J][3]; unread while since < 0).  clear(r): one 4-byte upload.  timed: the
+    state of dpp_pose_smooth_t, which adds `tlast` (float64 [R], the row's last sample time; unread while since < 0) as a buffer of its
+    own -- without it the state allocates what it always did."""
 
-    def __init__(self, rt, R, J):
+    def __init__(self, rt, R, J, timed=False):
         self.R, self.J = int(R), int(J)
         self.since = rt.upload(np.full(self.R, -1, np.int32))
         self.xh, self.dxh = rt.alloc((self.R, self.J, 3), np.float64), rt.alloc((self.R, self.J, 3), np.float64)
+        self.tlast = rt.alloc((self.R,), np.float64) if timed else None
         self._empty = np.full(1, -1, np.int32)
 
     def clear(self, r):
@@ -1152,9 +1155,11 @@ class SmoothState(object):
 
 
 def pose_smooth(rt, pose3d, status, T, J, spec, state, pose_f, pose_img_f, sstat, cam=None, src=None, table=None, fused_pose=None, n=None,
-                G=0, fused_pose_f=None, gstat=None, name='pose_smooth'):
+                G=0, fused_pose_f=None, gstat=None, stamps=None, C=None, name=None):
     """dpp_pose_smooth: one workgroup per row of `state` -- T tracks, then G groups (G = 0: no group rows, the four group buffers go
-    unread).  spec: smooth_spec's tuple.  table: an ops.SourceTable with `src`, or None with `cam` for every track."""
+    unread).  spec: smooth_spec's tuple.  table: an ops.SourceTable with `src`, or None with `cam` for every track.  stamps (float64
+    [C + 1] on the device: one per source, then `now`) with C: dpp_pose_smooth_t, the same kernel over real elapsed time on a
+    SmoothState(timed=True); spec's rate goes unread and src (None: every track is source 0) also names the track's stamp."""
     rate, mincutoff, beta, dcutoff, hold = spec
     if state.R < T + G or state.J != J:
         raise ValueError("the state has %d rows of %d joints, the launch %d of %d" % (state.R, state.J, T + G, J))
@@ -1164,11 +1169,103 @@ def pose_smooth(rt, pose3d, status, T, J, spec, state, pose_f, pose_img_f, sstat
     grp = (fused_pose, n, fused_pose_f, gstat) if G else (None,) * 4
     if G and any(b is None for b in grp):
         raise ValueError("G = %d groups need fused_pose, n, fused_pose_f and gstat" % G)
-    return Launch(rt.lib.dpp_pose_smooth,
-                  (pose3d.ptr, status.ptr, _p(src), T, J, _p(grp[0]), _p(grp[1]), int(G), None if table is None else table.dev.ptr, float(fx),
-                   float(fy), float(ux), float(uy), int(flip), rate, mincutoff, beta, dcutoff, hold, state.since.ptr, state.xh.ptr,
-                   state.dxh.ptr, pose_f.ptr, pose_img_f.ptr, sstat.ptr, _p(grp[2]), _p(grp[3])),
-                  (pose3d, status, src, None if table is None else table.dev, state, pose_f, pose_img_f, sstat) + grp, name)
+    head = (pose3d.ptr, status.ptr, _p(src), T, J, _p(grp[0]), _p(grp[1]), int(G), None if table is None else table.dev.ptr, float(fx),
+            float(fy), float(ux), float(uy), int(flip))
+    tail = (state.xh.ptr, state.dxh.ptr, pose_f.ptr, pose_img_f.ptr, sstat.ptr, _p(grp[2]), _p(grp[3]))
+    keep = (pose3d, status, src, None if table is None else table.dev, state, pose_f, pose_img_f, sstat) + grp
+    if stamps is None:
+        return Launch(rt.lib.dpp_pose_smooth, head + (rate, mincutoff, beta, dcutoff, hold, state.since.ptr) + tail, keep, name or 'pose_smooth')
+    if state.tlast is None or C is None or stamps.size < int(C) + 1:
+        raise ValueError("stamps need a timed state and C, the number of sources, with C + 1 stamps")
+    return Launch(rt.lib.dpp_pose_smooth_t, head + (stamps.ptr, int(C), mincutoff, beta, dcutoff, hold, state.since.ptr, state.tlast.ptr) + tail,
+                  keep + (stamps,), name or 'pose_smooth_t')
+
+
+# ---- every track of a tick brought to one instant (include/dpp_hip.h, ABI v24; csrc/align.hip) ------------------------------------------
+ALIGN_NONE, ALIGN_MOVED, ALIGN_ASIS, ALIGN_NOPREV, ALIGN_GAP, ALIGN_FAR = 0, 1, 2, 4, 8, 16        # DPP_ALIGN_*: dpp_pose_align's per-track word
+SMOOTH_STALE = 32                                                                        # DPP_SMOOTH_STALE: dpp_pose_smooth_t's refusal bit
+
+
+def timing_spec(timing):
+    """dict(max_gap=, max_lead=) checked on the host -> (max_gap, max_lead), both in seconds: the longest step between two samples of a
+    track over which a velocity is still formed (> 0), and the farthest a sample is moved to the tick's instant (>= 0).  Neither has a
+    default: none has been chosen for a rig."""
+    known = ('max_gap', 'max_lead')
+    if not isinstance(timing, dict) or set(timing) - set(known):
+        raise ValueError("timing takes max_gap and max_lead, not %r" % (sorted(set(timing) - set(known)) if isinstance(timing, dict) else timing,))
+    missing = [k for k in known if k not in timing]
+    if missing:
+        raise ValueError("timing needs %s: no default has been chosen for a rig" % ', '.join(missing))
+    try:
+        gap, lead = float(timing['max_gap']), float(timing['max_lead'])
+    except (TypeError, ValueError):
+        raise ValueError("timing takes numbers: %r" % (timing,))
+    if not (np.isfinite(gap) and gap > 0.):
+        raise ValueError("max_gap (s) is finite and > 0: %r" % (timing['max_gap'],))
+    if not (np.isfinite(lead) and lead >= 0.):
+        raise ValueError("max_lead (s) is finite and >= 0: %r" % (timing['max_lead'],))
+    return gap, lead
+
+
+def tick_stamps(stamps, now, fresh, C):
+    """The float64 [C + 1] array a timed tick uploads: one finite stamp (s) per source that delivers a frame (`fresh[c]` is not None; a
+    source without one keeps 0., which nothing reads: its tracks are IDLE), then `now` -- by default the largest stamp of the fresh
+    frames."""
+    if stamps is None or len(stamps) != C:
+        raise ValueError("a timed tick needs stamps: one per source (%d), None where the source has no frame" % C)
+    out = np.zeros(C + 1, np.float64)
+    for c in range(C):
+        if fresh[c] is None:
+            continue
+        try:
+            v = float(stamps[c])
+        except (TypeError, ValueError):
+            v = np.nan
+        if not np.isfinite(v):
+            raise ValueError("source %d delivers a frame without a finite stamp: %r" % (c, stamps[c]))
+        out[c] = v
+    live = [out[c] for c in range(C) if fresh[c] is not None]
+    if now is None:
+        now = max(live) if live else 0.
+    if not np.isfinite(float(now)):
+        raise ValueError("now is a finite time in seconds: %r" % (now,))
+    out[C] = float(now)
+    return out
+
+
+class AlignState(object):
+    """dpp_pose_align's device state over T tracks of J joints, never downloaded: `have` (int32 [T], 0: the row is empty), `pt` (float64
+    [T], the previous stamp), `pp` / `pc` (float32 [T][J][3] / [T][3], the previous pose and centre; all three unused while have == 0).
+    clear(t): one 4-byte upload."""
+
+    def __init__(self, rt, T, J):
+        self.T, self.J = int(T), int(J)
+        self.have = rt.upload(np.zeros(self.T, np.int32))
+        self.pt = rt.alloc((self.T,), np.float64)
+        self.pp, self.pc = rt.alloc((self.T, self.J, 3), np.float32), rt.alloc((self.T, 3), np.float32)
+        self._empty = np.zeros(1, np.int32)
+
+    def clear(self, t):
+        self.have.view(int(t), (1,)).set(self._empty)
+
+
+def pose_align(rt, pose3d, com3d, status, src, T, J, stamps, C, spec, state, pose_t, pose_img_t, com3d_t, lead, astat, cam=None, table=None,
+               name='pose_align'):
+    """dpp_pose_align: one workgroup per track.  spec: timing_spec's tuple.  stamps: float64 [C + 1] on the device.  table: an
+    ops.SourceTable with `src`, or None with `cam` for every track (src then still names the track's stamp; None: stamps[0])."""
+    gap, lead_max = spec
+    if state.T < T or state.J != J:
+        raise ValueError("the state has %d rows of %d joints, the launch %d of %d" % (state.T, state.J, T, J))
+    if table is not None and src is None:
+        raise ValueError("a source table needs src")
+    if stamps.size < int(C) + 1:
+        raise ValueError("%d sources need %d stamps" % (C, int(C) + 1))
+    fx, fy, ux, uy, flip = (0., 0., 0., 0., 0) if table is not None else cam
+    return Launch(rt.lib.dpp_pose_align,
+                  (pose3d.ptr, com3d.ptr, status.ptr, _p(src), T, J, stamps.ptr, int(C), None if table is None else table.dev.ptr, float(fx),
+                   float(fy), float(ux), float(uy), int(flip), gap, lead_max, state.have.ptr, state.pt.ptr, state.pp.ptr, state.pc.ptr,
+                   pose_t.ptr, pose_img_t.ptr, com3d_t.ptr, lead.ptr, astat.ptr),
+                  (pose3d, com3d, status, src, stamps, None if table is None else table.dev, state, pose_t, pose_img_t, com3d_t, lead, astat), name)
 
 
 def refine_com_iterative(rt, frames, partial, B, H, W, com_in, cube, fx, fy, num_iter, com_out, status, name='refine_com_iterative'):

@@ -158,9 +158,16 @@ def visibility_fields(T, J, G=0):
     return f
 
 
+def timing_fields(T, J):
+    """What a MultiTracker with `timing` appends to its block, behind every other field (visibility's included): every track's pose, its
+    projection and its centre at the tick's instant, the time it was moved over and dpp_pose_align's word."""
+    f32 = np.float32
+    return [('pose_t', (T, J, 3), f32), ('pose_img_t', (T, J, 3), f32), ('com3D_t', (T, 3), f32), ('lead', (T,), f32), ('astat', (T,), np.int32)]
+
+
 class HandTracker(object):
     def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, hand_right=False, invX=False, invY=False, fx=None, fy=None, sensor=None,
-                 smooth=None, visibility=None):
+                 smooth=None, visibility=None, timing=False):
         """
         :param importer:   the dataset importer (camera; NYU / MSRA flip the y axis)
         :param poseNet:    the pose regressor, built for a batch of one; its output is J x 3 normalised joints
@@ -176,6 +183,9 @@ class HandTracker(object):
         :param visibility: None, or dict(radius=, margin=, min_support=, hidden_weight=0.0): one launch behind pose_finish classifies every
                            joint by the frame's depths around its pixel (hipdp/multitrack.py, VISIBILITY): the result gains `vis`
                            and `vis_class`
+        :param timing:     True (needs `smooth`): every frame carries its stamp (s) and the filter runs over real elapsed time
+                           (dpp_pose_smooth_t; smooth's `rate` is still validated but goes unread).  One camera has nothing to align:
+                           there is no align launch (hipdp/multitrack.py, TIMING)
         """
         self.rt, self.H, self.W = rt, int(H), int(W)
         self.importer = importer
@@ -198,7 +208,12 @@ class HandTracker(object):
         self.cube = rt.alloc((1, 3), f32)
         # everything the host reads per frame is ONE block: pose (mm), pose in image coordinates, centre (= the state), com3D, M, status
         self.smooth = None if smooth is None else ops.smooth_spec(smooth)
-        self.sstate = None if smooth is None else ops.SmoothState(rt, 1, self.J)   # the filter's state: never downloaded
+        self.timing = bool(timing)
+        if self.timing and smooth is None:
+            raise ValueError("timing needs smooth: with one camera the stamps are read by the filter alone")
+        self.sstate = None if smooth is None else ops.SmoothState(rt, 1, self.J, timed=self.timing)   # the filter's state: never downloaded
+        # with `timing` one (stamp, now = stamp) pair per frame buffer, uploaded with the frame
+        self.stamps = [rt.alloc((2,), np.float64) for _ in range(2)] if self.timing else None
         # (+ the detector's seed / cube / status words: acquire; with `smooth` the filtered pose, its projection and the filter's word follow)
         self.visibility = None if visibility is None else ops.visibility_spec(visibility)
         self.vsrc = None if visibility is None else rt.alloc((1,), np.int32)      # the one track's source: 0
@@ -315,8 +330,9 @@ class HandTracker(object):
                                            blk.view('vis_weight'), blk.view('vis_class'), H=H, W=W))
             if self.smooth is not None:
                 blk = self.block
+                timed = dict(stamps=self.stamps[slot], C=1) if self.timing else {}
                 p.add(ops.pose_smooth(rt, self.pose3d, self.status, 1, self.J, self.smooth, self.sstate, blk.view('pose_f'),
-                                      blk.view('pose_img_f'), blk.view('sstat'), cam=self.cam))
+                                      blk.view('pose_img_f'), blk.view('sstat'), cam=self.cam, **timed))
             self._plans[key] = p
         return self._plans[key]
 
@@ -339,12 +355,30 @@ class HandTracker(object):
     def _frame(self, frame):
         return check_frame(frame, self.sensor, (self.H, self.W), 'expected')
 
-    def process(self, frame, return_crop=False):
+    def _stamp(self, stamp):
+        """The frame's stamp checked: None without `timing` (where passing one raises), else the two doubles to upload."""
+        if not self.timing:
+            if stamp is not None:
+                raise ValueError("a stamp needs a tracker with timing=True")
+            return None
+        try:
+            v = float(stamp)
+        except (TypeError, ValueError):
+            v = np.nan
+        if not np.isfinite(v):
+            raise ValueError("a timed frame needs a finite stamp in seconds: %r" % (stamp,))
+        return np.float64([v, v])
+
+    def process(self, frame, return_crop=False, stamp=None):
         """One frame, synchronously: one upload, one plan, one download.  Returns dict(pose [J][3] mm, pose_img [J][3], com [3] image
         coordinates, com3D [3], M [3][3], status[, crop]) -- `crop` as the pose net saw it (normalised; mirrored for HAND_RIGHT).
-        status LOST: see the module docstring; the other entries are finite but meaningless and the tracker needs reset(com)."""
+        status LOST: see the module docstring; the other entries are finite but meaningless and the tracker needs reset(com).  With
+        `timing`, `stamp` is the frame's time in seconds: one more upload of 16 bytes."""
         frame = self._check(frame)
+        when = self._stamp(stamp)
         self.inputs[0].set(frame)
+        if when is not None:
+            self.stamps[0].set(when)
         self._slot = 0
         self.plan(0).run(self.rt)
         self.runs += 1
@@ -356,7 +390,7 @@ class HandTracker(object):
     def process_sequence(self, frames, return_crops=False):
         """A sequence of frames: the upload of frame t + 1 runs under the plan of frame t (two frame buffers, copy stream), the result
         of frame t is read while frame t + 1 is in flight.  Same values as process() frame by frame.  Stops at a lost frame (its
-        result is the last one returned)."""
+        result is the last one returned).  With `timing` the sequence's entries are (frame, stamp)."""
         rt = self.rt
         staged = hasattr(rt, 'staged_upload')
         results, pending, free = [], None, [None, None]
@@ -367,12 +401,21 @@ class HandTracker(object):
             results.append(out)
             return out['status'] == OK
         for n, frame in enumerate(frames):
+            when = None
+            if self.timing:
+                if not isinstance(frame, tuple) or len(frame) != 2:
+                    raise ValueError("a timed sequence's entries are (frame, stamp)")
+                frame, when = frame[0], self._stamp(frame[1])
             frame = self._check(frame)
             k = n & 1
             if staged:
                 rt.wait_event(rt.staged_upload(self.inputs[k], frame[None], free[k]))
+                if when is not None:
+                    rt.wait_event(rt.staged_upload(self.stamps[k], when, free[k]))
             else:
                 self.inputs[k].set(frame)
+                if when is not None:
+                    self.stamps[k].set(when)
             self.plan(k).run(rt)
             self._slot = k
             self.runs += 1

@@ -53,16 +53,28 @@ class CameraDevice(object):
     def getExtrinsics(self):
         raise NotImplementedError("!")
 
+    def getTimestamp(self):
+        """The time in seconds at which the frame last delivered by getDepth() was taken, on the clock all devices of a rig share, or
+        None: the device does not stamp its frames.  (Not in the reference, which has one camera: hipdp/multitrack.py, TIMING.)"""
+        return None
+
 
 class FileDevice(CameraDevice):
     """Loads the frames of a list of files through importer.loadDepthMap (cameradevice.py:348-397).  getDepth() returns
     (True, next frame) and raises IndexError past the last file, as the reference's list indexing does.  The reference sleeps 10 ms
-    per frame (:394) to pace its GUI; a headless player has nothing to pace, so that sleep is left out."""
+    per frame (:394) to pace its GUI; a headless player has nothing to pace, so that sleep is left out.  stamps: None, or a sequence of
+    seconds, one per file -- what a recording's sensor stamped its frames with; getTimestamp() then returns the stamp of the frame last
+    delivered."""
 
-    def __init__(self, filenames, importer, mirror=False):
+    def __init__(self, filenames, importer, mirror=False, stamps=None):
         super(FileDevice, self).__init__(mirror)
         if not isinstance(filenames, list):
             raise ValueError("Files must be list of filenames.")
+        if stamps is not None:
+            stamps = [float(s) for s in stamps]
+            if len(stamps) != len(filenames) or not numpy.isfinite(stamps).all():
+                raise ValueError("stamps must be one finite time in seconds per file")
+        self.stamps = stamps
         self.filenames = filenames
         self.importer = importer
         if hasattr(importer, 'getCameraIntrinsics'):
@@ -84,6 +96,11 @@ class FileDevice(CameraDevice):
         frame = self.importer.loadDepthMap(self.filenames[self.last_depth_num])
         self.last_depth_num += 1
         return True, frame
+
+    def getTimestamp(self):
+        if self.stamps is None or self.last_depth_num == 0:
+            return None
+        return self.stamps[self.last_depth_num - 1]
 
     def getLastDepthNum(self):
         return self.last_depth_num
@@ -179,6 +196,9 @@ class FilteredDevice(CameraDevice):
 
     def getExtrinsics(self):
         return self.device.getExtrinsics()
+
+    def getTimestamp(self):
+        return self.device.getTimestamp()
 
     def __getattr__(self, name):                                       # attributes of the wrapped device (filenames, importer, ...)
         if name == 'device':

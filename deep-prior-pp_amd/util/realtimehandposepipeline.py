@@ -69,6 +69,19 @@ def smoothing_figures(raw, filtered):
     return dict(raw_step=step(raw), filtered_step=step(filtered), distance=dist)
 
 
+def _stamp_of(device, what):
+    """The stamp of the frame `device` delivered last; a device that does not stamp its frames cannot feed a timed pipeline."""
+    stamp = device.getTimestamp() if hasattr(device, 'getTimestamp') else None
+    if stamp is None:
+        raise ValueError("timing needs stamped frames: %s returns no timestamp (FileDevice: stamps=)" % what)
+    return stamp
+
+
+class _Tick(list):
+    """One frame (or None) per device, with the frames' stamps where the pipeline is timed."""
+    stamps = None
+
+
 class RealtimeHandposePipeline(object):
     """Realtime pipeline for handpose estimation"""
 
@@ -85,7 +98,7 @@ class RealtimeHandposePipeline(object):
     DETECTOR_COM = 0
 
     def __init__(self, poseNet, config, di, verbose=False, comrefNet=None, init_com=None, seed_com=False, seed_detect=False, sensor=None,
-                 smooth=None, visibility=None):
+                 smooth=None, visibility=None, timing=False):
         """
         :param poseNet:   network for pose estimation (a built net, or PoseRegNetParams / ResNetParams, with loadFile or not)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=])
@@ -103,6 +116,8 @@ class RealtimeHandposePipeline(object):
         :param visibility: None, or HandTracker's dict(radius=, margin=, min_support=[, hidden_weight=]): processFrame's result gains
                           `vis` (the share of the pixels around each joint that lie at its depth) and `vis_class` (ops.VIS_* per joint),
                           and processVideo leaves the classes of the frames it returns in `vis_classes`
+        :param timing:    True (needs smooth): HandTracker's -- the filter runs over the frames' stamps: processFrame takes stamp=
+                          (seconds) and processVideo reads device.getTimestamp() behind every frame (a device that returns None raises)
         """
         self.importer = di
         self.poseNet = poseNet
@@ -130,6 +145,9 @@ class RealtimeHandposePipeline(object):
         self.poses_f = None
         self.visibility = None if visibility is None else dict(visibility)
         self.vis_classes = None
+        self.timing = bool(timing)
+        if self.timing and smooth is None:
+            raise ValueError("timing needs smooth: with one camera the stamps are read by the filter alone")
 
     def initNets(self):
         """Build the nets from their parameters (loading loadFile where set) and compile their forward plans (:118-141)."""
@@ -271,7 +289,7 @@ class RealtimeHandposePipeline(object):
         if t is None or (t.H, t.W) != (H, W) or (t.fx, t.fy) != (abs(float(cfg['fx'])), abs(float(cfg['fy']))):
             t = self._tracker = HandTracker(default_runtime(), self.importer, self.poseNet, self.comrefNet, H, W, cfg['cube'],
                                             fx=cfg['fx'], fy=cfg['fy'], sensor=self.sensor, smooth=self.smooth,
-                                            visibility=self.visibility)
+                                            visibility=self.visibility, timing=self.timing)
         if tuple(numpy.float32(cfg['cube'])) != tuple(t.cube_host):
             t.set_cube(cfg['cube'])
         t.set_hand(self.hand.value == self.HAND_RIGHT)
@@ -295,8 +313,11 @@ class RealtimeHandposePipeline(object):
             res.update(vis=numpy.zeros(J, numpy.float32), vis_class=numpy.zeros(J, numpy.int32))
         return res
 
-    def processFrame(self, frame):
-        """detect + estimatePose + the de-normalisation of one frame as ONE device plan: the tracker's result dict (pose in mm)."""
+    def processFrame(self, frame, stamp=None):
+        """detect + estimatePose + the de-normalisation of one frame as ONE device plan: the tracker's result dict (pose in mm).  With
+        `timing`, stamp is the frame's time in seconds."""
+        if self.timing and stamp is None:
+            raise ValueError("a pipeline with timing needs every frame's stamp")
         frame = numpy.asarray(frame, numpy.float32) if self.sensor is None else numpy.asarray(frame)     # (a raw frame: the tracker checks its dtype)
         acquiring = self.seed_detect and self.tracking.value and self.state.value != self.STATE_INIT and numpy.allclose(self.lastcom, 0)
         if acquiring:                                  # the centre goes from the detector plan into the tracker's state on the device
@@ -311,7 +332,7 @@ class RealtimeHandposePipeline(object):
         t = self.tracker(*frame.shape)
         if t.lost or not numpy.array_equal(numpy.asarray(lastcom, numpy.float32), numpy.asarray(getattr(self, '_devcom', (0, 0, 0)), numpy.float32)):
             t.reset(lastcom)                           # the host's centre changed behind the device's back (seed, reset, detect())
-        res = t.process(frame)
+        res = t.process(frame, stamp=stamp) if self.timing else t.process(frame)
         self.lastcom = (0, 0, 0) if res['status'] else res['com'].copy()
         self._devcom = self.lastcom
         self.sync.update(fid=self.sync['fid'] + 1, com3D=res['com3D'], M=res['M'])
@@ -333,8 +354,9 @@ class RealtimeHandposePipeline(object):
             if ret is False:
                 print("Error while reading frame.")
                 break
+            stamp = _stamp_of(device, 'the device') if self.timing else None
             start = time.time()
-            res = self.processFrame(frame)
+            res = self.processFrame(frame, stamp) if self.timing else self.processFrame(frame)
             times.append(time.time() - start)
             if res['status']:
                 print("Track lost (or no hand) in frame {}.".format(len(times) - 1))
@@ -457,12 +479,17 @@ class MultiStreamPipeline(object):
 
     Visibility (hipdp/multitrack.py, VISIBILITY): visibility=dict(radius=, margin=, min_support=[, hidden_weight=]) goes to MultiTracker:
     the results carry vis / vis_class per joint, the fusion is weighted by them, `fused` carries `weight`, and processVideos leaves
-    in `vis_classes` the classes of exactly the ticks that its return value holds."""
+    in `vis_classes` the classes of exactly the ticks that its return value holds.
+
+    Timing (hipdp/multitrack.py, TIMING): timing=dict(max_gap=, max_lead=) goes to MultiTracker: every tick carries the stamps that the
+    devices report for their frames (CameraDevice.getTimestamp(); a device that returns None for a delivered frame raises), `now` is
+    the latest of them, the results carry pose_t / pose_img_t / com3D_t / lead / align, `fused` refers to `now`, and processVideos
+    leaves in `poses_t` the aligned poses of exactly the ticks that its return value holds."""
 
     HAND_LEFT, HAND_RIGHT = RealtimeHandposePipeline.HAND_LEFT, RealtimeHandposePipeline.HAND_RIGHT
 
     def __init__(self, poseNet, config, di, devices, hands, comrefNet, init_com=None, seed_detect=False, sensor=None, verbose=False,
-                 max_extent=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None, visibility=None):
+                 max_extent=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None, visibility=None, timing=None):
         """
         :param poseNet, comrefNet: built nets or their parameters (as for RealtimeHandposePipeline), with batchSize == len(hands)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=]); fx / fy: one value, or a list with one per device
@@ -477,7 +504,10 @@ class MultiStreamPipeline(object):
         :param calibrate: MultiTracker's: entries of config['extrinsics'] may then be None, to be found by calibrateExtrinsics
         :param smooth:    MultiTracker's: the One-Euro filter over the tracked and the fused poses
         :param visibility: MultiTracker's: every joint classified by the frame around it, the fusion weighted by that
+        :param timing:    MultiTracker's: the devices' stamps carried through the plan, every track brought to the tick's instant
         """
+        self.timing = None if timing is None else dict(timing)
+        self.poses_t = None
         self.visibility = None if visibility is None else dict(visibility)
         self.vis_classes = None
         self.smooth = None if smooth is None else dict(smooth)
@@ -531,7 +561,7 @@ class MultiStreamPipeline(object):
                                          invX=cfg.get('invX') is True, invY=cfg.get('invY') is True, fx=cfg['fx'], fy=cfg['fy'],
                                          sensor=self.sensor, extrinsics=cfg.get('extrinsics'), groups=self.groups, max_dev=self.max_dev,
                                          handover=self.handover, calibrate=self.calibrate, smooth=self.smooth,
-                                         visibility=self.visibility)
+                                         visibility=self.visibility, timing=self.timing)
             self._tracker_key = shapes
             self._seeded = [False] * len(self.hands)
         return self._tracker
@@ -550,10 +580,23 @@ class MultiStreamPipeline(object):
         return [t for t, (d, _) in enumerate(self.hands) if mt.lost[t] and frames[d] is not None and
                 ((not self._seeded[t] and self.init_com[t] is not None) or self.seed_detect)]
 
-    def processFrames(self, frames):
+    def _stamps_for(self, frames, stamps):
+        """A timed tick's stamps: those given, else the ones _read() took from the devices with these frames."""
+        if self.timing is None:
+            if stamps is not None:
+                raise ValueError("stamps need a pipeline with timing=")
+            return None
+        stamps = getattr(frames, 'stamps', None) if stamps is None else stamps
+        if stamps is None:
+            raise ValueError("a pipeline with timing needs one stamp per frame")
+        return stamps
+
+    def processFrames(self, frames, stamps=None):
         """One tick: one frame (or None) per device -> one result dict per track (MultiTracker.process).  Tracks without a centre are
         seeded first: from init_com once, else (seed_detect) by detection in their device's frame -- one detector plan per device
-        for all its lost tracks."""
+        for all its lost tracks.  With `timing`: stamps has one time (s) per frame (default: what the devices reported when _read()
+        fetched these frames)."""
+        stamps = self._stamps_for(frames, stamps)
         mt = self._tracker_for(frames)
         search = set()
         for t, (d, _) in enumerate(self.hands):
@@ -566,7 +609,7 @@ class MultiStreamPipeline(object):
             self._seeded[t] = True
         for d in sorted(search):
             mt.acquire_source(d, frames[d], max_extent=self.max_extent)
-        res = mt.process(frames)
+        res = mt.process(frames) if stamps is None else mt.process(frames, stamps=stamps)
         self.fused = mt.fused
         return res
 
@@ -596,13 +639,15 @@ class MultiStreamPipeline(object):
 
     def _read(self):
         """One frame (or None) per device; None when a FileDevice has ended or no device delivered."""
-        frames = []
+        frames = _Tick()
         try:
             for dev in self.devices:
                 ret, frame = dev.getDepth()
                 frames.append(frame if ret is not False else None)
         except IndexError:
             return None
+        if self.timing is not None:
+            frames.stamps = [None if f is None else _stamp_of(dev, 'device %d' % d) for d, (dev, f) in enumerate(zip(self.devices, frames))]
         if all(f is None for f in frames):
             print("Error while reading frames.")
             return None
@@ -629,7 +674,7 @@ class MultiStreamPipeline(object):
 
         fused_poses = [[] for _ in (self.groups or [])]
         poses_f, fused_poses_f = [[] for _ in self.hands], [[] for _ in (self.groups or [])]
-        vis_classes = [[] for _ in self.hands]
+        vis_classes, poses_t = [[] for _ in self.hands], [[] for _ in self.hands]
 
         def collect(res, tick, fused):
             for g, f in enumerate(fused):
@@ -644,6 +689,8 @@ class MultiStreamPipeline(object):
                         poses_f[t].append(r['pose_f'].copy())
                     if self.visibility is not None:
                         vis_classes[t].append(r['vis_class'].copy())
+                    if self.timing is not None:
+                        poses_t[t].append(r['pose_t'].copy())
                 elif r['status'] == 1:
                     print("Track {} lost (or no hand) in tick {}.".format(t, tick))
 
@@ -661,7 +708,7 @@ class MultiStreamPipeline(object):
                     state['carry'] = frames
                     return
                 state['ticks'] += 1
-                yield frames
+                yield frames if self.timing is None else (list(frames), frames.stamps)
         while go_on():
             frames, state['carry'] = (state['carry'], None) if state['carry'] is not None else (self._read(), None)
             if frames is None:
@@ -694,4 +741,6 @@ class MultiStreamPipeline(object):
             self.fused_poses_f = [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in fused_poses_f]
         if self.visibility is not None:
             self.vis_classes = [numpy.asarray(c, numpy.int32).reshape(-1, J) for c in vis_classes]
+        if self.timing is not None:
+            self.poses_t = [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in poses_t]
         return [numpy.asarray(p, numpy.float32).reshape(-1, J, 3) for p in poses]

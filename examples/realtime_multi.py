@@ -43,6 +43,13 @@ track; with --fuse the fusion is weighted by it (a joint that is not visible wei
 pixel coordinates) and makes two more runs without output, the unoccluded one and the occluded one without --visibility, to print the
 mean distance of the fused joints from the unoccluded run's, weighted and unweighted: sanity figures, not bars.
 
+--fuse --stamps RATE [--lag-second N] stamps the frames: camera 0 delivers frame i in tick i with the stamp i / RATE, camera 1 frame
+max(i - N, 0) with the stamp (i - N) / RATE -- a camera that runs N frames behind and says so.  The tracker carries the stamps through the
+plan (MultiTracker timing=, this project's own): every track is moved to the tick's instant along its own velocity before the two are
+fused (max_gap = 4 / RATE, max_lead = (N + 1) / RATE: the example's choice, no default exists).  Two more runs without output, the
+synchronous one (N = 0, no timing) and the lagging one without timing, give the mean distance of the fused joints from the synchronous
+run's with and without timing: sanity figures, not bars.
+
     python examples/realtime_multi.py --dataset icvl --data ../data/ICVL/ --seqs test_seq_1 test_seq_2
 """
 import argparse
@@ -131,10 +138,16 @@ def print_visibility(t, shares):
     print("track {}, visibility: ".format(t) + ', '.join("{} {:.3f}".format(name, shares[name]) for name, _ in CLASSES))
 
 
-def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands, occlude=None, visibility=True):
+def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands, occlude=None, visibility=True, lag=0, timing=False):
     """--fuse: one sequence through two cameras, the two tracks of its hand fused; returns a dict of what is printed.  occlude: None or
-    (x0, y0, x1, y1, depth), the rectangle written into camera 1's frames; visibility False: without --visibility whatever args say."""
+    (x0, y0, x1, y1, depth), the rectangle written into camera 1's frames; visibility False: without --visibility whatever args say.
+    lag: camera 1 delivers frame max(i - lag, 0) in tick i; timing: the frames are stamped (--stamps) and the tracker reads the stamps."""
     files = [f.fileName for f in seqs[0].data]
+    files1, stamped, time_kw = [files[max(i - lag, 0)] for i in range(len(files))], [{}, {}], {}
+    if timing:
+        rate = float(args.stamps)
+        stamped = [dict(stamps=[i / rate for i in range(len(files))]), dict(stamps=[(i - lag) / rate for i in range(len(files))])]
+        time_kw = dict(timing=dict(max_gap=4. / rate, max_lead=(lag + 1.) / rate))
     H, W = numpy.asarray(di.loadDepthMap(files[0])).shape
     H2, W2 = (H + 1) // 2, (W + 1) // 2
     di2 = upside_down_half_res_importer(di, H2, W2)
@@ -146,9 +159,10 @@ def fuse_demo(args, di, seqs, config, poseNetParams, comrefNetParams, hands, occ
                extrinsics=[true_ext[0], None] if n_cal else true_ext)        # calibrating: camera 1's pose is withheld from the tracker
     c0 = numpy.asarray(seqs[0].data[0].gtorig[di.crop_joint_idx], numpy.float32)
     seeds = [c0, numpy.float32([(W2 - 1) - c0[0] / 2., (H2 - 1) - c0[1] / 2., c0[2]])]
-    devices = [FileDevice(files, di), UpsideDownHalfResFileDevice(files, di)]
+    devices = [FileDevice(files, di, **stamped[0]), UpsideDownHalfResFileDevice(files1, di, **stamped[1])]
     msp = MultiStreamPipeline(poseNetParams, cfg, [di, di2], devices, hands, comrefNetParams, init_com=seeds, groups=[[0, 1]],
-                              max_dev=args.max_dev, calibrate=dict(anchor=0) if n_cal else None, **dict(smooth_arg(args), **vis_kw))
+                              max_dev=args.max_dev, calibrate=dict(anchor=0) if n_cal else None,
+                              **dict(smooth_arg(args), **dict(vis_kw, **time_kw)))
     drop = range(0)
     if args.drop_second:
         a, b = (int(v) for v in args.drop_second.split(':'))
@@ -262,6 +276,9 @@ def main(argv=None):
     ap.add_argument('--hidden-weight', type=float, default=0., metavar='W', help='with --visibility: what a joint that is not visible weighs in the fusion')
     ap.add_argument('--occlude-second', default=None, metavar='X0:Y0:X1:Y1:DEPTH',
                     help="with --fuse --visibility: a rectangle of DEPTH mm written into camera 1's frames")
+    ap.add_argument('--stamps', type=float, default=None, metavar='RATE',
+                    help='with --fuse: the frames are stamped at RATE per second and the tracker aligns the tracks in time before it fuses them')
+    ap.add_argument('--lag-second', type=int, default=0, metavar='N', help='with --fuse --stamps: camera 1 runs N frames behind camera 0')
     ap.add_argument('--cache', default='./cache/')
     args = ap.parse_args(argv)
     Importer, seq_names, config = DATASETS[args.dataset]
@@ -286,12 +303,24 @@ def main(argv=None):
     config = dict(config, cube=tuple(seqs[0].config['cube']))
     if args.occlude_second and not (args.fuse and args.visibility is not None):
         raise SystemExit("--occlude-second compares the weighted with the unweighted fusion: it needs --fuse and --visibility")
+    if args.stamps is not None and not (args.fuse and numpy.isfinite(args.stamps) and args.stamps > 0. and not args.occlude_second):
+        raise SystemExit("--stamps RATE (> 0) stamps the two cameras of --fuse (not together with --occlude-second)")
+    if args.lag_second and (args.stamps is None or args.lag_second < 0):
+        raise SystemExit("--lag-second N (>= 0) needs --stamps")
     if args.fuse:
-        demo = (args, di, seqs, config, poseNetParams, comrefNetParams, hands)
-        if not args.occlude_second:
-            return fuse_demo(*demo)
         import contextlib
         import io
+        demo = (args, di, seqs, config, poseNetParams, comrefNetParams, hands)
+        if args.stamps is not None:
+            out = fuse_demo(*demo, lag=args.lag_second, timing=True)
+            with contextlib.redirect_stdout(io.StringIO()):            # the two runs to compare with: their own output is not repeated
+                sync, untimed = fuse_demo(*demo), fuse_demo(*demo, lag=args.lag_second)
+            out['lagging'] = dict(timed=fused_distance(out, sync), untimed=fused_distance(untimed, sync))
+            print("camera 1 lagging by {} frames (sanity figures): fused joints {timed:.3f} mm from the synchronous run's with timing, "
+                  "{untimed:.3f} mm without".format(args.lag_second, **out['lagging']))
+            return out
+        if not args.occlude_second:
+            return fuse_demo(*demo)
         occlude = tuple(float(v) for v in args.occlude_second.split(':'))
         if len(occlude) != 5:
             raise SystemExit("--occlude-second takes X0:Y0:X1:Y1:DEPTH")

@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 23
+#define DPP_ABI_VERSION 24
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -767,6 +767,68 @@ int dpp_pose_smooth(const float* pose3d, const int* status, const int* src, int 
 int dpp_joint_visibility(const float* pose_img, const int* status, const int* src, int T, int J, const float* frames, int C,
                          const void* sources, int H, int W, int radius, double margin, int min_support, double hidden_weight, float* vis,
                          float* weight, int* vword, dpp_stream_t stream);
+
+/* ---- every track of a tick brought to one instant (ABI v24; csrc/align.hip, dpp_pose_smooth_t in csrc/smooth.hip) -------------------------
+ * Cameras without a hardware sync line are not simultaneous: two 30 Hz cameras are up to half a period apart, and a hand at 1 m / s is
+ * then seen 17 mm apart by the two.  Every sensor stamps its frames.  ONE launch per tick behind dpp_pose_finish (and behind
+ * dpp_joint_visibility, which compares a joint with its own frame and keeps reading the unaligned pose_img) and before dpp_pose_fuse /
+ * dpp_pose_fuse_w / dpp_extrinsics_accumulate / dpp_pose_smooth_t moves every track's pose and centre from its source's stamp to the
+ * tick's instant `now` along the velocity between the track's previous sample and this one.  The launches that combine tracks then read
+ * pose_t / com3d_t in place of pose3d / com3d.  The reference has one camera and no counterpart: these semantics are THIS PROJECT'S
+ * OWN, restated in NumPy float64 by tests/align_ref.py and pinned to it bit for bit.  All arithmetic is float64 in the order given
+ * (+ - * /, no FMA contraction); every output is rounded to float32 once.
+ * Inputs (read only): pose3d [T][J][3], com3d [T][3] float32 (camera frame, mm); status [T], src [T] int32; stamps [C + 1] float64 in
+ *   device memory: stamps[c] is the time (s) of source c's frame of this tick, stamps[C] is `now`, the instant the tick's combined
+ *   outputs refer to.  All stamps are on ONE clock and finite (the host checks).  The kernel trusts src[] as every tracking launch does.
+ * Parameters, launch scalars: max_gap (s, > 0, finite), max_lead (s, >= 0, finite).
+ * State, device memory, updated in place, never downloaded: have [T] int32, 0: the row is empty (what a fresh state holds, and what
+ *   the host writes to clear a row); pt [T] float64, the previous stamp; pp [T][J][3], pc [T][3] float32, the previous pose and centre.
+ *   pt / pp / pc are not used while have == 0, so only `have` needs initialising.
+ * Per track t, with ts = stamps[src[t]], dt = ts - pt[t], lead = now - ts:
+ *   status[t] != DPP_TRACK_OK:  word DPP_ALIGN_NONE; all outputs of the row are zero, the state is untouched (a stale state is refused
+ *                       later by max_gap).
+ *   OK, have[t] != 0, dt > 0, dt <= max_gap and fabs(lead) <= max_lead:  word DPP_ALIGN_MOVED.  Per coordinate x with its previous
+ *                       value xp: v = ((double) x - (double) xp) / dt, y = (double) x + v * lead, out = (float) y; the same for the three
+ *                       coordinates of com3d against pc.
+ *   OK otherwise:       word DPP_ALIGN_ASIS with ONE reason bit, the first that applies: DPP_ALIGN_NOPREV (have[t] == 0), DPP_ALIGN_GAP
+ *                       (not dt > 0, or dt > max_gap), DPP_ALIGN_FAR (not fabs(lead) <= max_lead).  The outputs are the inputs' bits.
+ *   In both OK cases the state becomes the UNALIGNED sample afterwards: have = 1, pt = ts, pp = pose3d[t], pc = com3d[t].
+ * Outputs: pose_t [T][J][3]; pose_img_t [T][J][3] = that float32 joint projected by the track's own camera with joint3DToImg on a
+ *   float32 array, exactly as dpp_pose_finish projects pose3d (a NONE row is all zeros: it is not projected); com3d_t [T][3]; lead [T]
+ *   float32 = (float) lead, 0 for NONE; astat [T] int32, the word.
+ * Camera: sources == NULL (src may then be NULL too: every track is source 0 with the camera of the launch scalars) or the ABI v19
+ *   table with src [T].
+ * One workgroup of one wave per track; lanes stride over the joints, a joint's three coordinates in one lane; vector loads and stores
+ * only, no atomics.  Ticks on one state must be stream-ordered.
+ * DPP_E_BADARG (nothing launched): a NULL required pointer (sources and src may be NULL together, a table needs src); T / J / C below
+ * 1; max_gap not finite or <= 0; max_lead not finite or < 0; without a table a zero focal length.
+ * Out of scope: estimating an unknown clock offset between cameras, letting an IDLE track coast into the fusion, using the filtered
+ * derivative as the velocity. */
+#define DPP_ALIGN_NONE 0
+#define DPP_ALIGN_MOVED 1
+#define DPP_ALIGN_ASIS 2
+#define DPP_ALIGN_NOPREV 4
+#define DPP_ALIGN_GAP 8
+#define DPP_ALIGN_FAR 16
+int dpp_pose_align(const float* pose3d, const float* com3d, const int* status, const int* src, int T, int J, const double* stamps, int C,
+                   const void* sources, double fx, double fy, double ux, double uy, int flip_y, double max_gap, double max_lead, int* have,
+                   double* pt, float* pp, float* pc, float* pose_t, float* pose_img_t, float* com3d_t, float* lead, int* astat,
+                   dpp_stream_t stream);
+
+/* dpp_pose_smooth over real time: dpp_pose_smooth's kernel body and semantics with these differences and no others.  `rate` is not
+ * an argument.  stamps [C + 1] float64 (device) as above; tlast [R] float64, one more state array (a buffer of its own, not read while
+ * since < 0).  The sample time s of track row r is stamps[src[r]] (stamps[0] when src is NULL), of group row T + g stamps[C].
+ *   valid, since < 0:   as dpp_pose_smooth, and tlast = s.
+ *   valid, since >= 0, Te = s - tlast > 0:  as dpp_pose_smooth's OK branch with this Te, and tlast = s.
+ *   valid, since >= 0, Te not > 0:  the sample is refused: the row takes the not-valid path (HELD / DROPPED / EMPTY by the max_hold
+ *                       rule, which keeps counting ticks) with the additional bit DPP_SMOOTH_STALE; xh / dxh / tlast keep their bits.
+ * Track rows filter the unaligned pose3d at the track's own stamps; group rows filter the fused pose at `now`.
+ * DPP_E_BADARG: as dpp_pose_smooth without `rate`, and stamps or tlast NULL, C below 1. */
+#define DPP_SMOOTH_STALE 32
+int dpp_pose_smooth_t(const float* pose3d, const int* status, const int* src, int T, int J, const float* fused_pose, const int* n, int G,
+                      const void* sources, double fx, double fy, double ux, double uy, int flip_y, const double* stamps, int C,
+                      double mincutoff, double beta, double dcutoff, int max_hold, int* since, double* tlast, double* xh, double* dxh,
+                      float* pose_f, float* pose_img_f, int* sstat, float* fused_pose_f, int* gstat, dpp_stream_t stream);
 
 /* ---- whole-frame hand detection by connected components (ABI v14) -------------------------------------------------------------
  * What HandDetector.detect / estimateHandsize (handdetector.py:569-632, :911-937) take from cv2.findContours, restated with

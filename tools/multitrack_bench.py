@@ -51,6 +51,13 @@ Further legs, same protocol (a child process per leg, the legs alternating, 2 pr
                                grouped tick.  Claims, as for --smooth: (1) without `visibility` the tick and the plan's device time are
                                each within the larger spread of the parent's; (2) the plan with `visibility` costs at most ONE average
                                launch of that plan plus the larger spread of the two device-time legs more than the plan without.
+  --timing --parent DIR        the grouped tick with timing=dict(max_gap=0.1, max_lead=0.02) (one more launch, dpp_pose_align, at T
+                               workgroups behind pose_finish; the fusion launch reads the aligned poses; every tick uploads C + 1 stamps,
+                               source c stamped 2 c ms before source 0) at T = C = 8 in two groups of four, against this tree's grouped
+                               tick without `timing` and the PARENT's grouped tick.  Claims, as for --smooth: (1) without `timing` the
+                               tick and the plan's device time are each within the larger spread of the parent's; (2) the plan with
+                               `timing` costs at most ONE average launch of that plan plus the larger spread of the two device-time legs
+                               more than the plan without.  No wall-clock claim: the tick gains one small upload and a larger download.
 --configs 1x1,8x8 overrides a leg's (T, C) list.
 
 As in tools/track_bench.py the refinement net's last layer is zeroed, so every track stays on its seed whatever the random weights
@@ -237,6 +244,34 @@ def child(args):
             out['smooth_device_ms_' + _key(T, C)] = device_time(mt.plan())
             out['smooth_launches_' + _key(T, C)] = len(mt.plan().launches())
             out['smooth_block_bytes_' + _key(T, C)] = 4 * int(mt.res.size)
+    elif args.leg == 'timing':
+        from hipdp import ops
+        from hipdp.multitrack import MultiTracker
+        eye = (np.eye(3), np.zeros(3))
+        for T, C in configs:
+            pnet, snet = nets(T)
+            tracks = [(t % C, bool(t // C)) for t in range(T)]
+            half = max(1, T // 2)
+            groups = [g for g in (list(range(half)), list(range(half, T))) if g]
+            mt = MultiTracker(rt, di, pnet, snet, 480, 640, cube, tracks, extrinsics=[eye] * C, groups=groups, max_dev=50.,
+                              timing=dict(max_gap=0.1, max_lead=0.02))
+            for t in range(T):
+                mt.reset(t, com0)
+            clock = [0]
+
+            def tick(i):
+                clock[0] += 1                                           # the stamps go on over the repetitions: every tick is MOVED
+                res = mt.process(tick_frames(i, C), stamps=[clock[0] / 30. - 0.002 * c for c in range(C)])
+                assert all(r['status'] == 0 and r['align'] == ops.ALIGN_MOVED for r in res) and all(f['n'] == len(g) for f, g in zip(mt.fused, groups))
+            mt.process(tick_frames(0, C), stamps=[-0.002 * c for c in range(C)])    # the tick that starts every row
+            for i in range(10):
+                tick(i)
+            names = [l.name for l in mt.plan().launches()]
+            assert names[-2:] == ['pose_align', 'pose_fuse'], names[-3:]
+            out['timing_ms_' + _key(T, C)] = timed(tick)
+            out['timing_device_ms_' + _key(T, C)] = device_time(mt.plan())
+            out['timing_launches_' + _key(T, C)] = len(mt.plan().launches())
+            out['timing_block_bytes_' + _key(T, C)] = 4 * int(mt.res.size)
     elif args.leg == 'vis':
         from hipdp import ops
         from hipdp.multitrack import MultiTracker
@@ -363,7 +398,8 @@ def main():
     ap.add_argument('--calibrate', action='store_true', help="the calibrating and the calibrated tick against this tree's and the parent's ticks (needs --parent)")
     ap.add_argument('--smooth', action='store_true', help="the grouped tick with the One-Euro filter against this tree's and the parent's grouped tick (needs --parent)")
     ap.add_argument('--visibility', action='store_true', help="the grouped tick with joint visibility and the weighted fusion against this tree's and the parent's grouped tick (needs --parent)")
-    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse', 'fuse_tick', 'calib', 'smooth', 'vis'], default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--timing', action='store_true', help="the grouped tick with stamps and the alignment launch against this tree's and the parent's grouped tick (needs --parent)")
+    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse', 'fuse_tick', 'calib', 'smooth', 'vis', 'timing'], default=None, help=argparse.SUPPRESS)
     ap.add_argument('--tree', default=ROOT, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.leg:
@@ -511,6 +547,38 @@ def main():
                 print("  claim 2 is missed by %.2f us" % (extra - bar))
             print("  wall clock with visibility over without: %+.4f ms (no claim: the download grows by %d bytes)"
                   % (s[0] - f[0], res['vis_block_bytes_' + k] - res['fuse_block_bytes_' + k]))
+            ok = fits and ok
+        return 0 if ok else 1
+    if args.timing:
+        if not args.parent:
+            raise SystemExit("--timing compares against --parent DIR")
+        cfgs = args.configs or '8x8'
+        res = run_legs([('fuse_tick', ytree, 'parent_'), ('fuse_tick', ROOT, ''), ('timing', ROOT, '')], cfgs)
+        print("the grouped tick with timing= (two groups of T / 2 tracks; one more launch, dpp_pose_align, at T workgroups behind pose_finish; "
+              "the fusion reads the aligned poses; C + 1 stamps uploaded per tick) against the grouped tick without it of this tree and of the "
+              "parent checkout; " + head)
+        print("all times in ms per tick: median (spread = max - min over the repetitions)")
+        ok = True
+        for c in cfgs.split(','):
+            T, C = (int(v) for v in c.split('x'))
+            k = _key(T, C)
+            s, f, y = _stat(res['timing_ms_' + k]), _stat(res['fuse_ms_' + k]), _stat(res['parent_fuse_ms_' + k])
+            ds, df, dy = _stat(res['timing_device_ms_' + k]), _stat(res['fuse_device_ms_' + k]), _stat(res['parent_fuse_device_ms_' + k])
+            nl = res['timing_launches_' + k]
+            per = ds[0] / nl
+            print("T = C = %d, wall clock: with timing %.4f (%.4f), without %.4f (%.4f), parent %.4f (%.4f)" % ((T,) + s + f + y))
+            print("T = C = %d, plan device time: with timing %.4f (%.4f), without %.4f (%.4f), parent %.4f (%.4f); launches %d / %d / %d; device "
+                  "time per launch of the timed plan %.2f us" % ((T,) + ds + df + dy + (nl, res['fuse_launches_' + k], res['parent_fuse_launches_' + k], per * 1e3)))
+            ok = two_sided('T = C = %d, claim 1, the tick without timing' % T, f, y, 'this tree', 'the parent') and ok
+            ok = two_sided('T = C = %d, claim 1, the plan device time without timing' % T, df, dy, 'this tree', 'the parent') and ok
+            extra, bar = (ds[0] - df[0]) * 1e3, (per + max(ds[1], df[1])) * 1e3
+            fits = extra <= bar
+            print("verdict T = C = %d, claim 2, plan device time with timing over the plan without: %+.2f us; one average launch %.2f us + larger "
+                  "spread %.2f us = %.2f us -> %s" % (T, extra, per * 1e3, max(ds[1], df[1]) * 1e3, bar, 'holds' if fits else 'DOES NOT hold'))
+            if not fits:
+                print("  claim 2 is missed by %.2f us" % (extra - bar))
+            print("  wall clock with timing over without: %+.4f ms (no claim: one upload of %d bytes more, the download grows by %d bytes)"
+                  % (s[0] - f[0], 8 * (C + 1), res['timing_block_bytes_' + k] - res['fuse_block_bytes_' + k]))
             ok = fits and ok
         return 0 if ok else 1
     if args.calibrate:
