@@ -118,13 +118,16 @@ __global__ __launch_bounds__(RPL_THREADS) void reduce_partials_loss_kernel(const
 // broadcastable column in Theano -- minus the VECTOR y (B,) is the (B, B) matrix o_i - y_j, so
 //   cost = mean_i mean_j (o_i - y_j)^2 ,   d cost / d o_i = (2 / B) (o_i - mean(y)).
 // (Whatever the authors meant, this is what the graph computes.)  One block; sums in f64.
+// The four sums are taken of o - p and y - p with the pivot p = y[0]: o_i - y_j does not change, but the expanded form below cancels
+// the digits of the common offset (targets at 1000 +- 1e-3: eleven of the sixteen a double has), and mean(y) = p + sum / B.
 __global__ __launch_bounds__(DPP_THREADS) void loss_sse_bcast_kernel(const float* __restrict__ out, const float* __restrict__ y, int n,
                                                                      float* __restrict__ cost, float* __restrict__ dout,
                                                                      float* __restrict__ err) {
     __shared__ double s[4][DPP_THREADS];
+    const double pivot = (double)y[0];
     double so = 0.0, soo = 0.0, sy = 0.0, syy = 0.0;
     for (int i = threadIdx.x; i < n; i += DPP_THREADS) {
-        const double o = out[i], t = y[i];
+        const double o = (double)out[i] - pivot, t = (double)y[i] - pivot;
         so += o; soo += o * o; sy += t; syy += t * t;
     }
     s[0][threadIdx.x] = so; s[1][threadIdx.x] = soo; s[2][threadIdx.x] = sy; s[3][threadIdx.x] = syy;
@@ -134,10 +137,10 @@ __global__ __launch_bounds__(DPP_THREADS) void loss_sse_bcast_kernel(const float
             for (int k = 0; k < 4; ++k) s[k][threadIdx.x] += s[k][threadIdx.x + w];
         __syncthreads();
     }
-    const double B = (double)n, ybar = s[2][0] / B;
+    const double B = (double)n, ybar = s[2][0] / B;             // mean(y) - pivot
     if (threadIdx.x == 0) cost[0] = (float)((B * s[1][0] - 2.0 * s[0][0] * s[2][0] + B * s[3][0]) / (B * B));
     if (dout)
-        for (int i = threadIdx.x; i < n; i += DPP_THREADS) dout[i] = (float)(2.0 / B * ((double)out[i] - ybar));
+        for (int i = threadIdx.x; i < n; i += DPP_THREADS) dout[i] = (float)(2.0 / B * (((double)out[i] - pivot) - ybar));
     if (err == nullptr) return;
     // the monitor of poseregnettrainer.py:115 under the same broadcast: mean (and max) over all pairs of |o_i - y_j|
     __syncthreads();
