@@ -35,6 +35,16 @@ passes and K workspaces of 40 bytes per pixel): do_hand_size with hands > 1 rais
 
 With sensor=dict(dtype=, median=, mirror=) the frames handed to run() are RAW sensor frames: frame_ingest (csrc/ingest.hip) converts,
 mirrors and median-filters them into the float32 frame buffer and writes the depth-range partials, in frame_range's place.
+
+BACKGROUND.  The nearest object of more than 200 px is a desk edge, a monitor or the user's torso wherever one is nearer than the hand.
+FrameDetector(background=dict(margin=, rel=0.0, min_seen=1)) cuts a learned per-pixel background from the frames first (hipdp/tracker.py,
+BACKGROUND; csrc/background.hip): frame_background keeps a depth only where it is not 0 and strictly below its cut, in place, and
+writes the depth-range partials of what it kept, so the slabs, the labelling, the seed window, the refinement and the hand size all
+work on the masked frame.  stage(with_range=True) opens with frame_background instead of frame_range -- behind a frame_ingest without
+partials where there is a sensor.  A tracker's detectors take views of the tracker's cut map (cut=); a detector of its own owns a model
+(self.bg) whose cut map is +inf, the neutral element, until something was learned.  Out of scope: updating the model while tracking,
+per-source options, a cut inside the ingest kernel, the host HandDetector API, morphological clean-up of the mask, mixed pixels at
+object edges, choosing margin / rel for a sensor.
 """
 import numpy as np
 
@@ -45,7 +55,7 @@ NUM_REFINE_ITER = 5                 # handdetector.py:610
 
 class FrameDetector(object):
     def __init__(self, rt, H, W, fx, fy, B=1, frames=None, partial=None, com=None, cube=None, res=None, sensor=None, raw=None, hands=1,
-                 max_extent=None):
+                 max_extent=None, background=None, cut=None):
         """
         :param H, W:    frame size
         :param fx, fy:  what the reference hands to HandDetector
@@ -60,6 +70,9 @@ class FrameDetector(object):
                         an own result block then also holds the centres and the per-slot report (key, count, box), so that the host
                         reads ONE block; res, when given, has 14 * B * K words, com (B * K, 3).  Hand size is measured for one hand only
         :param max_extent: None / 0, or the largest metric width and height (mm) a component may have to be a hand
+        :param background: None, or dict(margin=, rel=0.0, min_seen=1): a learned background is cut from the frames first (BACKGROUND above)
+        :param cut:     with a background: the owner's cut map (B, H, W) (a tracker hands a view of its own); by default the map of an own
+                        model, self.bg (an ops.BackgroundModel: learn through ops.background_learn, then bg.refresh())
         """
         self.rt, self.B, self.H, self.W = rt, int(B), int(H), int(W)
         self.K = int(hands)
@@ -77,6 +90,14 @@ class FrameDetector(object):
         if self.sensor is not None:
             self.raw = raw if raw is not None else rt.alloc((self.B, self.H, self.W), self.sensor[0], zero=False)
         self.partial = partial if partial is not None else ops.frame_range_workspace(rt, self.B)
+        self.background = None if background is None else ops.background_spec(background)
+        self.bg = self.cut = None
+        if self.background is not None:
+            if cut is None:
+                self.bg = ops.BackgroundModel(rt, self.background, self.B, self.H, self.W)
+            self.cut = cut if cut is not None else self.bg.cut
+        elif cut is not None:
+            raise ValueError("a cut map needs the background options it was computed with")
         self.cube = cube if cube is not None else rt.alloc((self.B, 3), f32)
         self.ws = ops.ComponentWorkspace(rt, self.B, self.H, self.W, candidates=self.multi)
         self._plans = {}
@@ -108,6 +129,9 @@ class FrameDetector(object):
         if do_hand_size and self.K > 1:
             raise ValueError("hand size is measured for one hand per frame: do_hand_size needs hands=1")
         out = [ops.frame_range(rt, fr, B, H, W, self.partial)] if with_range else []
+        if with_range and self.cut is not None:     # the same launch(es) a tracker's plan opens with: [frame_ingest,] frame_background
+            from .tracker import frame_stage
+            out = frame_stage(rt, fr, self.raw, B, H, W, self.partial, self.sensor, self.cut)
         if self.multi:
             out += [ops.slab_keys(rt, fr, self.partial, ws),
                     ops.label_components(rt, ws),
@@ -150,10 +174,10 @@ class FrameDetector(object):
         key = bool(do_hand_size)
         if key not in self._plans:
             p = ops.Plan('detect')
-            if self.sensor is not None:             # raw -> frames and the partials, then the stage without its range pass
+            if self.sensor is not None and self.cut is None:     # raw -> frames and the partials, then the stage without its range pass
                 p.add(ops.frame_ingest(self.rt, self.raw, self.B, self.H, self.W, self.frames, self.partial, median=self.sensor[1],
                                        mirror=self.sensor[2]))
-            for op in self.stage(key, with_range=self.sensor is None):
+            for op in self.stage(key, with_range=self.sensor is None or self.cut is not None):
                 p.add(op)
             self._plans[key] = p
         return self._plans[key]

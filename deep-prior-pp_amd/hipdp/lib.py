@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(os.path.dirname(_HERE), 'lib', 'libdpp_hip.so')
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 ST_A, ST_B, ST_C, ST_BNX = 1, 2, 4, 8      # DPP_ST_*: which pointers of a call address bf16-stored activation tensors
 c_float_p = C.c_void_p      # device pointers travel as integers
 stream_t = C.c_void_p
@@ -207,6 +207,10 @@ SIGNATURES = {
     'dpp_source_record_bytes': (C.c_size_t, []),
     'dpp_frame_range_src': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, stream_t]),
     'dpp_frame_ingest_src': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, stream_t]),
+    'dpp_frame_background': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, stream_t]),
+    'dpp_frame_background_src': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, stream_t]),
+    'dpp_background_learn': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, stream_t]),
+    'dpp_background_learn_src': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, stream_t]),
     'dpp_crop_prepare_ranged_src': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                               C.c_void_p, C.c_void_p, stream_t]),
     'dpp_crop_warp_src': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, stream_t]),

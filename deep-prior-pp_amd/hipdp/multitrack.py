@@ -128,6 +128,25 @@ one stamps buffer per input set, uploaded with that set's frames.  Out of scope:
 stamps are taken as one clock), letting an IDLE track coast into the fusion, using the filtered derivative as the velocity, and per-source
 sensor options.  timing=None: allocation, uploads, plans, result block and keys are those of before.
 
+BACKGROUND (ABI v25; csrc/background.hip; this project's own as well, restated by tests/background_ref.py).  Everything above combines
+tracks that were already found; finding the hand still needed an empty scene: the detector starts from the nearest object of more than
+200 px, the depth range feeds its slabs and crop_warp keeps whatever lies inside the cube, so on a fixed camera a desk edge, a monitor
+or the user's torso is what acquire / acquire_source return.  With background=dict(margin=, rel=0.0, min_seen=1) (common to all sources,
+like `sensor`; margin in mm has no default) every source has a per-pixel model at its own frame size -- near (float32, the smallest
+non-zero depth seen while learning; 0: none) and seen (int32, the learning frames with a depth) -- and a cut map computed on the HOST
+once per model change, every operation rounded to float32: near - (margin + rel * near) where seen >= min_seen, near != 0 and the
+result is > 0, +inf elsewhere.  frame_background keeps a depth only where it is not 0 and strictly below its cut, IN PLACE in the
+frame buffer everything downstream reads, and writes the depth-range partials of what it kept: without a sensor in frame_range's place
+(the launch count does not change), with one behind a frame_ingest that writes no partials (one launch more).  Both input sets of
+process_sequence are masked against the one cut map; masking is idempotent, so the stale frame of a source that sits a tick out is
+masked again to the same bits.  The per-track and per-source detectors take views of the cut map, so acquire, acquire_source, hand
+size and joint_visibility see the masked frame.  learn_background(frames) (None where a source sits out) is a plan of its own: upload,
+[frame_ingest], background_learn, then the cut maps of the sources that took part.  background_model(c) / set_background_model(c,
+model) / clear_background([c]) let a rig learn once and reload.  A model that was never learned is the neutral element.  Out of scope:
+updating the model while tracking, per-source options, a cut inside the ingest kernel, the host HandDetector API, morphological
+clean-up of the mask, mixed pixels at object edges, choosing margin / rel for a sensor.  background=None: allocation, uploads, plans,
+result block and keys are those of before.
+
 acquire_source(c, frame) finds ALL hands of a source in one detector plan and starts the source's tracks from them; the detectors
 are built per source, at that source's size and focal lengths, on views of its frame slice.
 
@@ -142,12 +161,13 @@ import numpy as np
 
 from . import ops
 from .augmenter import camera_tuple
-from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, refine_stage, smooth_fields, timing_fields, track_fields, valid_centre, visibility_fields
+from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, frame_stage, refine_stage, smooth_fields, timing_fields, track_fields, valid_centre, visibility_fields
 
 
 class MultiTracker(object):
     def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, tracks, sources=None, invX=False, invY=False, fx=None, fy=None,
-                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None, visibility=None, timing=None):
+                 sensor=None, extrinsics=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None, visibility=None, timing=None,
+                 background=None):
         """
         :param importer:   the dataset importer (the camera) of all sources, or a sequence of C importers, one per source
         :param poseNet, comrefNet: as for HandTracker, but built for a batch of T, the number of tracks: row t is track t
@@ -174,6 +194,8 @@ class MultiTracker(object):
         :param timing:     None, or dict(max_gap=, max_lead=) (seconds; neither has a default): every tick carries one stamp per source and
                            an instant `now`; every track is brought to `now` before tracks are combined, and `smooth` filters over the
                            stamps -- its `rate` is still validated but goes unread (TIMING above)
+        :param background: None, or dict(margin=, rel=0.0, min_seen=1), for ALL sources: a learned per-pixel background is removed from
+                           every frame as the plan's first step (BACKGROUND above); margin (mm) has no default
         """
         self.rt = rt
         tracks = [(int(s), bool(r)) for s, r in tracks]
@@ -239,6 +261,10 @@ class MultiTracker(object):
         self._inputs2 = self._frames2 = self._gate2 = None                         # process_sequence's second set, made when first used
         self.partial = ops.frame_range_workspace(rt, C)
         self._pstride = self.partial.size // C
+        self.background = None if background is None else ops.background_spec(background)
+        # near, seen, cut and take in the frames' own layout (with a table: the ragged one)
+        self.bg = None if background is None else ops.BackgroundModel(rt, self.background, C, self.H, self.W, table=self.table)
+        self._learn = None
         self.rec = rt.alloc(T * rt.lib.dpp_crop_record_bytes(), np.uint8)
         self.cube = rt.alloc((T, 3), f32)
         ix = rt.alloc((3, T), i32)                                                 # src, gate (all zero: nobody has started), tflags
@@ -380,8 +406,60 @@ class MultiTracker(object):
                 self.rt, H, W, self.fxs[c], self.fys[c], 1, frames=self._slice(self.frames, c),
                 partial=self.partial.view(c * self._pstride, (self._pstride,)), com=self.com.view(3 * t, (1, 3)),
                 cube=self.cube.view(3 * t, (1, 3)), res=self.block.view('det'), sensor=self.sensor,
-                raw=None if self.sensor is None else self._slice(self.raw, c, raw=True))
+                raw=None if self.sensor is None else self._slice(self.raw, c, raw=True), **self._cut(c))
         return self._detectors[t]
+
+    def _cut(self, c):
+        """What a detector of source c is handed beside its frame: the background options and a view of the source's cut map."""
+        return {} if self.bg is None else dict(background=self.background, cut=self.bg.view(self.bg.cut, c))
+
+    # ---- the learned background ---------------------------------------------------------------------------------------------
+    def _model(self):
+        if self.bg is None:
+            raise RuntimeError("the tracker was built without background=")
+        return self.bg
+
+    def learn_background(self, frames):
+        """One frame per source of the scene WITHOUT hands into the sources' models, None where a source sits out (raw frames with a
+        sensor: what is learned is frame_ingest's output): one upload per frame (and of `take`, when it differs from the last call's),
+        a plan of its own ([frame_ingest], background_learn), then the cut maps of the sources that took part -- a download of the
+        model, the map on the host, an upload.  Not on the per-tick path."""
+        bg = self._model()
+        if len(frames) != self.C:
+            raise ValueError("%d frames for %d sources" % (len(frames), self.C))
+        fresh = [None if f is None else self._frame(f, c) for c, f in enumerate(frames)]
+        if self._learn is None:
+            rt, p = self.rt, ops.Plan('learn_background')
+            if self.sensor is not None:
+                p.add(ops.frame_ingest(rt, self.raw, self.C, self.H, self.W, self.frames, None, median=self.sensor[1], mirror=self.sensor[2],
+                                       table=self.table))
+            p.add(ops.background_learn(rt, self.frames, bg.take, self.C, self.H, self.W, bg.near, bg.seen, table=self.table))
+            self._learn = p
+        for c, f in enumerate(fresh):
+            if f is not None:
+                self._input(c).set(f)
+        bg.set_take([int(f is not None) for f in fresh])
+        self._learn.run(self.rt)
+        self.rt.synchronize()
+        for c, f in enumerate(fresh):
+            if f is not None:
+                bg.refresh(c)
+
+    def background_model(self, c=None):
+        """dict(near, seen, cut) of source c ((H, W) arrays of its size), or the list of all sources' without c."""
+        self.rt.synchronize()
+        bg = self._model()
+        return [bg.get(s) for s in range(self.C)] if c is None else bg.get(c)
+
+    def set_background_model(self, c, model):
+        """Load dict(near=, seen=) as background_model(c) returned it into source c (the cut map is computed with THIS tracker's options)."""
+        self.rt.synchronize()
+        self._model().set(c, model['near'], model['seen'])
+
+    def clear_background(self, c=None):
+        """Forget the model of source c (or of all): until something is learned again the source is that of a tracker without the option."""
+        self.rt.synchronize()
+        self._model().clear(c)
 
     def acquire(self, t, frame, do_hand_size=False):
         """Find a hand in `frame` of track t's source and start track t (again) from it, as HandTracker.acquire does: one upload, the
@@ -421,7 +499,8 @@ class MultiTracker(object):
             self._detectors[key] = FrameDetector(
                 self.rt, H, W, self.fxs[c], self.fys[c], 1, frames=self._slice(self.frames, c),
                 partial=self.partial.view(c * self._pstride, (self._pstride,)), cube=self.cube.view(3 * ts[0], (1, 3)), sensor=self.sensor,
-                raw=None if self.sensor is None else self._slice(self.raw, c, raw=True), hands=len(ts), max_extent=max_extent)
+                raw=None if self.sensor is None else self._slice(self.raw, c, raw=True), hands=len(ts), max_extent=max_extent,
+                **self._cut(c))
         return self._detectors[key], ts
 
     def acquire_source(self, c, frame, max_extent=None, order='near'):
@@ -535,10 +614,9 @@ class MultiTracker(object):
             fr = self._inputs2 if slot and self.sensor is None else self.frames
             raw = self._inputs2 if slot else self.raw
             p = ops.Plan('multitrack')
-            if self.sensor is None:
-                p.add(ops.frame_range(rt, fr, C, H, W, self.partial, table=self.table))
-            else:
-                p.add(ops.frame_ingest(rt, raw, C, H, W, fr, self.partial, median=self.sensor[1], mirror=self.sensor[2], table=self.table))
+            # frame_range; with a sensor frame_ingest in its place; with a background frame_background, which then writes the partials
+            for op in frame_stage(rt, fr, raw, C, H, W, self.partial, self.sensor, None if self.bg is None else self.bg.cut, table=self.table):
+                p.add(op)
             # the T centres are read (prepare, track_refine) and then rewritten by one lane per track of track_refine: in place
             for op, side in refine_stage(rt, fr, H, W, self.partial, self.rec, self.com, self.cube, self.ceng, self.cam, self.fx, self.fy,
                                          self.ds, self.com, self.com3d, self.rec, self.status, self.M, tracks=tracks):

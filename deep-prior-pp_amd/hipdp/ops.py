@@ -812,6 +812,137 @@ def frame_ingest(rt, raw, B, H, W, frames, partial, median=False, mirror=False, 
     return Launch(fn, args, keep, name, dict(kernel='frame_ingest', flops=(22.0 if median else 2.0) * npx, bytes=(raw.dtype.itemsize + 4.0) * npx))
 
 
+# ---- a learned static background removed from the frame (include/dpp_hip.h, ABI v25; csrc/background.hip) -------------------------------
+def background_spec(background):
+    """dict(margin=, rel=0.0, min_seen=1) checked on the host -> (margin, rel, min_seen); such a tuple (a tracker hands its own to its
+    detectors) passes through.  margin (mm, finite, >= 0) is required: none has been chosen for a sensor.  0 <= rel < 1; min_seen an
+    int >= 1."""
+    if isinstance(background, tuple):
+        return background
+    known = ('margin', 'rel', 'min_seen')
+    if not isinstance(background, dict) or set(background) - set(known):
+        raise ValueError("background takes margin, rel and min_seen, not %r" %
+                         (sorted(set(background) - set(known)) if isinstance(background, dict) else background,))
+    s = dict(rel=0.0, min_seen=1)
+    s.update(background)
+    if 'margin' not in s:
+        raise ValueError("background needs margin (mm): no default has been chosen for a sensor")
+    try:
+        margin, rel, seen = float(s['margin']), float(s['rel']), int(s['min_seen'])
+    except (TypeError, ValueError):
+        raise ValueError("background takes numbers: %r" % (background,))
+    if not (np.isfinite(margin) and margin >= 0.):
+        raise ValueError("margin (mm) is finite and >= 0: %r" % (s['margin'],))
+    if not 0. <= rel < 1.:
+        raise ValueError("rel is a share of the depth, 0 <= rel < 1: %r" % (s['rel'],))
+    if seen != s['min_seen'] or not 1 <= seen < 2 ** 31:
+        raise ValueError("min_seen is a number of frames >= 1: %r" % (s['min_seen'],))
+    return margin, rel, seen
+
+
+def background_cut(near, seen, spec):
+    """The cut map of a model on the host, every operation rounded to float32: near - (margin + rel * near) where seen >= min_seen,
+    near != 0 and the result is > 0; +inf elsewhere (no background is known there: every depth is foreground)."""
+    margin, rel, min_seen = spec
+    near = np.asarray(near, np.float32)
+    cut = near - (np.float32(margin) + np.float32(rel) * near)
+    known = (np.asarray(seen) >= min_seen) & (near != 0) & (cut > 0)
+    return np.where(known, cut, np.float32(np.inf)).astype(np.float32)
+
+
+def frame_background(rt, frames, cut, B, H, W, partial, name='frame_background', table=None):
+    """dpp_frame_background: frames = (f != 0 and f < cut) ? f : 0 IN PLACE, and frame_range's partials of the result (partial may be
+    None) -- in a plan it stands where frame_range stood.  table (a SourceTable): dpp_frame_background_src on the ragged buffers of the
+    table's sources (cut has the frames' layout); B, H, W are not read."""
+    if table is None:
+        fn, args, keep, npx = rt.lib.dpp_frame_background, (frames.ptr, cut.ptr, B, H, W, _p(partial)), (frames, cut, partial), float(B) * H * W
+    else:
+        fn, args, npx = rt.lib.dpp_frame_background_src, (frames.ptr, cut.ptr, table.dev.ptr, table.C, _p(partial)), table.npx
+        keep = (frames, cut, table.dev, partial)
+    # per pixel: the frame read and written, the cut read; two compares and a select, min / max
+    return Launch(fn, args, keep, name, dict(kernel='frame_background', flops=4.0 * npx, bytes=3 * 4.0 * npx))
+
+
+def background_learn(rt, frames, take, B, H, W, near, seen, name='background_learn', table=None):
+    """dpp_background_learn: one float32 frame per source into the model (near: the smallest non-zero depth; seen: the frames with a
+    depth); take (int32 per source): 0 leaves that source's model untouched.  table: dpp_background_learn_src, as frame_background."""
+    if table is None:
+        fn, args, npx = rt.lib.dpp_background_learn, (frames.ptr, take.ptr, B, H, W, near.ptr, seen.ptr), float(B) * H * W
+        keep = (frames, take, near, seen)
+    else:
+        fn, args, npx = rt.lib.dpp_background_learn_src, (frames.ptr, take.ptr, table.dev.ptr, table.C, near.ptr, seen.ptr), table.npx
+        keep = (frames, take, table.dev, near, seen)
+    return Launch(fn, args, keep, name, dict(kernel='background_learn', flops=3.0 * npx, bytes=5 * 4.0 * npx))
+
+
+class BackgroundModel(object):
+    """The background model of C frame sources and what is derived from it, in the layout of the frames they are applied to ((C, H, W),
+    or with a SourceTable the ragged one): `near` (float32), `seen` (int32), `cut` (float32, what frame_background reads; +inf until
+    refresh() after something was learned or set) and `take` (int32 [C], background_learn's per-source switch).  The model lives on
+    the device; refresh() downloads it, computes the cut map on the host (background_cut) and uploads it: once per model change, never
+    per tick."""
+
+    def __init__(self, rt, spec, C, H=None, W=None, table=None):
+        self.rt, self.spec, self.C, self.table = rt, background_spec(spec), int(C), table
+        if table is None:
+            self.sizes, self.offs, n = [(int(H), int(W))] * self.C, [c * int(H) * int(W) for c in range(self.C)], self.C * int(H) * int(W)
+        else:
+            self.sizes, self.offs, n = [table.size(c) for c in range(self.C)], [int(o) for o in table.host['frame_off']], table.frame_elems
+        self.near, self.seen = rt.alloc((n,), np.float32), rt.alloc((n,), np.int32)
+        self.cut = rt.upload(np.full(n, np.inf, np.float32))
+        self.take_host = np.ones(self.C, np.int32)
+        self.take = rt.upload(self.take_host)
+
+    def view(self, buf, c):
+        """Source c's (1, H, W) part of one of the model's buffers."""
+        H, W = self.sizes[c]
+        return buf.view(self.offs[c], (1, H, W))
+
+    def set_take(self, take):
+        take = np.asarray(take, np.int32).reshape(self.C)
+        if not np.array_equal(take, self.take_host):
+            self.take.set(take)
+            self.take_host = take.copy()
+
+    def _sources(self, c):
+        if c is None:
+            return list(range(self.C))
+        if not 0 <= int(c) < self.C:
+            raise IndexError("source %r of %d" % (c, self.C))
+        return [int(c)]
+
+    def refresh(self, c=None):
+        """Recompute and upload the cut map (of source c alone, or of every source)."""
+        for s in self._sources(c):
+            cut = background_cut(self.view(self.near, s).get(), self.view(self.seen, s).get(), self.spec)
+            self.view(self.cut, s).set(cut)
+
+    def clear(self, c=None):
+        """Forget what was learned (for source c, or for all): the cut map is +inf again, the tracker that of one without the option."""
+        for s in self._sources(c):
+            H, W = self.sizes[s]
+            self.view(self.near, s).set(np.zeros((H, W), np.float32))
+            self.view(self.seen, s).set(np.zeros((H, W), np.int32))
+            self.view(self.cut, s).set(np.full((H, W), np.inf, np.float32))
+
+    def get(self, c):
+        """dict(near, seen, cut) of source c, (H, W) each, downloaded."""
+        (s,) = self._sources(int(c))
+        return dict(near=self.view(self.near, s).get()[0], seen=self.view(self.seen, s).get()[0], cut=self.view(self.cut, s).get()[0])
+
+    def set(self, c, near, seen):
+        """Load a model learned earlier into source c and refresh its cut map."""
+        (s,) = self._sources(int(c))
+        near, seen = np.asarray(near), np.asarray(seen)
+        if near.shape != self.sizes[s] or seen.shape != self.sizes[s]:
+            raise ValueError("background model shapes %s / %s, source %d delivers %s" % (near.shape, seen.shape, s, self.sizes[s]))
+        if not np.issubdtype(seen.dtype, np.integer) or (seen < 0).any() or not np.all(np.isfinite(near)) or (near < 0).any():
+            raise ValueError("near holds finite depths >= 0 (0: none seen), seen counts of frames")
+        self.view(self.near, s).set(near.astype(np.float32))
+        self.view(self.seen, s).set(seen.astype(np.int32))
+        self.refresh(s)
+
+
 def crop_prepare_ranged(rt, partial, B, com, cube, fx, fy, dsz, records, M_out=None, stretch=False, name='crop_prepare_ranged', tracks=None):
     """dpp_crop_prepare_ranged: crop_prepare's records from frame_range's partials (no pass over the frame)."""
     tail = (dsz, int(bool(stretch)), records.ptr, _p(M_out))

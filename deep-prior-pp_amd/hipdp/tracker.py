@@ -34,6 +34,21 @@ delivers them: the host uploads the RAW frame (half the bytes for uint16) and th
 mirror, 3x3 median with a replicated border, conversion to float32 -- what the reference's CreativeCameraDevice.getDepth does on the
 host, src/util/cameradevice.py:189-200 of the reference) IN PLACE OF frame_range: it writes the float32 frame buffer everything
 downstream reads and the same depth-range partials, so the launch count does not change.  sensor=None is the plan above, untouched.
+
+BACKGROUND.  On a fixed camera a desk edge, a monitor or the user's torso is nearer than the hand: the detector starts from it, the
+depth range feeds its slabs, the crop keeps what lies inside the cube.  HandTracker(..., background=dict(margin=, rel=0.0,
+min_seen=1)) keeps a per-pixel model of the empty scene on the device -- near (the smallest non-zero depth seen while learning) and
+seen (the learning frames with a depth) -- and from it a cut map, computed on the host once per model change: near - (margin + rel *
+near) in float32 where seen >= min_seen, near != 0 and the result is > 0, +inf elsewhere.  frame_background (csrc/background.hip)
+keeps a depth only where it is not 0 and strictly below its cut, IN PLACE in the frame buffer everything downstream reads, and writes
+the depth-range partials of what it kept: without a sensor it stands in frame_range's place (the launch count does not change), with
+one frame_ingest runs without partials and frame_background follows it (one launch more).  Both frame slots are masked against the
+one cut map; the detector (acquire, hand_size) and joint_visibility see the masked frame.  learn_background(frame) is a plan of its
+own (upload, [frame_ingest], background_learn, then the cut map); background_model() / set_background_model() / clear_background()
+let a rig learn once and reload.  A model that was never learned is the neutral element: every output is that of a tracker without
+the option.  background=None is the plan above, untouched.  Out of scope: updating the model while tracking, per-source options, a
+cut inside the ingest kernel, the host HandDetector API, morphological clean-up of the mask, mixed pixels at object edges, choosing
+margin / rel for a sensor.
 """
 import numpy as np
 
@@ -86,6 +101,20 @@ def refine_stage(rt, frame, H, W, partial, rec, com_in, cube, ceng, cam, fx, fy,
     out.extend(ceng.fwd.ops)
     out.append((ops.track_refine(rt, frame, rec, B, H, W, com_in, cube, ceng.out.buf, cam, fx, fy, dsz_final, com_out, com3d, rec_out, status,
                                  M_out=M, tracks=tracks), False))
+    return out
+
+
+def frame_stage(rt, fr, raw, B, H, W, partial, sensor, cut=None, table=None):
+    """The launches that open a plan on B frames (with a table: on its sources): they leave the float32 frames in `fr` and their
+    depth-range partials in `partial`.  frame_range; with a sensor (ops.sensor_spec's tuple) frame_ingest from `raw` in its place;
+    with a background cut map frame_background in frame_range's place, behind a frame_ingest that then writes no partials."""
+    out = []
+    if sensor is not None:
+        out.append(ops.frame_ingest(rt, raw, B, H, W, fr, partial if cut is None else None, median=sensor[1], mirror=sensor[2], table=table))
+    elif cut is None:
+        out.append(ops.frame_range(rt, fr, B, H, W, partial, table=table))
+    if cut is not None:
+        out.append(ops.frame_background(rt, fr, cut, B, H, W, partial, table=table))
     return out
 
 
@@ -167,7 +196,7 @@ def timing_fields(T, J):
 
 class HandTracker(object):
     def __init__(self, rt, importer, poseNet, comrefNet, H, W, cube, hand_right=False, invX=False, invY=False, fx=None, fy=None, sensor=None,
-                 smooth=None, visibility=None, timing=False):
+                 smooth=None, visibility=None, timing=False, background=None):
         """
         :param importer:   the dataset importer (camera; NYU / MSRA flip the y axis)
         :param poseNet:    the pose regressor, built for a batch of one; its output is J x 3 normalised joints
@@ -186,6 +215,9 @@ class HandTracker(object):
         :param timing:     True (needs `smooth`): every frame carries its stamp (s) and the filter runs over real elapsed time
                            (dpp_pose_smooth_t; smooth's `rate` is still validated but goes unread).  One camera has nothing to align:
                            there is no align launch (hipdp/multitrack.py, TIMING)
+        :param background: None, or dict(margin=, rel=0.0, min_seen=1): a learned per-pixel background is removed from every frame as
+                           the plan's first step (BACKGROUND above); margin (mm) has no default.  Nothing is removed until
+                           learn_background() / set_background_model()
         """
         self.rt, self.H, self.W = rt, int(H), int(W)
         self.importer = importer
@@ -204,6 +236,9 @@ class HandTracker(object):
         self.raw = None if sensor is None else [rt.alloc((1, self.H, self.W), self.sensor[0], zero=False) for _ in range(2)]
         self.inputs = self.frames if sensor is None else self.raw
         self.partial = ops.frame_range_workspace(rt, 1)
+        self.background = None if background is None else ops.background_spec(background)
+        self.bg = None if background is None else ops.BackgroundModel(rt, self.background, 1, self.H, self.W)   # near, seen, cut, take
+        self._learn = None
         self.rec = rt.alloc(rt.lib.dpp_crop_record_bytes(), np.uint8)
         self.cube = rt.alloc((1, 3), f32)
         # everything the host reads per frame is ONE block: pose (mm), pose in image coordinates, centre (= the state), com3D, M, status
@@ -255,8 +290,48 @@ class HandTracker(object):
             from .detect import FrameDetector
             self._detector = FrameDetector(self.rt, self.H, self.W, self.fx, self.fy, 1, frames=self.frames[0], partial=self.partial,
                                            com=self.com, cube=self.cube, res=self.block.view('det'), sensor=self.sensor,
-                                           raw=None if self.sensor is None else self.raw[0])
+                                           raw=None if self.sensor is None else self.raw[0],
+                                           **({} if self.bg is None else dict(background=self.background, cut=self.bg.view(self.bg.cut, 0))))
         return self._detector
+
+    # ---- the learned background ---------------------------------------------------------------------------------------------
+    def _model(self):
+        if self.bg is None:
+            raise RuntimeError("the tracker was built without background=")
+        return self.bg
+
+    def learn_background(self, frame):
+        """One frame of the scene WITHOUT the hand into the model (a raw one with a sensor: what is learned is frame_ingest's output):
+        one upload, a plan of its own ([frame_ingest], background_learn), then the cut map -- a download of the model, the map on the
+        host, one upload.  Not on the per-frame path."""
+        bg = self._model()
+        frame = self._frame(frame)
+        if self._learn is None:
+            rt, p = self.rt, ops.Plan('learn_background')
+            if self.sensor is not None:
+                p.add(ops.frame_ingest(rt, self.raw[0], 1, self.H, self.W, self.frames[0], None, median=self.sensor[1], mirror=self.sensor[2]))
+            p.add(ops.background_learn(rt, self.frames[0], bg.take, 1, self.H, self.W, bg.near, bg.seen))
+            self._learn = p
+        self.inputs[0].set(frame)
+        self._slot = 0
+        self._learn.run(self.rt)
+        self.rt.synchronize()
+        bg.refresh()
+
+    def background_model(self):
+        """dict(near, seen, cut), (H, W) arrays: what set_background_model() of another tracker takes."""
+        self.rt.synchronize()
+        return self._model().get(0)
+
+    def set_background_model(self, model):
+        """Load dict(near=, seen=) as background_model() returned it (the cut map is computed from them with THIS tracker's options)."""
+        self.rt.synchronize()
+        self._model().set(0, model['near'], model['seen'])
+
+    def clear_background(self):
+        """Forget the model: the tracker is that of one without the option until something is learned again."""
+        self.rt.synchronize()
+        self._model().clear()
 
     def acquire(self, frame, do_hand_size=False):
         """Find the hand in `frame` (a raw one with a sensor: frame_ingest then opens the detector plan) and start (again) from it: one
@@ -311,10 +386,10 @@ class HandTracker(object):
         if key not in self._plans:
             rt, H, W, fr = self.rt, self.H, self.W, self.frames[slot]
             p = ops.Plan('track')
-            if self.sensor is None:
-                p.add(ops.frame_range(rt, fr, 1, H, W, self.partial))
-            else:                                   # raw -> fr and the same partials: in frame_range's place, not in front of it
-                p.add(ops.frame_ingest(rt, self.raw[slot], 1, H, W, fr, self.partial, median=self.sensor[1], mirror=self.sensor[2]))
+            # frame_range; with a sensor raw -> fr and the same partials IN ITS PLACE; with a background the cut, which writes them
+            for op in frame_stage(rt, fr, None if self.sensor is None else self.raw[slot], 1, H, W, self.partial, self.sensor,
+                                  None if self.bg is None else self.bg.cut):
+                p.add(op)
             # the state buffer is read (prepare, track_refine) and then rewritten by ONE lane of track_refine: in place
             for op, side in refine_stage(rt, fr, H, W, self.partial, self.rec, self.com, self.cube, self.ceng, self.cam, self.fx, self.fy,
                                          self.ds, self.com, self.com3d, self.rec, self.status, self.M):

@@ -28,6 +28,11 @@ to float32 of the reference's CreativeCameraDevice.getDepth (cameradevice.py:189
 (hipdp.tracker.HandTracker(sensor=...)), and the per-call paths filter through util.cameradevice.filter_depth first, so that both
 routes see the same frame.
 
+BACKGROUND: with background=dict(margin=[, rel=, min_seen=]) learnBackground(device, frames=N) learns a per-pixel model of the scene
+without the hand (hipdp/tracker.py, BACKGROUND), and the fused path removes it from every frame on the device before the detector of
+seed_detect, the tracker and calibrateHandsize look at it: on a fixed camera the nearest object is then the hand, not the desk.  The
+per-call API (detect) runs the host HandDetector and does not see the model.
+
 A LOST track (the tracked centre's depth is close to 0: the reference would crop the middle of the frame through comToBounds'
 "CoM ill-defined" branch, which is not built) gives a zero crop, eye(3) and a zero com3D -- the answer of :326-327 -- and clears
 the last centre, so that the next frame needs a seed again.
@@ -98,7 +103,7 @@ class RealtimeHandposePipeline(object):
     DETECTOR_COM = 0
 
     def __init__(self, poseNet, config, di, verbose=False, comrefNet=None, init_com=None, seed_com=False, seed_detect=False, sensor=None,
-                 smooth=None, visibility=None, timing=False):
+                 smooth=None, visibility=None, timing=False, background=None):
         """
         :param poseNet:   network for pose estimation (a built net, or PoseRegNetParams / ResNetParams, with loadFile or not)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=])
@@ -118,6 +123,9 @@ class RealtimeHandposePipeline(object):
                           and processVideo leaves the classes of the frames it returns in `vis_classes`
         :param timing:    True (needs smooth): HandTracker's -- the filter runs over the frames' stamps: processFrame takes stamp=
                           (seconds) and processVideo reads device.getTimestamp() behind every frame (a device that returns None raises)
+        :param background: None, or HandTracker's dict(margin=[, rel=, min_seen=]): a per-pixel background learned by learnBackground(device)
+                          is removed from every frame on the device before the fused path (processFrame / processVideo /
+                          calibrateHandsize) looks at it; the per-call API (detect) works on the host and does not see it
         """
         self.importer = di
         self.poseNet = poseNet
@@ -148,6 +156,7 @@ class RealtimeHandposePipeline(object):
         self.timing = bool(timing)
         if self.timing and smooth is None:
             raise ValueError("timing needs smooth: with one camera the stamps are read by the filter alone")
+        self.background = None if background is None else dict(background)
 
     def initNets(self):
         """Build the nets from their parameters (loading loadFile where set) and compile their forward plans (:118-141)."""
@@ -289,7 +298,7 @@ class RealtimeHandposePipeline(object):
         if t is None or (t.H, t.W) != (H, W) or (t.fx, t.fy) != (abs(float(cfg['fx'])), abs(float(cfg['fy']))):
             t = self._tracker = HandTracker(default_runtime(), self.importer, self.poseNet, self.comrefNet, H, W, cfg['cube'],
                                             fx=cfg['fx'], fy=cfg['fy'], sensor=self.sensor, smooth=self.smooth,
-                                            visibility=self.visibility, timing=self.timing)
+                                            visibility=self.visibility, timing=self.timing, background=self.background)
         if tuple(numpy.float32(cfg['cube'])) != tuple(t.cube_host):
             t.set_cube(cfg['cube'])
         t.set_hand(self.hand.value == self.HAND_RIGHT)
@@ -376,6 +385,31 @@ class RealtimeHandposePipeline(object):
         self.poses_f = None if self.smooth is None else numpy.asarray(poses_f, numpy.float32).reshape(-1, J, 3)
         self.vis_classes = None if self.visibility is None else numpy.asarray(vis_classes, numpy.int32).reshape(-1, J)
         return numpy.asarray(poses, numpy.float32).reshape(-1, J, 3)
+
+    def learnBackground(self, device, frames=None):
+        """Headless, like calibrateHandsize: `frames` (default numinitframes) frames of `device`, showing the scene WITHOUT the hand,
+        into the tracker's background model (raw frames with a sensor).  Raises RuntimeError if the device runs out of frames first.
+        Returns the model, dict(near, seen, cut); tracker(H, W).set_background_model() of a later run takes it.  (A tracker for another
+        frame size or other fx / fy is a new tracker: it starts without a model.)"""
+        if self.background is None:
+            raise RuntimeError("the pipeline was built without background=")
+        n = self.numinitframes if frames is None else int(frames)
+        self.initNets()
+        device.start()
+        t = None
+        for i in range(n):
+            try:
+                ret, frame = device.getDepth()
+            except IndexError:
+                ret = False
+            if ret is False:
+                device.stop()
+                raise RuntimeError("the device ran out of frames after %d of %d" % (i, n))
+            frame = numpy.asarray(frame, numpy.float32) if self.sensor is None else numpy.asarray(frame)
+            t = self.tracker(*frame.shape)
+            t.learn_background(frame)
+        device.stop()
+        return None if t is None else t.background_model()
 
     def calibrateHandsize(self, device, num_frames=None):
         """Headless hand-size calibration, the counterpart of STATE_INIT (:312-324): `num_frames` (default numinitframes) frames of
@@ -489,7 +523,8 @@ class MultiStreamPipeline(object):
     HAND_LEFT, HAND_RIGHT = RealtimeHandposePipeline.HAND_LEFT, RealtimeHandposePipeline.HAND_RIGHT
 
     def __init__(self, poseNet, config, di, devices, hands, comrefNet, init_com=None, seed_detect=False, sensor=None, verbose=False,
-                 max_extent=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None, visibility=None, timing=None):
+                 max_extent=None, groups=None, max_dev=None, handover=True, calibrate=None, smooth=None, visibility=None, timing=None,
+                 background=None):
         """
         :param poseNet, comrefNet: built nets or their parameters (as for RealtimeHandposePipeline), with batchSize == len(hands)
         :param config:    dict(fx=, fy=, cube=(x, y, z)[, invX=, invY=]); fx / fy: one value, or a list with one per device
@@ -505,7 +540,9 @@ class MultiStreamPipeline(object):
         :param smooth:    MultiTracker's: the One-Euro filter over the tracked and the fused poses
         :param visibility: MultiTracker's: every joint classified by the frame around it, the fusion weighted by that
         :param timing:    MultiTracker's: the devices' stamps carried through the plan, every track brought to the tick's instant
+        :param background: MultiTracker's, for all devices: the per-pixel background learnBackground(ticks) learned is removed from every frame
         """
+        self.background = None if background is None else dict(background)
         self.timing = None if timing is None else dict(timing)
         self.poses_t = None
         self.visibility = None if visibility is None else dict(visibility)
@@ -561,7 +598,7 @@ class MultiStreamPipeline(object):
                                          invX=cfg.get('invX') is True, invY=cfg.get('invY') is True, fx=cfg['fx'], fy=cfg['fy'],
                                          sensor=self.sensor, extrinsics=cfg.get('extrinsics'), groups=self.groups, max_dev=self.max_dev,
                                          handover=self.handover, calibrate=self.calibrate, smooth=self.smooth,
-                                         visibility=self.visibility, timing=self.timing)
+                                         visibility=self.visibility, timing=self.timing, background=self.background)
             self._tracker_key = shapes
             self._seeded = [False] * len(self.hands)
         return self._tracker
@@ -612,6 +649,26 @@ class MultiStreamPipeline(object):
         res = mt.process(frames) if stamps is None else mt.process(frames, stamps=stamps)
         self.fused = mt.fused
         return res
+
+    def learnBackground(self, ticks):
+        """`ticks` ticks of the devices, showing the scene WITHOUT hands, into the tracker's per-device background models (a device that
+        delivers no frame in a tick sits that tick out).  Raises RuntimeError if the devices run out of frames first.  Returns the models,
+        one dict(near, seen, cut) per device."""
+        if self.background is None:
+            raise RuntimeError("the pipeline was built without background=")
+        self.initNets()
+        for dev in self.devices:
+            dev.start()
+        for i in range(int(ticks)):
+            frames = self._read()
+            if frames is None:
+                for dev in self.devices:
+                    dev.stop()
+                raise RuntimeError("the devices ran out of frames after %d of %d ticks" % (i, int(ticks)))
+            self._tracker_for(frames).learn_background(list(frames))
+        for dev in self.devices:
+            dev.stop()
+        return None if self._tracker is None else self._tracker.background_model()
 
     def calibrateExtrinsics(self, ticks):
         """Find the extrinsics that config['extrinsics'] leaves open (None entries; calibrate=) from the hand the devices see: `ticks`

@@ -50,6 +50,13 @@ fused (max_gap = 4 / RATE, max_lead = (N + 1) / RATE: the example's choice, no d
 synchronous one (N = 0, no timing) and the lagging one without timing, give the mean distance of the fused joints from the synchronous
 run's with and without timing: sanity figures, not bars.
 
+--background MARGIN REL [--learn N] [--clutter X0:Y0:X1:Y1:DEPTH] removes a learned per-pixel background from every camera's frames
+as the plan's first step (MultiTracker background=, this project's own; the options and the devices of examples/realtime_background.py):
+the static rectangle is pasted into every frame of both cameras, the models are learned from the first N ticks (default 5) with the
+hand taken out around each sequence's annotated first centre, and with --seed detect / detect-all the detector then starts from the
+hand and not from the rectangle.  Prints the share of pixels at which each camera's model knows a background.  Not with --fuse or
+--half-res-second.
+
     python examples/realtime_multi.py --dataset icvl --data ../data/ICVL/ --seqs test_seq_1 test_seq_2
 """
 import argparse
@@ -68,6 +75,16 @@ from net.scalenet import ScaleNetParams  # noqa: E402
 from util.cameradevice import FileDevice  # noqa: E402
 from util.handpose_evaluation import HandposeEvaluation  # noqa: E402
 from util.realtimehandposepipeline import MultiStreamPipeline, smoothing_figures  # noqa: E402
+
+
+def background_example():
+    """examples/realtime_background.py as a module: its options' parser and its devices are used here as they are."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('realtime_background_example', os.path.join(ROOT, 'examples', 'realtime_background.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
 
 DATASETS = {'icvl': (ICVLImporter, ('test_seq_1', 'test_seq_2'), {'fx': 241.42, 'fy': 241.42, 'cube': (250, 250, 250)}),
             'nyu': (NYUImporter, ('test_1', 'test_2'), {'fx': 588., 'fy': 587., 'cube': (300, 300, 300)}),
@@ -279,6 +296,10 @@ def main(argv=None):
     ap.add_argument('--stamps', type=float, default=None, metavar='RATE',
                     help='with --fuse: the frames are stamped at RATE per second and the tracker aligns the tracks in time before it fuses them')
     ap.add_argument('--lag-second', type=int, default=0, metavar='N', help='with --fuse --stamps: camera 1 runs N frames behind camera 0')
+    ap.add_argument('--background', nargs=2, type=float, default=None, metavar=('MARGIN', 'REL'),
+                    help="remove a learned per-pixel background from every camera's frames: mm, and a share of the depth")
+    ap.add_argument('--learn', type=int, default=5, metavar='N', help='with --background: the ticks the models are learned from')
+    ap.add_argument('--clutter', default=None, metavar='X0:Y0:X1:Y1:DEPTH', help='with --background: a static rectangle pasted into every frame')
     ap.add_argument('--cache', default='./cache/')
     args = ap.parse_args(argv)
     Importer, seq_names, config = DATASETS[args.dataset]
@@ -307,6 +328,10 @@ def main(argv=None):
         raise SystemExit("--stamps RATE (> 0) stamps the two cameras of --fuse (not together with --occlude-second)")
     if args.lag_second and (args.stamps is None or args.lag_second < 0):
         raise SystemExit("--lag-second N (>= 0) needs --stamps")
+    if args.background is not None and (args.fuse or args.half_res_second):
+        raise SystemExit("--background is not combined with --fuse or --half-res-second")
+    if args.clutter is not None and args.background is None:
+        raise SystemExit("--clutter needs --background")
     if args.fuse:
         import contextlib
         import io
@@ -345,8 +370,24 @@ def main(argv=None):
             seeds = [c if c is None or d == 0 else numpy.asarray(c, numpy.float32) * numpy.float32([.5, .5, 1.]) for c, (d, _) in zip(init, hands)]
         else:
             dis, cfg, devices, seeds = di, config, [FileDevice(f, di) for f in files], init
+        bg_kw = {}
+        if args.background is not None:                                # the rooms are not empty: the rectangle in every frame of both cameras
+            bg = background_example()
+            clutter = bg.parse_clutter(args.clutter)
+            devices = [bg.ClutterDevice(f, di, clutter) for f in files]
+            bg_kw = dict(background=dict(margin=args.background[0], rel=args.background[1]))
         msp = MultiStreamPipeline(poseNetParams, cfg, dis, devices, hands, comrefNetParams, init_com=seeds, seed_detect=args.seed != 'gt',
-                                  max_extent=args.max_extent, **dict(smooth_arg(args), **visibility_arg(args)))
+                                  max_extent=args.max_extent, **dict(smooth_arg(args), **dict(visibility_arg(args), **bg_kw)))
+        if bg_kw:                                                      # learn the rooms without the hand, then play the sequences
+            n = min([max(1, args.learn)] + [len(f) for f in files])
+            cz = float(config['cube'][2])
+            msp.devices = [bg.ClutterDevice(f[:n], di, clutter, hand=(float(s.data[0].gtorig[di.crop_joint_idx][2]), cz))
+                           for f, s in zip(files, seqs)]
+            models = msp.learnBackground(n)
+            msp.devices = devices
+            msp.background_known = [float(numpy.isfinite(m['cut']).mean()) for m in models]
+            print("background learned from {} ticks: known at {} of the pixels".format(
+                n, ', '.join("{:.1%} (camera {})".format(k, c) for c, k in enumerate(msp.background_known))))
         return msp, msp.processVideos(max_frames=args.max_frames, overlapped=args.overlapped)
     msp, poses = run(args.half_res_second)
     t = numpy.asarray(msp.frame_times[1:] or msp.frame_times)         # the first tick records the plan

@@ -34,7 +34,7 @@ typedef void* dpp_stream_t; /* a hipStream_t */
 #define DPP_E_BADARG 10001
 #define DPP_E_UNSUPPORTED 10002
 
-#define DPP_ABI_VERSION 24
+#define DPP_ABI_VERSION 25
 int dpp_abi_version(void);
 
 /* bf16 STORAGE of activation tensors (ABI v9; BASELINE config 5 "bf16 MFMA, 256x256 input stress").  The [pixels][channels] tensors the
@@ -829,6 +829,32 @@ int dpp_pose_smooth_t(const float* pose3d, const int* status, const int* src, in
                       const void* sources, double fx, double fy, double ux, double uy, int flip_y, const double* stamps, int C,
                       double mincutoff, double beta, double dcutoff, int max_hold, int* since, double* tlast, double* xh, double* dxh,
                       float* pose_f, float* pose_img_f, int* sstat, float* fused_pose_f, int* gstat, dpp_stream_t stream);
+
+/* ---- a learned static background removed from the frame (ABI v25; csrc/background.hip) ------------------------------------------------------
+ * A fixed depth camera sees the same desk edge, monitor or torso in every frame; the detector starts from the nearest object and the
+ * crop keeps whatever lies inside the cube.  This project's own semantics (the reference has no counterpart), restated in NumPy by
+ * tests/background_ref.py:
+ *   model, per source and pixel, in the frames' layout:  near (float32; 0: nothing seen) the smallest non-zero depth of the learning
+ *     frames, seen (int32) the number of learning frames in which the pixel had a depth.
+ *   dpp_background_learn, one float32 frame f (with a sensor: dpp_frame_ingest's output), for every pixel with f != 0:
+ *     near = (near == 0 || f < near) ? f : near;  seen += 1.      take [B] int32 (device): take[b] == 0 leaves frame b's model untouched.
+ *   cut map (float32, the frames' layout), computed by the HOST once per model change, every operation rounded to float32:
+ *     cut = near - (margin + rel * near)   where seen >= min_seen, near != 0 and the result is > 0;   +inf elsewhere.
+ *   dpp_frame_background:  frames = (f != 0 && f < cut) ? f : 0, IN PLACE.  The comparison is strict: a depth exactly at cut is
+ *     background.  A pure selection: nothing rounds, applying twice gives the bits of applying once, an all-+inf cut map keeps every
+ *     frame (and its partials) as dpp_frame_range sees it.
+ * partial: NULL, or dpp_frame_range's workspace: EVERY band's (min, max) over the values stored is written, in dpp_frame_range's
+ * layout and element partition; a band without elements gets its identities (3.4e38f, -3.4e38f).  In a plan the launch stands in
+ * dpp_frame_range's place (behind dpp_frame_ingest with partial NULL where there is a sensor).
+ * *_src: the ragged layout of ABI v19 -- frames, cut, near and seen all start source c at element sources[c].frame_off; the padding
+ * words between frames are neither read nor written.
+ * DPP_E_BADARG (nothing launched, nothing written): a NULL pointer other than partial, B / C outside 1 .. 65535, H or W below 1, H * W
+ * above 2^31 - 1, cut (near, seen) overlapping frames (*_src: equal to it; the host keeps the ragged buffers apart). */
+int dpp_frame_background(float* frames, const float* cut, int B, int H, int W, float* partial, dpp_stream_t stream);
+int dpp_frame_background_src(float* frames, const float* cut, const void* sources, int C, float* partial, dpp_stream_t stream);
+int dpp_background_learn(const float* frames, const int* take, int B, int H, int W, float* near_, int* seen, dpp_stream_t stream);
+int dpp_background_learn_src(const float* frames, const int* take, const void* sources, int C, float* near_, int* seen,
+                             dpp_stream_t stream);
 
 /* ---- whole-frame hand detection by connected components (ABI v14) -------------------------------------------------------------
  * What HandDetector.detect / estimateHandsize (handdetector.py:569-632, :911-937) take from cv2.findContours, restated with

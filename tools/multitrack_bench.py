@@ -58,6 +58,13 @@ Further legs, same protocol (a child process per leg, the legs alternating, 2 pr
                                tick and the plan's device time are each within the larger spread of the parent's; (2) the plan with
                                `timing` costs at most ONE average launch of that plan plus the larger spread of the two device-time legs
                                more than the plan without.  No wall-clock claim: the tick gains one small upload and a larger download.
+  --background [--parent DIR]  the tick with background=dict(margin=50, rel=0.01) at T = C = 8 (a model that knows a background behind
+                               everything at every pixel, loaded through set_background_model: no timing depends on the values).
+                               Without a sensor dpp_frame_background stands in dpp_frame_range's place (three frames' worth of bytes
+                               for one); with sensor=dict(dtype='uint16', median=True) it follows dpp_frame_ingest (one launch more),
+                               measured against the same sensor without `background`.  Claim (two-sided, needs --parent): with
+                               background=None the tick and the plan's device time are each within the larger spread of the parent's.
+                               The two deltas are reported against the average launch of their plan, without a claim.
 --configs 1x1,8x8 overrides a leg's (T, C) list.
 
 As in tools/track_bench.py the refinement net's last layer is zeroed, so every track stays on its seed whatever the random weights
@@ -244,6 +251,35 @@ def child(args):
             out['smooth_device_ms_' + _key(T, C)] = device_time(mt.plan())
             out['smooth_launches_' + _key(T, C)] = len(mt.plan().launches())
             out['smooth_block_bytes_' + _key(T, C)] = 4 * int(mt.res.size)
+    elif args.leg == 'bg':
+        from hipdp.multitrack import MultiTracker
+        sensor = dict(dtype='uint16', median=True)
+        raw = np.rint(frames).astype(np.uint16)
+        far = dict(near=np.full((480, 640), 5000., np.float32), seen=np.ones((480, 640), np.int32))      # behind everything: nothing is cut
+        for T, C in configs:
+            pnet, snet = nets(T)
+            tracks = [(t % C, bool(t // C)) for t in range(T)]
+            for name, kw, src in (('bg', dict(background=dict(margin=50., rel=0.01)), frames), ('sensor', dict(sensor=sensor), raw),
+                                  ('sensor_bg', dict(sensor=sensor, background=dict(margin=50., rel=0.01)), raw)):
+                mt = MultiTracker(rt, di, pnet, snet, 480, 640, cube, tracks, **kw)
+                if 'background' in kw:
+                    for c in range(C):
+                        mt.set_background_model(c, far)
+                    assert np.isfinite(mt.background_model(0)['cut']).all()
+                for t in range(T):
+                    mt.reset(t, com0)
+
+                def tick(i):
+                    assert all(r['status'] == 0 for r in mt.process([src[(i + c) % nfr] for c in range(C)]))
+                for i in range(10):
+                    tick(i)
+                names = [l.name for l in mt.plan().launches()]
+                assert names[:2] == dict(bg=['frame_background', 'crop_prepare_ranged'], sensor=['frame_ingest', 'crop_prepare_ranged'],
+                                         sensor_bg=['frame_ingest', 'frame_background'])[name], names[:3]
+                out[name + '_ms_' + _key(T, C)] = timed(tick)
+                out[name + '_device_ms_' + _key(T, C)] = device_time(mt.plan())
+                out[name + '_launches_' + _key(T, C)] = len(names)
+                assert not mt.lost.any()
     elif args.leg == 'timing':
         from hipdp import ops
         from hipdp.multitrack import MultiTracker
@@ -399,7 +435,8 @@ def main():
     ap.add_argument('--smooth', action='store_true', help="the grouped tick with the One-Euro filter against this tree's and the parent's grouped tick (needs --parent)")
     ap.add_argument('--visibility', action='store_true', help="the grouped tick with joint visibility and the weighted fusion against this tree's and the parent's grouped tick (needs --parent)")
     ap.add_argument('--timing', action='store_true', help="the grouped tick with stamps and the alignment launch against this tree's and the parent's grouped tick (needs --parent)")
-    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse', 'fuse_tick', 'calib', 'smooth', 'vis', 'timing'], default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--background', action='store_true', help="the tick with a learned background, without and with a sensor, against this tree's and the parent's tick")
+    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse', 'fuse_tick', 'calib', 'smooth', 'vis', 'timing', 'bg'], default=None, help=argparse.SUPPRESS)
     ap.add_argument('--tree', default=ROOT, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.leg:
@@ -580,6 +617,39 @@ def main():
             print("  wall clock with timing over without: %+.4f ms (no claim: one upload of %d bytes more, the download grows by %d bytes)"
                   % (s[0] - f[0], 8 * (C + 1), res['timing_block_bytes_' + k] - res['fuse_block_bytes_' + k]))
             ok = fits and ok
+        return 0 if ok else 1
+    if args.background:
+        cfgs = args.configs or '8x8'
+        legs = ([('multi', ytree, 'parent_')] if args.parent else []) + [('multi', ROOT, ''), ('bg', ROOT, '')]
+        res = run_legs(legs, cfgs)
+        print("the tick with background= (dpp_frame_background in dpp_frame_range's place; with a uint16 sensor and the 3x3 median: behind "
+              "dpp_frame_ingest, one launch more) against the tick without it of this tree%s; " % (' and of the parent checkout' if args.parent else '') + head)
+        print("all times in ms per tick: median (spread = max - min over the repetitions)")
+        ok = True
+        for c in cfgs.split(','):
+            T, C = (int(v) for v in c.split('x'))
+            k = _key(T, C)
+            m, dm = _stat(res['multi_ms_' + k]), _stat(res['device_ms_' + k])
+            b, db = _stat(res['bg_ms_' + k]), _stat(res['bg_device_ms_' + k])
+            s_, ds = _stat(res['sensor_ms_' + k]), _stat(res['sensor_device_ms_' + k])
+            sb, dsb = _stat(res['sensor_bg_ms_' + k]), _stat(res['sensor_bg_device_ms_' + k])
+            print("T = C = %d, wall clock: background=None %.4f (%.4f), with background %.4f (%.4f); sensor %.4f (%.4f), sensor with background "
+                  "%.4f (%.4f)" % ((T,) + m + b + s_ + sb))
+            print("T = C = %d, plan device time: background=None %.4f (%.4f), with background %.4f (%.4f); sensor %.4f (%.4f), sensor with "
+                  "background %.4f (%.4f); launches %d / %d / %d / %d" % ((T,) + dm + db + ds + dsb + (
+                      res['launches_' + k], res['bg_launches_' + k], res['sensor_launches_' + k], res['sensor_bg_launches_' + k])))
+            if args.parent:
+                y, dy = _stat(res['parent_multi_ms_' + k]), _stat(res['parent_device_ms_' + k])
+                print("T = C = %d, the parent's tick %.4f (%.4f), its plan's device time %.4f (%.4f)" % ((T,) + y + dy))
+                ok = two_sided('T = C = %d, the tick with background=None' % T, m, y, 'this tree', 'the parent') and ok
+                ok = two_sided('T = C = %d, the plan device time with background=None' % T, dm, dy, 'this tree', 'the parent') and ok
+            per, per_s = db[0] / res['bg_launches_' + k] * 1e3, dsb[0] / res['sensor_bg_launches_' + k] * 1e3
+            mb = 4. * C * 480 * 640 / 1e6
+            print("  without a sensor, frame_background for frame_range (%.1f MB moved for %.1f MB): plan device time %+.2f us (spreads %.2f / %.2f "
+                  "us); the plan's average launch is %.2f us; wall clock %+.4f ms" % (3 * mb, mb, (db[0] - dm[0]) * 1e3, db[1] * 1e3, dm[1] * 1e3,
+                                                                                     per, b[0] - m[0]))
+            print("  with the sensor, one launch more: plan device time %+.2f us (spreads %.2f / %.2f us); the plan's average launch is %.2f us; "
+                  "wall clock %+.4f ms" % ((dsb[0] - ds[0]) * 1e3, dsb[1] * 1e3, ds[1] * 1e3, per_s, sb[0] - s_[0]))
         return 0 if ok else 1
     if args.calibrate:
         if not args.parent:
