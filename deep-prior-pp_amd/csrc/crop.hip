@@ -13,6 +13,7 @@
 // Compiled with -ffp-contract=off like augment.hip: the reference's NumPy/OpenCV arithmetic rounds after every operation, so no fused
 // multiply-add may be formed here (pixel coordinates at rounding boundaries would move).
 #include "geom.h"
+#include "crop_rec.h"
 
 namespace {
 
@@ -23,14 +24,7 @@ namespace {
 // the frame -> the detector's valid depth range, then lane 0 does the bounds / resize geometry in f64) and crop_warp (one
 // thread per output pixel: gather through the nearest-neighbour resize map, range clamp, z-threshold, background,
 // optional normalisation to [-1, 1]).
-struct CropRec {
-    int xstart, ystart, cw, ch;    // crop window in the frame (may leave the frame: zero padding)
-    int szw, szh, xs, ys;          // resized size and paste offset inside the dsz x dsz output
-    double ifx, ify;               // resizeNN: source index = min(floor(x * ifx), cw - 1)
-    float min_depth, max_depth;    // detector range: outside -> 0
-    float zstart, zend;
-    float far_v, norm_off, norm_div;
-};
+// (CropRec itself: crop_rec.h, shared with background.hip, which reads a track's window.)
 
 // The crop geometry of one frame from its depth range (mn, mx) and centre c: the detector's valid range, the window of the metric
 // cube, the resized size / paste offset and the crop transform M (9 floats, may be null).  Shared by crop_prepare_kernel (range from

@@ -2,8 +2,8 @@
 // and the workgroup reductions of the whole-frame kernels (crop.hip, components.hip, ingest.hip, background.hip).
 //
 // Everything here restates NumPy / OpenCV 2.4 arithmetic that rounds after every operation and is pinned bit for bit to the reference,
-// so every unit that uses that arithmetic is compiled with -ffp-contract=off (csrc/Makefile names them; ingest.hip and
-// background.hip take only the min / max reductions and the source table, which do not round).  One body per rule: a fix
+// so every unit that uses that arithmetic is compiled with -ffp-contract=off (csrc/Makefile names them; ingest.hip takes
+// only the min / max reductions and the source table, which do not round; background.hip is listed for its own cut-map arithmetic).  One body per rule: a fix
 // made here reaches every kernel that applies the rule.
 #pragma once
 #include "dpp_common.h"

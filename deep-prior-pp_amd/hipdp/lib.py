@@ -211,6 +211,11 @@ SIGNATURES = {
     'dpp_frame_background_src': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, stream_t]),
     'dpp_background_learn': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, stream_t]),
     'dpp_background_learn_src': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, stream_t]),
+    # frames, cut, near, seen, cand, run, take | B, H, W or sources, C | records, T, src | margin, rel, min_seen, persist, guard | partial
+    'dpp_frame_background_adapt': (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 2 + [C.c_int] * 3 +
+                                   [C.c_void_p, stream_t]),
+    'dpp_frame_background_adapt_src': (C.c_int, [C.c_void_p] * 7 + [C.c_void_p, C.c_int] + [C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 2 +
+                                       [C.c_int] * 3 + [C.c_void_p, stream_t]),
     'dpp_crop_prepare_ranged_src': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                               C.c_void_p, C.c_void_p, stream_t]),
     'dpp_crop_warp_src': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, stream_t]),

@@ -143,9 +143,28 @@ masked again to the same bits.  The per-track and per-source detectors take view
 size and joint_visibility see the masked frame.  learn_background(frames) (None where a source sits out) is a plan of its own: upload,
 [frame_ingest], background_learn, then the cut maps of the sources that took part.  background_model(c) / set_background_model(c,
 model) / clear_background([c]) let a rig learn once and reload.  A model that was never learned is the neutral element.  Out of scope:
-updating the model while tracking, per-source options, a cut inside the ingest kernel, the host HandDetector API, morphological
-clean-up of the mask, mixed pixels at object edges, choosing margin / rel for a sensor.  background=None: allocation, uploads, plans,
-result block and keys are those of before.
+per-source options, a cut inside the ingest kernel, the host HandDetector API, morphological clean-up of the mask, mixed pixels at
+object edges, choosing margin / rel (or persist / guard) for a sensor.  background=None: allocation, uploads, plans, result block and
+keys are those of before.
+
+ADAPTATION (additive to ABI v25: dpp_frame_background_adapt; this project's own, restated by tests/background_adapt_ref.py).  A model
+learned once goes stale: a cup put on the desk is the nearest object from then on, and something taken away leaves a cut that is too
+near.  With background=dict(..., adapt=dict(persist=, guard=, every=1)) the plan's frame_background launch is frame_background_adapt,
+the launch count unchanged: in the pass that cuts the frame it also confirms the model where the raw depth lies in its band
+(near = min, seen += 1), counts a depth that stays elsewhere as a candidate (cand, run; the model's own band around cand) and
+replaces the model with it after `persist` adapting ticks, and rewrites the cut map on the device, in the host's float32 arithmetic,
+where the model changed; the new cut holds from the next tick on.  What must not be learned is on the device already: track_refine
+left every track's final crop window in the records buffer, and the pixels inside a window of the source, dilated by `guard`, only
+lose their candidate.  The host sets take[c] = 1 when source c delivered a fresh frame, the tick's number (process() calls and
+sequence ticks alike) is a multiple of `every`, and no track on c was restarted from the host since c's last tick -- reset, acquire,
+acquire_source, the automatic peer_com reset, a set_hand that changes the hand: such a track's window is stale for one tick; take is
+uploaded only when it changes, one array per input set.  A source with take 0 runs the plain cut and reads no model array; its
+stale frame is cut again, possibly by a newer cut.  set / clear / learn_background zero the candidates of the sources they touch;
+background_model(c) returns the adapted model; the detectors take views of the cut map and do not adapt.  Known limits: a lost or
+gated track has no window, so its hand is absorbed if it stays still for `persist` adapting ticks; a forearm outside the crop window
+can be absorbed, and recedes again once it moves; a hand handed over on the device is unprotected for one tick (persist >= 2 keeps
+that tick from changing `near` through a candidate); no per-source options, and no persist / guard chosen for a sensor.  adapt absent:
+allocation, uploads, plans, result block and keys are those of before.
 
 acquire_source(c, frame) finds ALL hands of a source in one detector plan and starts the source's tracks from them; the detectors
 are built per source, at that source's size and focal lengths, on views of its frame slice.
@@ -161,7 +180,7 @@ import numpy as np
 
 from . import ops
 from .augmenter import camera_tuple
-from .tracker import IDLE, LOST, OK, ResultBlock, _engine, check_frame, frame_stage, refine_stage, smooth_fields, timing_fields, track_fields, valid_centre, visibility_fields
+from .tracker import IDLE, LOST, OK, AdaptClock, ResultBlock, _engine, check_frame, frame_stage, refine_stage, smooth_fields, timing_fields, track_fields, valid_centre, visibility_fields
 
 
 class MultiTracker(object):
@@ -195,7 +214,9 @@ class MultiTracker(object):
                            an instant `now`; every track is brought to `now` before tracks are combined, and `smooth` filters over the
                            stamps -- its `rate` is still validated but goes unread (TIMING above)
         :param background: None, or dict(margin=, rel=0.0, min_seen=1), for ALL sources: a learned per-pixel background is removed from
-                           every frame as the plan's first step (BACKGROUND above); margin (mm) has no default
+                           every frame as the plan's first step (BACKGROUND above); margin (mm) has no default.  With
+                           adapt=dict(persist=, guard=, every=1) among its keys the models are kept current while tracking, by the
+                           same launch (ADAPTATION above); persist (ticks) and guard (pixels) have no default
         """
         self.rt = rt
         tracks = [(int(s), bool(r)) for s, r in tracks]
@@ -263,7 +284,8 @@ class MultiTracker(object):
         self._pstride = self.partial.size // C
         self.background = None if background is None else ops.background_spec(background)
         # near, seen, cut and take in the frames' own layout (with a table: the ragged one)
-        self.bg = None if background is None else ops.BackgroundModel(rt, self.background, C, self.H, self.W, table=self.table)
+        self.bg = None if background is None else ops.BackgroundModel(rt, background, C, self.H, self.W, table=self.table)
+        self.adapt = None if self.bg is None or self.bg.adapt is None else AdaptClock(rt, C, self.bg.adapt[2])
         self._learn = None
         self.rec = rt.alloc(T * rt.lib.dpp_crop_record_bytes(), np.uint8)
         self.cube = rt.alloc((T, 3), f32)
@@ -371,6 +393,8 @@ class MultiTracker(object):
             self.sstate.clear(t)
         if self.astate is not None:
             self.astate.clear(t)
+        if self.adapt is not None:                      # the window the device holds for t is not this hand's: its source sits one tick out
+            self.adapt.restart(self.src_host[t])
 
     def drop(self, t):
         """Mark track t lost: the application knows what the tracker cannot see (the only loss test is a centre at depth 0) -- its
@@ -444,9 +468,11 @@ class MultiTracker(object):
         for c, f in enumerate(fresh):
             if f is not None:
                 bg.refresh(c)
+                bg.forget_candidates(c)
 
     def background_model(self, c=None):
-        """dict(near, seen, cut) of source c ((H, W) arrays of its size), or the list of all sources' without c."""
+        """dict(near, seen, cut) of source c ((H, W) arrays of its size), or the list of all sources' without c.  With adapt these are
+        the adapted ones."""
         self.rt.synchronize()
         bg = self._model()
         return [bg.get(s) for s in range(self.C)] if c is None else bg.get(c)
@@ -480,6 +506,8 @@ class MultiTracker(object):
         self.com_host[t] = coms[0]
         if ok:                                                                     # a restart, as reset(t, com) is
             self._clear_row(t)
+        elif self.adapt is not None:
+            self.adapt.restart(c)
         return dict(com=coms[0], cube=cubes[0], found=ok)
 
     def source_detector(self, c, max_extent=None):
@@ -615,7 +643,10 @@ class MultiTracker(object):
             raw = self._inputs2 if slot else self.raw
             p = ops.Plan('multitrack')
             # frame_range; with a sensor frame_ingest in its place; with a background frame_background, which then writes the partials
-            for op in frame_stage(rt, fr, raw, C, H, W, self.partial, self.sensor, None if self.bg is None else self.bg.cut, table=self.table):
+            # ... and with adapt the adapting cut in ITS place: the windows track_refine left in `rec` in the last tick are kept out
+            adapt = None if self.adapt is None else dict(bg=self.bg, take=self.adapt.buf(slot), records=self.rec, T=T, src=self.src)
+            for op in frame_stage(rt, fr, raw, C, H, W, self.partial, self.sensor, None if self.bg is None else self.bg.cut, table=self.table,
+                                  adapt=adapt):
                 p.add(op)
             # the T centres are read (prepare, track_refine) and then rewritten by one lane per track of track_refine: in place
             for op, side in refine_stage(rt, fr, H, W, self.partial, self.rec, self.com, self.cube, self.ceng, self.cam, self.fx, self.fy,
@@ -743,6 +774,8 @@ class MultiTracker(object):
         if not np.array_equal(gate, self.gate_host):
             self.gate.set(gate)
             self.gate_host = gate
+        if self.adapt is not None:
+            self.adapt.step([f is not None for f in fresh], 0)
         self.plan().run(self.rt)
         self.runs += 1
         self.rt.synchronize()
@@ -817,9 +850,12 @@ class MultiTracker(object):
                     self._gate2_host = gate
                 else:
                     self.gate_host = gate
+            plan = self.plan(k)
+            if self.adapt is not None:
+                self.adapt.step([f is not None for f in fresh], k)
             for ev in events:
                 rt.wait_event(ev)
-            self.plan(k).run(rt)
+            plan.run(rt)
             self.runs += 1
             free[k] = rt.record_event() if staged else None
             handle = (rt.read_async(self.res), rt.read_async(self.crop) if return_crops else None, gate)

@@ -814,14 +814,14 @@ def frame_ingest(rt, raw, B, H, W, frames, partial, median=False, mirror=False, 
 
 # ---- a learned static background removed from the frame (include/dpp_hip.h, ABI v25; csrc/background.hip) -------------------------------
 def background_spec(background):
-    """dict(margin=, rel=0.0, min_seen=1) checked on the host -> (margin, rel, min_seen); such a tuple (a tracker hands its own to its
-    detectors) passes through.  margin (mm, finite, >= 0) is required: none has been chosen for a sensor.  0 <= rel < 1; min_seen an
-    int >= 1."""
+    """dict(margin=, rel=0.0, min_seen=1[, adapt=dict(persist=, guard=, every=1)]) checked on the host -> (margin, rel, min_seen); such
+    a tuple (a tracker hands its own to its detectors, which never adapt) passes through.  margin (mm, finite, >= 0) is required: none
+    has been chosen for a sensor.  0 <= rel < 1; min_seen an int >= 1.  adapt is checked here and read by background_adapt_spec."""
     if isinstance(background, tuple):
         return background
-    known = ('margin', 'rel', 'min_seen')
+    known = ('margin', 'rel', 'min_seen', 'adapt')
     if not isinstance(background, dict) or set(background) - set(known):
-        raise ValueError("background takes margin, rel and min_seen, not %r" %
+        raise ValueError("background takes margin, rel, min_seen and adapt, not %r" %
                          (sorted(set(background) - set(known)) if isinstance(background, dict) else background,))
     s = dict(rel=0.0, min_seen=1)
     s.update(background)
@@ -837,7 +837,42 @@ def background_spec(background):
         raise ValueError("rel is a share of the depth, 0 <= rel < 1: %r" % (s['rel'],))
     if seen != s['min_seen'] or not 1 <= seen < 2 ** 31:
         raise ValueError("min_seen is a number of frames >= 1: %r" % (s['min_seen'],))
+    _adapt_spec(s.get('adapt'), seen)
     return margin, rel, seen
+
+
+def _adapt_spec(adapt, min_seen):
+    if adapt is None:
+        return None
+    known = ('persist', 'guard', 'every')
+    if not isinstance(adapt, dict) or set(adapt) - set(known):
+        raise ValueError("adapt takes persist, guard and every, not %r" % (sorted(set(adapt) - set(known)) if isinstance(adapt, dict) else adapt,))
+    a = dict(every=1)
+    a.update(adapt)
+    for k in ('persist', 'guard'):
+        if k not in a:
+            raise ValueError("adapt needs %s: no default has been chosen for a sensor" % k)
+    out = []
+    for k, low in (('persist', max(2, min_seen)), ('guard', 0), ('every', 1)):
+        try:
+            v = int(a[k])
+        except (TypeError, ValueError):
+            raise ValueError("adapt takes integers: %s = %r" % (k, a[k]))
+        if isinstance(a[k], bool) or v != a[k] or not low <= v < 2 ** 31:
+            raise ValueError("adapt's %s is an integer >= %d%s: %r" % (k, low, " (max(2, min_seen))" if k == 'persist' else "", a[k]))
+        out.append(v)
+    return tuple(out)
+
+
+def background_adapt_spec(background):
+    """None, or (persist, guard, every) of background=dict(..., adapt=dict(persist=, guard=, every=1)): the model is kept current while
+    tracking.  persist (adapting ticks until a depth that stays becomes the background, an int >= max(2, min_seen)) and guard (pixels
+    around a track's crop window that are kept out, an int >= 0) have no default; every (ticks, an int >= 1): the tracker adapts in
+    the ticks whose number is a multiple of it.  A tuple (background_spec's own result) has no adapt."""
+    if isinstance(background, tuple):
+        return None
+    min_seen = background_spec(background)[2]              # first: whatever is no dict of the known keys is its ValueError
+    return _adapt_spec(background.get('adapt'), min_seen)
 
 
 def background_cut(near, seen, spec):
@@ -863,6 +898,25 @@ def frame_background(rt, frames, cut, B, H, W, partial, name='frame_background',
     return Launch(fn, args, keep, name, dict(kernel='frame_background', flops=4.0 * npx, bytes=3 * 4.0 * npx))
 
 
+def frame_background_adapt(rt, frames, bg, take, B, H, W, records, T, src, partial, name='frame_background_adapt', table=None):
+    """dpp_frame_background_adapt: frame_background on `frames` with bg's cut map as it stands, and in the same pass bg (a
+    BackgroundModel with adapt=) adapted from the raw depths of the sources with take[c] != 0 (tests/background_adapt_ref.py):
+    near / seen confirmed, cand / run counted, the model replaced at persist, the cut map rewritten where the model changed.
+    records: the crop records of T tracks as track_refine left them (their windows, dilated by guard, are kept out), src [T] int32
+    their sources (None: track t reads frame t); records None: nothing is kept out."""
+    margin, rel, min_seen = bg.spec
+    persist, guard, _ = bg.adapt
+    head = (frames.ptr, bg.cut.ptr, bg.near.ptr, bg.seen.ptr, bg.cand.ptr, bg.run.ptr, take.ptr)
+    tail = (_p(records), int(T) if records is not None else 0, _p(src), margin, rel, min_seen, persist, guard, _p(partial))
+    keep = (frames, bg.cut, bg.near, bg.seen, bg.cand, bg.run, take, records, src, partial)
+    if table is None:
+        fn, args, npx = rt.lib.dpp_frame_background_adapt, head + (B, H, W) + tail, float(B) * H * W
+    else:
+        fn, args, npx, keep = rt.lib.dpp_frame_background_adapt_src, head + (table.dev.ptr, table.C) + tail, table.npx, keep + (table.dev,)
+    # per pixel at the most: six arrays read and written; the cut's compares, two bands and a cut map's three operations, min / max
+    return Launch(fn, args, keep, name, dict(kernel='frame_background_adapt', flops=16.0 * npx, bytes=12 * 4.0 * npx))
+
+
 def background_learn(rt, frames, take, B, H, W, near, seen, name='background_learn', table=None):
     """dpp_background_learn: one float32 frame per source into the model (near: the smallest non-zero depth; seen: the frames with a
     depth); take (int32 per source): 0 leaves that source's model untouched.  table: dpp_background_learn_src, as frame_background."""
@@ -880,10 +934,13 @@ class BackgroundModel(object):
     or with a SourceTable the ragged one): `near` (float32), `seen` (int32), `cut` (float32, what frame_background reads; +inf until
     refresh() after something was learned or set) and `take` (int32 [C], background_learn's per-source switch).  The model lives on
     the device; refresh() downloads it, computes the cut map on the host (background_cut) and uploads it: once per model change, never
-    per tick."""
+    per tick.  With spec's adapt= (background_adapt_spec) the model is also kept current by the plan's own cut launch
+    (frame_background_adapt), which rewrites the cut map on the device; `cand` (float32) and `run` (int32) are its candidate state in
+    the same layout (None without adapt), zeroed by set / clear / forget for the sources they touch."""
 
     def __init__(self, rt, spec, C, H=None, W=None, table=None):
         self.rt, self.spec, self.C, self.table = rt, background_spec(spec), int(C), table
+        self.adapt = background_adapt_spec(spec)
         if table is None:
             self.sizes, self.offs, n = [(int(H), int(W))] * self.C, [c * int(H) * int(W) for c in range(self.C)], self.C * int(H) * int(W)
         else:
@@ -892,6 +949,17 @@ class BackgroundModel(object):
         self.cut = rt.upload(np.full(n, np.inf, np.float32))
         self.take_host = np.ones(self.C, np.int32)
         self.take = rt.upload(self.take_host)
+        self.cand = self.run = None
+        if self.adapt is not None:
+            self.cand, self.run = rt.alloc((n,), np.float32), rt.alloc((n,), np.int32)
+
+    def forget_candidates(self, c=None):
+        """Zero cand / run (of source c, or of all): what was counted belongs to a model that was set, cleared or learned since."""
+        if self.adapt is not None:
+            for s in self._sources(c):
+                H, W = self.sizes[s]
+                self.view(self.cand, s).set(np.zeros((H, W), np.float32))
+                self.view(self.run, s).set(np.zeros((H, W), np.int32))
 
     def view(self, buf, c):
         """Source c's (1, H, W) part of one of the model's buffers."""
@@ -924,6 +992,7 @@ class BackgroundModel(object):
             self.view(self.near, s).set(np.zeros((H, W), np.float32))
             self.view(self.seen, s).set(np.zeros((H, W), np.int32))
             self.view(self.cut, s).set(np.full((H, W), np.inf, np.float32))
+        self.forget_candidates(c)
 
     def get(self, c):
         """dict(near, seen, cut) of source c, (H, W) each, downloaded."""
@@ -941,6 +1010,7 @@ class BackgroundModel(object):
         self.view(self.near, s).set(near.astype(np.float32))
         self.view(self.seen, s).set(seen.astype(np.int32))
         self.refresh(s)
+        self.forget_candidates(s)
 
 
 def crop_prepare_ranged(rt, partial, B, com, cube, fx, fy, dsz, records, M_out=None, stretch=False, name='crop_prepare_ranged', tracks=None):

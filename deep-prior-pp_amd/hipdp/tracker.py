@@ -46,9 +46,17 @@ one frame_ingest runs without partials and frame_background follows it (one laun
 one cut map; the detector (acquire, hand_size) and joint_visibility see the masked frame.  learn_background(frame) is a plan of its
 own (upload, [frame_ingest], background_learn, then the cut map); background_model() / set_background_model() / clear_background()
 let a rig learn once and reload.  A model that was never learned is the neutral element: every output is that of a tracker without
-the option.  background=None is the plan above, untouched.  Out of scope: updating the model while tracking, per-source options, a
-cut inside the ingest kernel, the host HandDetector API, morphological clean-up of the mask, mixed pixels at object edges, choosing
-margin / rel for a sensor.
+the option.  background=None is the plan above, untouched.  Out of scope: per-source options, a cut inside the ingest kernel, the
+host HandDetector API, morphological clean-up of the mask, mixed pixels at object edges, choosing margin / rel for a sensor.
+
+ADAPTATION.  background=dict(..., adapt=dict(persist=, guard=, every=1)) keeps that model current while tracking (hipdp/multitrack.py,
+ADAPTATION; tests/background_adapt_ref.py is the definition): frame_background_adapt stands in frame_background's place, cuts the
+frame with the cut map as it stands and, from the raw depth, confirms the model, counts a depth that stays elsewhere for `persist`
+adapting ticks before it replaces the model, and rewrites the cut map on the device where the model changed.  The pixels inside the
+crop window track_refine left in the last tick, dilated by `guard`, are kept out.  The tracker adapts in every `every`-th tick, and
+not in the tick after reset / acquire / a set_hand that changes the hand (the window on the device is stale there).  Known limits: a
+lost track has no window, so a hand that rests for `persist` adapting ticks after the track was lost is absorbed; a forearm outside
+the window can be absorbed and recedes once it moves; persist and guard have no default, none has been chosen for a sensor.
 """
 import numpy as np
 
@@ -104,18 +112,56 @@ def refine_stage(rt, frame, H, W, partial, rec, com_in, cube, ceng, cam, fx, fy,
     return out
 
 
-def frame_stage(rt, fr, raw, B, H, W, partial, sensor, cut=None, table=None):
+def frame_stage(rt, fr, raw, B, H, W, partial, sensor, cut=None, table=None, adapt=None):
     """The launches that open a plan on B frames (with a table: on its sources): they leave the float32 frames in `fr` and their
     depth-range partials in `partial`.  frame_range; with a sensor (ops.sensor_spec's tuple) frame_ingest from `raw` in its place;
-    with a background cut map frame_background in frame_range's place, behind a frame_ingest that then writes no partials."""
+    with a background cut map frame_background in frame_range's place, behind a frame_ingest that then writes no partials.  adapt
+    (dict(bg=, take=, records=, T=, src=); cut is then bg's): frame_background_adapt in frame_background's place, the same count."""
     out = []
     if sensor is not None:
         out.append(ops.frame_ingest(rt, raw, B, H, W, fr, partial if cut is None else None, median=sensor[1], mirror=sensor[2], table=table))
     elif cut is None:
         out.append(ops.frame_range(rt, fr, B, H, W, partial, table=table))
-    if cut is not None:
+    if adapt is not None:
+        out.append(ops.frame_background_adapt(rt, fr, adapt['bg'], adapt['take'], B, H, W, adapt['records'], adapt['T'], adapt['src'], partial,
+                                              table=table))
+    elif cut is not None:
         out.append(ops.frame_background(rt, fr, cut, B, H, W, partial, table=table))
     return out
+
+
+class AdaptClock(object):
+    """The host's side of background adaptation for a tracker of C sources: which sources adapt in a tick (`take`), kept per input set
+    in a device array that is uploaded only when it changes.  Source c adapts when it delivered a fresh frame, the tick's number
+    (counted over process() calls and sequence ticks alike) is a multiple of `every`, and no track on c was restarted from the host
+    since c's last tick: such a track's window on the device is stale (or empty) for one tick."""
+
+    def __init__(self, rt, C, every):
+        self.rt, self.C, self.every, self.tick = rt, int(C), int(every), 0
+        self.restarted = np.ones(self.C, bool)                  # nothing was tracked yet: no window to trust
+        self.bufs, self.hosts = [rt.alloc((self.C,), np.int32)], [np.zeros(self.C, np.int32)]
+
+    def buf(self, slot):
+        if slot == len(self.bufs):                              # process_sequence's second set, made when first used
+            self.bufs.append(self.rt.alloc((self.C,), np.int32))
+            self.hosts.append(np.zeros(self.C, np.int32))
+        return self.bufs[slot]
+
+    def restart(self, c):
+        self.restarted[c] = True
+
+    def step(self, fresh, slot=0):
+        """One tick with fresh[c] true where source c delivered a frame: the tick's take, uploaded into the slot's array if it differs
+        from what that array holds (the slot's last plan is behind us, as for the gates)."""
+        on = self.tick % self.every == 0
+        take = np.array([int(bool(f) and on and not r) for f, r in zip(fresh, self.restarted)], np.int32)
+        self.restarted &= ~np.asarray(fresh, bool)
+        self.tick += 1
+        buf = self.buf(slot)                                    # first: it makes the second set, hosts[slot] with it
+        if not np.array_equal(take, self.hosts[slot]):
+            buf.set(take)
+            self.hosts[slot] = take
+        return take
 
 
 def valid_centre(com):
@@ -217,7 +263,9 @@ class HandTracker(object):
                            there is no align launch (hipdp/multitrack.py, TIMING)
         :param background: None, or dict(margin=, rel=0.0, min_seen=1): a learned per-pixel background is removed from every frame as
                            the plan's first step (BACKGROUND above); margin (mm) has no default.  Nothing is removed until
-                           learn_background() / set_background_model()
+                           learn_background() / set_background_model().  With adapt=dict(persist=, guard=, every=1) among its keys
+                           the model is kept current while tracking, by the same launch (ADAPTATION above); persist (ticks) and
+                           guard (pixels) have no default
         """
         self.rt, self.H, self.W = rt, int(H), int(W)
         self.importer = importer
@@ -237,7 +285,8 @@ class HandTracker(object):
         self.inputs = self.frames if sensor is None else self.raw
         self.partial = ops.frame_range_workspace(rt, 1)
         self.background = None if background is None else ops.background_spec(background)
-        self.bg = None if background is None else ops.BackgroundModel(rt, self.background, 1, self.H, self.W)   # near, seen, cut, take
+        self.bg = None if background is None else ops.BackgroundModel(rt, background, 1, self.H, self.W)   # near, seen, cut, take[, cand, run]
+        self.adapt = None if self.bg is None or self.bg.adapt is None else AdaptClock(rt, 1, self.bg.adapt[2])
         self._learn = None
         self.rec = rt.alloc(rt.lib.dpp_crop_record_bytes(), np.uint8)
         self.cube = rt.alloc((1, 3), f32)
@@ -279,9 +328,12 @@ class HandTracker(object):
         self._clear_smooth()
 
     def _clear_smooth(self):
-        """A restart or another hand: what is followed now is not what was filtered (one 4-byte upload)."""
+        """A restart or another hand: what is followed now is not what was filtered (one 4-byte upload), and the crop window the
+        device holds is not this hand's: the background does not adapt in the next tick."""
         if self.sstate is not None:
             self.sstate.clear(0)
+        if self.adapt is not None:
+            self.adapt.restart(0)
 
     def detector(self):
         """The whole-frame detector on this tracker's buffers: frame slot 0 (and its raw buffer, with a sensor), the depth-range partials,
@@ -317,9 +369,11 @@ class HandTracker(object):
         self._learn.run(self.rt)
         self.rt.synchronize()
         bg.refresh()
+        bg.forget_candidates()
 
     def background_model(self):
-        """dict(near, seen, cut), (H, W) arrays: what set_background_model() of another tracker takes."""
+        """dict(near, seen, cut), (H, W) arrays: what set_background_model() of another tracker takes.  With adapt these are the
+        adapted ones."""
         self.rt.synchronize()
         return self._model().get(0)
 
@@ -350,6 +404,8 @@ class HandTracker(object):
         self.lost = not ok
         if ok:                                                                 # a restart, as reset(com) is
             self._clear_smooth()
+        elif self.adapt is not None:
+            self.adapt.restart(0)
         return dict(com=coms[0], cube=cubes[0], found=ok)
 
     def hand_size(self, tol=0.0):
@@ -387,8 +443,10 @@ class HandTracker(object):
             rt, H, W, fr = self.rt, self.H, self.W, self.frames[slot]
             p = ops.Plan('track')
             # frame_range; with a sensor raw -> fr and the same partials IN ITS PLACE; with a background the cut, which writes them
+            # ... and with adapt the adapting cut in ITS place: the window track_refine left in `rec` in the last tick is kept out
+            adapt = None if self.adapt is None else dict(bg=self.bg, take=self.adapt.buf(slot), records=self.rec, T=1, src=None)
             for op in frame_stage(rt, fr, None if self.sensor is None else self.raw[slot], 1, H, W, self.partial, self.sensor,
-                                  None if self.bg is None else self.bg.cut):
+                                  None if self.bg is None else self.bg.cut, adapt=adapt):
                 p.add(op)
             # the state buffer is read (prepare, track_refine) and then rewritten by ONE lane of track_refine: in place
             for op, side in refine_stage(rt, fr, H, W, self.partial, self.rec, self.com, self.cube, self.ceng, self.cam, self.fx, self.fy,
@@ -454,6 +512,8 @@ class HandTracker(object):
         self.inputs[0].set(frame)
         if when is not None:
             self.stamps[0].set(when)
+        if self.adapt is not None:
+            self.adapt.step([True], 0)
         self._slot = 0
         self.plan(0).run(self.rt)
         self.runs += 1
@@ -465,7 +525,13 @@ class HandTracker(object):
     def process_sequence(self, frames, return_crops=False):
         """A sequence of frames: the upload of frame t + 1 runs under the plan of frame t (two frame buffers, copy stream), the result
         of frame t is read while frame t + 1 is in flight.  Same values as process() frame by frame.  Stops at a lost frame (its
-        result is the last one returned).  With `timing` the sequence's entries are (frame, stamp)."""
+        result is the last one returned).  With `timing` the sequence's entries are (frame, stamp).
+
+        With `adapt` a lost frame leaves more behind than the process() loop would: frame n + 1 was launched before the host learnt
+        that frame n was lost, and only its RESULT is dropped.  Its tick has adapted the model, with an empty window, so nothing
+        was kept out, and has advanced the adaptation's tick counter by one.  One such tick changes `near` nowhere through a candidate
+        (persist >= 2), but it confirms, counts candidates and counts towards `every`.  After a lost frame neither the model nor the
+        tick counter is what the loop leaves; reset(com) restarts the track either way, and the tick after it does not adapt."""
         rt = self.rt
         staged = hasattr(rt, 'staged_upload')
         results, pending, free = [], None, [None, None]
@@ -491,7 +557,10 @@ class HandTracker(object):
                 self.inputs[k].set(frame)
                 if when is not None:
                     self.stamps[k].set(when)
-            self.plan(k).run(rt)
+            plan = self.plan(k)
+            if self.adapt is not None:
+                self.adapt.step([True], k)
+            plan.run(rt)
             self._slot = k
             self.runs += 1
             free[k] = rt.record_event() if staged else None

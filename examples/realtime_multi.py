@@ -55,7 +55,9 @@ as the plan's first step (MultiTracker background=, this project's own; the opti
 the static rectangle is pasted into every frame of both cameras, the models are learned from the first N ticks (default 5) with the
 hand taken out around each sequence's annotated first centre, and with --seed detect / detect-all the detector then starts from the
 hand and not from the rectangle.  Prints the share of pixels at which each camera's model knows a background.  Not with --fuse or
---half-res-second.
+--half-res-second.  --clutter ...:DEPTH:START pastes the rectangle only from tick START of the played sequences on (an object put down
+after learning), and --adapt PERSIST GUARD [--adapt-every N] keeps the models current while tracking (MultiTracker's adapt=): the
+rectangle is absorbed PERSIST adapting ticks later; prints the share of the rectangle each camera's model has taken over at the end.
 
     python examples/realtime_multi.py --dataset icvl --data ../data/ICVL/ --seqs test_seq_1 test_seq_2
 """
@@ -299,7 +301,11 @@ def main(argv=None):
     ap.add_argument('--background', nargs=2, type=float, default=None, metavar=('MARGIN', 'REL'),
                     help="remove a learned per-pixel background from every camera's frames: mm, and a share of the depth")
     ap.add_argument('--learn', type=int, default=5, metavar='N', help='with --background: the ticks the models are learned from')
-    ap.add_argument('--clutter', default=None, metavar='X0:Y0:X1:Y1:DEPTH', help='with --background: a static rectangle pasted into every frame')
+    ap.add_argument('--clutter', default=None, metavar='X0:Y0:X1:Y1:DEPTH[:START]',
+                    help='with --background: a static rectangle pasted into every frame (from tick START of the sequences on, and not while learning)')
+    ap.add_argument('--adapt', nargs=2, type=int, default=None, metavar=('PERSIST', 'GUARD'),
+                    help='with --background: keep the models current while tracking: ticks until a depth that stays is background, guard pixels')
+    ap.add_argument('--adapt-every', type=int, default=None, metavar='N', help='with --adapt: adapt in every N-th tick')
     ap.add_argument('--cache', default='./cache/')
     args = ap.parse_args(argv)
     Importer, seq_names, config = DATASETS[args.dataset]
@@ -330,8 +336,8 @@ def main(argv=None):
         raise SystemExit("--lag-second N (>= 0) needs --stamps")
     if args.background is not None and (args.fuse or args.half_res_second):
         raise SystemExit("--background is not combined with --fuse or --half-res-second")
-    if args.clutter is not None and args.background is None:
-        raise SystemExit("--clutter needs --background")
+    if (args.clutter is not None or args.adapt is not None or args.adapt_every is not None) and args.background is None:
+        raise SystemExit("--clutter and --adapt need --background")
     if args.fuse:
         import contextlib
         import io
@@ -373,22 +379,30 @@ def main(argv=None):
         bg_kw = {}
         if args.background is not None:                                # the rooms are not empty: the rectangle in every frame of both cameras
             bg = background_example()
-            clutter = bg.parse_clutter(args.clutter)
-            devices = [bg.ClutterDevice(f, di, clutter) for f in files]
+            clutter, start = bg.parse_clutter(args.clutter, with_start=True)
+            devices = [bg.ClutterDevice(f, di, clutter, first=start or 0) for f in files]
             bg_kw = dict(background=dict(margin=args.background[0], rel=args.background[1]))
+            if bg.parse_adapt(args) is not None:
+                bg_kw['background']['adapt'] = bg.parse_adapt(args)
         msp = MultiStreamPipeline(poseNetParams, cfg, dis, devices, hands, comrefNetParams, init_com=seeds, seed_detect=args.seed != 'gt',
                                   max_extent=args.max_extent, **dict(smooth_arg(args), **dict(visibility_arg(args), **bg_kw)))
         if bg_kw:                                                      # learn the rooms without the hand, then play the sequences
             n = min([max(1, args.learn)] + [len(f) for f in files])
             cz = float(config['cube'][2])
-            msp.devices = [bg.ClutterDevice(f[:n], di, clutter, hand=(float(s.data[0].gtorig[di.crop_joint_idx][2]), cz))
-                           for f, s in zip(files, seqs)]
+            msp.devices = [bg.ClutterDevice(f[:n], di, None if start is not None else clutter,
+                                            hand=(float(s.data[0].gtorig[di.crop_joint_idx][2]), cz)) for f, s in zip(files, seqs)]
             models = msp.learnBackground(n)
             msp.devices = devices
             msp.background_known = [float(numpy.isfinite(m['cut']).mean()) for m in models]
             print("background learned from {} ticks: known at {} of the pixels".format(
                 n, ', '.join("{:.1%} (camera {})".format(k, c) for c, k in enumerate(msp.background_known))))
-        return msp, msp.processVideos(max_frames=args.max_frames, overlapped=args.overlapped)
+        poses = msp.processVideos(max_frames=args.max_frames, overlapped=args.overlapped)
+        if bg_kw and clutter is not None and start is not None:        # how much of the late rectangle each camera's model has taken over
+            x0, y0, x1, y1, d = clutter
+            msp.background_absorbed = [float((numpy.abs(m['near'][y0:y1, x0:x1] - d) < 25.).mean()) for m in msp._tracker.background_model()]
+            print("background: the rectangle appeared in tick {}; absorbed at the end: {}".format(
+                start, ', '.join("{:.1%} (camera {})".format(k, c) for c, k in enumerate(msp.background_absorbed))))
+        return msp, poses
     msp, poses = run(args.half_res_second)
     t = numpy.asarray(msp.frame_times[1:] or msp.frame_times)         # the first tick records the plan
     print("{} ticks, {} tracks, {:.3f} ms per tick (median; {:.3f} ms mean)".format(len(msp.frame_times), T, numpy.median(t) * 1000., t.mean() * 1000.))

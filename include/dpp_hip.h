@@ -856,6 +856,35 @@ int dpp_background_learn(const float* frames, const int* take, int B, int H, int
 int dpp_background_learn_src(const float* frames, const int* take, const void* sources, int C, float* near_, int* seen,
                              dpp_stream_t stream);
 
+/* ---- ... kept current while tracking (additive to ABI v25: new symbols only -- DPP_ABI_VERSION stays 25, no existing prototype, record
+ * or result block changes) ------------------------------------------------------------------------------------------------------
+ * dpp_frame_background_adapt is dpp_frame_background -- the same grid, element partition and partials, frames cut IN PLACE by the cut
+ * map AS IT STOOD BEFORE the launch -- and adapts the model from the raw depth in the same pass.  This project's own semantics,
+ * restated by tests/background_adapt_ref.py.  Beside near / seen / cut, in their layout: cand (float32; 0: none), a depth that may
+ * become the background, and run (int32), the consecutive adapting ticks that supported it.
+ *   band(x) = float32(margin + float32(rel * x)), the cut map's roundings.
+ *   One launch, for source b with take[b] != 0 (take[b] == 0: the cut alone, no model array is read) and every pixel with raw depth f:
+ *     protected -- inside the window [xstart - guard, xstart + cw + guard) x [ystart - guard, ystart + ch + guard) of a track t with
+ *       src[t] == b (src NULL: t == b) whose crop record records[t] has cw > 0 and ch > 0:   cand = 0, run = 0, nothing else.
+ *     f == 0 (a hole):   nothing.
+ *     confirm, near != 0 and float32(near - band(near)) <= f <= float32(near + band(near)):
+ *       near = min(near, f); seen += 1 (saturating at 2^31 - 1); cand = 0, run = 0.
+ *     candidate, everything else:   cand != 0 and float32(cand - band(cand)) <= f <= float32(cand + band(cand)):
+ *       cand = min(cand, f), run += 1;   otherwise cand = f, run = 1.
+ *       run >= persist:   near = cand, seen = run, cand = 0, run = 0 -- the model is replaced.
+ *     where a pixel confirmed or was replaced, cut = float32(near - band(near)) where seen >= min_seen, near != 0 and the result is
+ *     > 0, else +inf: the bits of the host's cut map.  The new cut applies from the next launch on.
+ * records [T] crop records (dpp_crop_record_bytes() each) as dpp_track_refine left them in the previous tick: a lost or gated track
+ * has the empty window and protects nothing.  records NULL or T == 0: no protection.  T is any number >= 0.
+ * DPP_E_BADARG (nothing launched, nothing written): as dpp_frame_background, and any of the six buffers NULL or overlapping another
+ * (*_src: equal to another), take NULL, T < 0, margin or rel not finite, min_seen < 1, persist < 2 or < min_seen, guard < 0. */
+int dpp_frame_background_adapt(float* frames, float* cut, float* near_, int* seen, float* cand, int* run, const int* take, int B, int H,
+                               int W, const void* records, int T, const int* src, float margin, float rel, int min_seen, int persist,
+                               int guard, float* partial, dpp_stream_t stream);
+int dpp_frame_background_adapt_src(float* frames, float* cut, float* near_, int* seen, float* cand, int* run, const int* take,
+                                   const void* sources, int C, const void* records, int T, const int* src, float margin, float rel,
+                                   int min_seen, int persist, int guard, float* partial, dpp_stream_t stream);
+
 /* ---- whole-frame hand detection by connected components (ABI v14) -------------------------------------------------------------
  * What HandDetector.detect / estimateHandsize (handdetector.py:569-632, :911-937) take from cv2.findContours, restated with
  * 8-connected component labelling (csrc/components.hip): pixel count for contourArea, raster order for contour order, a depth

@@ -65,6 +65,16 @@ Further legs, same protocol (a child process per leg, the legs alternating, 2 pr
                                measured against the same sensor without `background`.  Claim (two-sided, needs --parent): with
                                background=None the tick and the plan's device time are each within the larger spread of the parent's.
                                The two deltas are reported against the average launch of their plan, without a claim.
+  --adapt [--parent DIR]       the tick with background=dict(margin=50, rel=0.01, adapt=dict(persist=5, guard=8, every=1 | 8)) at
+                               T = C = 8: dpp_frame_background_adapt in dpp_frame_background's place.  The cut is written in place, so a
+                               plan run again on its own frame buffer adapts from nothing (the wall is holes by then).  The adapting tick
+                               (take all 1) is therefore timed with a device-to-device copy in front of every run that puts the raw frames
+                               of that tick back; so are, for the difference, the same plan with take all 0 and background alone, and the
+                               copies alone.  The share of pixels that confirm in such a tick is reported with it.  The back-to-back time
+                               with take all 1 is reported as what it is, a lower bound.  Claims (two-sided, on back-to-back runs): with
+                               background alone the tick and the plan's device time are each within the larger spread of the parent's
+                               (needs --parent); a non-adapting tick's plan (take all 0) within the larger spread of background alone.
+                               The cost of an adapting tick is reported, not bounded.
 --configs 1x1,8x8 overrides a leg's (T, C) list.
 
 As in tools/track_bench.py the refinement net's last layer is zeroed, so every track stays on its seed whatever the random weights
@@ -280,6 +290,85 @@ def child(args):
                 out[name + '_device_ms_' + _key(T, C)] = device_time(mt.plan())
                 out[name + '_launches_' + _key(T, C)] = len(names)
                 assert not mt.lost.any()
+    elif args.leg == 'adapt':
+        from hipdp.multitrack import MultiTracker
+        far = dict(near=np.full((480, 640), 5000., np.float32), seen=np.ones((480, 640), np.int32))      # behind everything: nothing is cut
+        for T, C in configs:
+            pnet, snet = nets(T)
+            tracks = [(t % C, bool(t // C)) for t in range(T)]
+            # the frames of tick i as one device array per i: the raw depths are gone after the in-place cut, so a plan that is run
+            # again on its own frame buffer sees the holes the cut left and adapts nothing.  Every timed run is therefore preceded by a
+            # device-to-device copy that puts the raw frames of its tick back (in stream order, no host in between).
+            keep = [rt.upload(np.stack(tick_frames(i, C))) for i in range(nfr)]
+
+            def fresh_time(mt, copy_only=False):
+                """Device time per tick of [restore the raw frames of tick i; run the plan], i going round the nfr ticks; copy_only:
+                of the restoring copies alone."""
+                plan, vals = mt.plan(), []
+                assert mt.frames.size == keep[0].size and mt.sensor is None
+                for _ in range(reps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record(torch.cuda.current_stream())
+                    for i in range(N):
+                        rt.copy(mt.frames, keep[i % nfr])
+                        if not copy_only:
+                            plan.run(rt)
+                    e1.record(torch.cuda.current_stream())
+                    torch.cuda.synchronize()
+                    vals.append(e0.elapsed_time(e1) / N)
+                return vals
+
+            def set_take(mt, v):
+                take = np.full(C, v, np.int32)
+                mt.adapt.buf(0).set(take)
+                mt.adapt.hosts[0] = take
+
+            def share_confirmed(mt):
+                """Share of source 0's pixels that one more adapting tick on raw frames confirms (seen goes up)."""
+                set_take(mt, 1)
+                before = mt.bg.view(mt.bg.seen, 0).get()
+                rt.copy(mt.frames, keep[0])
+                mt.plan().run(rt)
+                rt.synchronize()
+                return float((mt.bg.view(mt.bg.seen, 0).get() != before).mean())
+            # background alone, by the same method: the reference of the two adapting plans
+            mt = MultiTracker(rt, di, pnet, snet, 480, 640, cube, tracks, background=dict(margin=50., rel=0.01))
+            for c in range(C):
+                mt.set_background_model(c, far)
+            for t in range(T):
+                mt.reset(t, com0)
+            for i in range(10):
+                assert all(r['status'] == 0 for r in mt.process(tick_frames(i, C)))
+            out['alone_fresh_device_ms_' + _key(T, C)] = fresh_time(mt)
+            out['copy_device_ms_' + _key(T, C)] = fresh_time(mt, copy_only=True)
+            for name, every in (('adapt1', 1), ('adapt8', 8)):
+                mt = MultiTracker(rt, di, pnet, snet, 480, 640, cube, tracks,
+                                  background=dict(margin=50., rel=0.01, adapt=dict(persist=5, guard=8, every=every)))
+                for c in range(C):
+                    mt.set_background_model(c, far)
+                for t in range(T):
+                    mt.reset(t, com0)
+
+                def tick(i):
+                    assert all(r['status'] == 0 for r in mt.process(tick_frames(i, C)))
+                for i in range(10 * every):                             # past persist adapting ticks: the scene has replaced the far model
+                    tick(i)
+                names = [l.name for l in mt.plan().launches()]
+                assert names[:2] == ['frame_background_adapt', 'crop_prepare_ranged'], names[:3]
+                out[name + '_ms_' + _key(T, C)] = timed(tick)
+                out[name + '_launches_' + _key(T, C)] = len(names)
+                # the take array as the host leaves it for an adapting (all 1) and for a non-adapting tick (all 0)
+                for key, v in (('on', 1), ('off', 0)):
+                    set_take(mt, v)
+                    # on raw frames: with take 1 the wall confirms in every run, as in a real adapting tick
+                    out['%s_%s_fresh_device_ms_%s' % (name, key, _key(T, C))] = fresh_time(mt)
+                    # the plan run again on the frame it has already cut (device_time's way): with take 1 a LOWER BOUND of an adapting
+                    # tick, the six arrays are read but nothing confirms and `seen` is not stored
+                    out['%s_%s_device_ms_%s' % (name, key, _key(T, C))] = device_time(mt.plan())
+                out[name + '_confirmed_' + _key(T, C)] = share_confirmed(mt)
+                assert out[name + '_confirmed_' + _key(T, C)] > 0.5, "the timed adapting ticks must confirm the scene"
+                assert not mt.lost.any()
     elif args.leg == 'timing':
         from hipdp import ops
         from hipdp.multitrack import MultiTracker
@@ -436,7 +525,8 @@ def main():
     ap.add_argument('--visibility', action='store_true', help="the grouped tick with joint visibility and the weighted fusion against this tree's and the parent's grouped tick (needs --parent)")
     ap.add_argument('--timing', action='store_true', help="the grouped tick with stamps and the alignment launch against this tree's and the parent's grouped tick (needs --parent)")
     ap.add_argument('--background', action='store_true', help="the tick with a learned background, without and with a sensor, against this tree's and the parent's tick")
-    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse', 'fuse_tick', 'calib', 'smooth', 'vis', 'timing', 'bg'], default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--adapt', action='store_true', help="the tick with background adapt= (every 1 and 8; adapting and non-adapting ticks) against the tick with background alone of this tree and of the parent")
+    ap.add_argument('--leg', choices=['multi', 'yardstick', 'mixed', 'sequence', 'fuse', 'fuse_tick', 'calib', 'smooth', 'vis', 'timing', 'bg', 'adapt'], default=None, help=argparse.SUPPRESS)
     ap.add_argument('--tree', default=ROOT, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.leg:
@@ -650,6 +740,48 @@ def main():
                                                                                      per, b[0] - m[0]))
             print("  with the sensor, one launch more: plan device time %+.2f us (spreads %.2f / %.2f us); the plan's average launch is %.2f us; "
                   "wall clock %+.4f ms" % ((dsb[0] - ds[0]) * 1e3, dsb[1] * 1e3, ds[1] * 1e3, per_s, sb[0] - s_[0]))
+        return 0 if ok else 1
+    if args.adapt:
+        cfgs = args.configs or '8x8'
+        res = run_legs(([('bg', ytree, 'parent_')] if args.parent else []) + [('bg', ROOT, ''), ('adapt', ROOT, '')], cfgs)
+        print("the tick with background=dict(..., adapt=) (dpp_frame_background_adapt in dpp_frame_background's place, the launch count unchanged) "
+              "against the tick with background alone of this tree%s; " % (' and of the parent checkout' if args.parent else '') + head)
+        print("all times in ms per tick: median (spread = max - min over the repetitions)")
+        ok = True
+        for c in cfgs.split(','):
+            T, C = (int(v) for v in c.split('x'))
+            k = _key(T, C)
+            b, db = _stat(res['bg_ms_' + k]), _stat(res['bg_device_ms_' + k])
+            a1, a8 = _stat(res['adapt1_ms_' + k]), _stat(res['adapt8_ms_' + k])
+            rp1, rp8, off8 = (_stat(res[n + '_device_ms_' + k]) for n in ('adapt1_on', 'adapt8_on', 'adapt8_off'))
+            al, cp = _stat(res['alone_fresh_device_ms_' + k]), _stat(res['copy_device_ms_' + k])
+            on1, of1, on8, of8 = (_stat(res[n + '_fresh_device_ms_' + k]) for n in ('adapt1_on', 'adapt1_off', 'adapt8_on', 'adapt8_off'))
+            print("T = C = %d, wall clock: background alone %.4f (%.4f); adapt every=1 %.4f (%.4f); adapt every=8 %.4f (%.4f)" % ((T,) + b + a1 + a8))
+            print("T = C = %d, plan device time, the plan run again on the frames it has cut: background alone %.4f (%.4f); take all 0 "
+                  "(a non-adapting tick) %.4f (%.4f); launches %d / %d / %d" % ((T,) + db + off8 + (
+                      res['bg_launches_' + k], res['adapt1_launches_' + k], res['adapt8_launches_' + k])))
+            if args.parent:
+                y, dy = _stat(res['parent_bg_ms_' + k]), _stat(res['parent_bg_device_ms_' + k])
+                print("T = C = %d, the parent's tick with background %.4f (%.4f), its plan's device time %.4f (%.4f)" % ((T,) + y + dy))
+                ok = two_sided('T = C = %d, the tick with background alone' % T, b, y, 'this tree', 'the parent') and ok
+                ok = two_sided('T = C = %d, the plan device time with background alone' % T, db, dy, 'this tree', 'the parent') and ok
+            ok = two_sided('T = C = %d, the plan device time of a non-adapting tick' % T, off8, db, 'adapt (take 0)', 'background alone') and ok
+            mb = 4. * C * 480 * 640 / 1e6
+            print("T = C = %d, device time of [a device copy puts the tick's raw frames back (%.1f MB read, %.1f MB written); the plan], so "
+                  "that every run sees depths to adapt from: the copies alone %.4f (%.4f); background alone %.4f (%.4f); every=1: take all "
+                  "0 %.4f (%.4f), take all 1 (an adapting tick) %.4f (%.4f); every=8: take all 0 %.4f (%.4f), take all 1 %.4f (%.4f)"
+                  % ((T, mb, mb) + cp + al + of1 + on1 + of8 + on8))
+            print("  share of source 0's pixels that one such adapting tick confirms: %.3f (every=1), %.3f (every=8)"
+                  % (res['adapt1_confirmed_' + k], res['adapt8_confirmed_' + k]))
+            two_sided('T = C = %d, take all 0 on raw frames (reported)' % T, of8, al, 'adapt (take 0)', 'background alone')
+            for nm, on, of in (('every=1', on1, of1), ('every=8', on8, of8)):
+                print("  an adapting tick, %s (six arrays read, the frame and `seen` stored, the rest where it changed; up to %.1f MB for "
+                      "%.1f MB): %+.2f us over the same plan with take all 0, %+.2f us over background alone (spreads %.2f / %.2f / %.2f us; "
+                      "no claim: reported)" % (nm, 12 * mb, 3 * mb, (on[0] - of[0]) * 1e3, (on[0] - al[0]) * 1e3, on[1] * 1e3, of[1] * 1e3, al[1] * 1e3))
+            print("  a LOWER BOUND, not an adapting tick: take all 1 with the plan run again on the frames it has cut (the wall is holes by "
+                  "then: the six arrays are read, nothing confirms, `seen` is not stored): %.4f (%.4f) at every=1, %.4f (%.4f) at every=8, "
+                  "%+.2f / %+.2f us over background alone" % (rp1 + rp8 + ((rp1[0] - db[0]) * 1e3, (rp8[0] - db[0]) * 1e3)))
+            print("  wall clock of the tick over background alone: %+.4f ms at every=1, %+.4f ms at every=8" % (a1[0] - b[0], a8[0] - b[0]))
         return 0 if ok else 1
     if args.calibrate:
         if not args.parent:
