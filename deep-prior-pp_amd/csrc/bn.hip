@@ -525,10 +525,15 @@ __global__ __launch_bounds__(DPP_THREADS) void bn_bwd_finalize_apply_kernel(cons
 
 bool ok_c(int C) { return C >= 4 && (C & 3) == 0 && (C >> 2) <= MAXQ && (DPP_THREADS % (C >> 2) == 0 || (C >> 2) > DPP_THREADS); }
 
+// The [M][C] tensors and the per-channel vectors are only ever accessed four channels at a time (16 bytes; 8 of a bf16-stored tensor):
+// a pointer off that boundary (NULL passes) is refused by the entry points below.  Partials, column sums, dbeta / dgamma go float by float.
+bool al4(const void* p, bool b16 = false) { return (reinterpret_cast<uintptr_t>(p) & (b16 ? 7 : 15)) == 0; }
+
 }  // namespace
 
 extern "C" int dpp_bn_stats_partial(const float* X, int M, int C, int rows_per_block, float* partial, int store, dpp_stream_t stream) {
     if (!X || !partial || M < 1 || rows_per_block < 1 || !ok_c(C) || (C >> 2) > DPP_THREADS || (store & ~DPP_ST_A)) return DPP_E_BADARG;
+    if (!al4(X, (store & DPP_ST_A) != 0)) return DPP_E_BADARG;
     int nb = dpp_cdiv(M, rows_per_block);
     if (store & DPP_ST_A)
         DPP_LAUNCH(bn_stats_partial_kernel<dpp_bf16>, dim3(nb), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream),
@@ -577,6 +582,7 @@ extern "C" int dpp_bn_bwd_reduce(const float* dA, const float* X, int M, int C, 
         return DPP_E_BADARG;
     const bool x16 = (store & DPP_ST_BNX) != 0, g16 = (store & DPP_ST_A) != 0;
     if (g16 != ((store & DPP_ST_C) != 0)) return DPP_E_UNSUPPORTED;            // dA and G are stored alike (G usually overwrites dA)
+    if (!al4(dA, g16) || !al4(G, g16) || !al4(X, x16) || !al4(mean) || !al4(inv_std) || !al4(scale) || !al4(beta)) return DPP_E_BADARG;
     int nb = dpp_cdiv(M, rows_per_block);
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define DPP_BR(TX_, TG_) DPP_LAUNCH((bn_bwd_reduce_kernel<TX_, TG_>), dim3(nb), dim3(DPP_THREADS), 0, st, reinterpret_cast<const TG_*>(dA), \
@@ -605,6 +611,8 @@ extern "C" int dpp_bn_bwd_apply(const float* G, const float* X, int M, int C, co
     if (!G || !X || !dX || M < 1 || rows_per_block < 1 || !ok_c(C) || (C >> 2) > DPP_THREADS || (store & ~(DPP_ST_BNX | DPP_ST_A | DPP_ST_C)))
         return DPP_E_BADARG;
     const bool x16 = (store & DPP_ST_BNX) != 0, g16 = (store & DPP_ST_A) != 0, o16 = (store & DPP_ST_C) != 0;
+    if (!al4(G, g16) || !al4(X, x16) || !al4(add, o16) || !al4(dX, o16) || !al4(mean) || !al4(inv_std) || !al4(scale) || !al4(c1) || !al4(c2))
+        return DPP_E_BADARG;
     const dim3 grid(dpp_cdiv(M, rows_per_block));
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define DPP_BA(TX_, TG_, TO_) DPP_LAUNCH((bn_bwd_apply_kernel<TX_, TG_, TO_>), grid, dim3(DPP_THREADS), 0, st, reinterpret_cast<const TG_*>(G), \
@@ -629,6 +637,9 @@ extern "C" int dpp_bn_bwd_finalize_apply(const float* G, const float* X, int M, 
     if (!G || !X || !dX || !partial || !dbeta || !dgamma || rows_per_block < 1 || (store & ~(DPP_ST_BNX | DPP_ST_A | DPP_ST_C))) return DPP_E_BADARG;
     if (!dpp_bn_bwd_finalize_apply_ok(M, C, nb)) return DPP_E_UNSUPPORTED;
     const bool x16 = (store & DPP_ST_BNX) != 0, g16 = (store & DPP_ST_A) != 0, o16 = (store & DPP_ST_C) != 0;
+    // (the block sums are read four at a time when nb % 4 == 0)
+    if (!al4(G, g16) || !al4(X, x16) || !al4(add, o16) || !al4(dX, o16) || !al4(mean) || !al4(inv_std) || !al4(scale) || ((nb & 3) == 0 && !al4(partial)))
+        return DPP_E_BADARG;
     const dim3 grid(dpp_cdiv(M, rows_per_block), C / 32);
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define DPP_BFA(TX_, TG_, TO_) DPP_LAUNCH((bn_bwd_finalize_apply_kernel<TX_, TG_, TO_>), grid, dim3(DPP_THREADS), 0, st, reinterpret_cast<const TG_*>(G), \

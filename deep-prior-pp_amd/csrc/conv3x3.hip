@@ -780,6 +780,11 @@ static int conv3x3_launch(const float* X, int N, int H, int W, int Ci, const dpp
                           dpp_stream_t stream) {
     if (!X || !Wk || !Y || N < 1 || H < 1 || W < 1 || Ci < 16 || (Ci & 15) || Co < 16 || (Co & 15)) return DPP_E_BADARG;
     if (store & ~(DPP_ST_A | DPP_ST_C | DPP_ST_BNX)) return DPP_E_BADARG;
+    // the halo and the weight slices are staged with one 16-byte load per channel quad (8 bytes of a bf16-stored X), the prologue's
+    // per-channel vectors likewise: no kernel here has a scalar form of those loads, so a pointer off that boundary is refused
+    if ((reinterpret_cast<uintptr_t>(X) & ((store & DPP_ST_A) ? 7 : 15)) || (reinterpret_cast<uintptr_t>(Wk) & 15)) return DPP_E_BADARG;
+    if (act && (act->mode & 2) && ((reinterpret_cast<uintptr_t>(act->mean) | reinterpret_cast<uintptr_t>(act->scale) | reinterpret_cast<uintptr_t>(act->beta)) & 15))
+        return DPP_E_BADARG;
     Conv3Args a;
     a.store = store;
     a.X = X; a.N = N; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co;
@@ -972,6 +977,10 @@ static int conv3x3_wgrad_launch(const float* X, int N, int H, int W, int Ci, con
                                 float* partial, int bm, int store, int precision, dpp_stream_t stream) {
     if (!X || !dY || !partial || N < 1 || Ci < 16 || (Ci & 15) || Co < 16 || (Co & 15) || (bm != 64 && bm != 128) || (store & ~(DPP_ST_A | DPP_ST_B))) return DPP_E_BADARG;
     const int y16 = (store & DPP_ST_B) ? 1 : 0;
+    // X, dY and the prologue vectors are staged four channels at a time (16 bytes, 8 of a bf16-stored tensor); the partials go float by float
+    if ((reinterpret_cast<uintptr_t>(X) & ((store & DPP_ST_A) ? 7 : 15)) || (reinterpret_cast<uintptr_t>(dY) & (y16 ? 7 : 15))) return DPP_E_BADARG;
+    if (act && (act->mode & 2) && ((reinterpret_cast<uintptr_t>(act->mean) | reinterpret_cast<uintptr_t>(act->scale) | reinterpret_cast<uintptr_t>(act->beta)) & 15))
+        return DPP_E_BADARG;
     Wgrad3Args a;
     a.X = X; a.N = N; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co; a.dY = dY; a.partial = partial;
     if (act && (act->mode & 4)) return DPP_E_UNSUPPORTED;       // the two-tensor BatchNorm-backward operand is a dpp_gemm feature

@@ -559,6 +559,11 @@ extern "C" int dpp_fc_gemm(const dpp_gemm_desc* dp, int precision, int kchunk, d
     if (ldc % 4 || (reinterpret_cast<uintptr_t>(d.splitk > 1 ? d.partial : d.C) & 15)) return DPP_E_UNSUPPORTED;
     if (d.residual && (reinterpret_cast<uintptr_t>(d.residual) & 15)) return DPP_E_UNSUPPORTED;
     if (d.splitk == 1 && d.bias && (reinterpret_cast<uintptr_t>(d.bias) & 15)) return DPP_E_UNSUPPORTED;     // one 16-byte load per column quad
+    // like dpp_gemm: the prologue's per-channel vectors are loaded 16 bytes at a time by every kernel here
+    auto vec_ok = [](const dpp_act& a) {
+        return !(a.mode & 2) || ((reinterpret_cast<uintptr_t>(a.mean) | reinterpret_cast<uintptr_t>(a.scale) | reinterpret_cast<uintptr_t>(a.beta)) & 15) == 0;
+    };
+    if (!vec_ok(d.actA) || !vec_ok(d.actB)) return DPP_E_BADARG;
     const int KC = kchunk == 0 ? 64 : kchunk;
     if (KC != 32 && KC != 64) return DPP_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -427,6 +427,8 @@ static int wgrad_stream_launch(const float* dY, int Co, const float* X, int Ci, 
     if (a.actX.mode & ~3) return DPP_E_UNSUPPORTED;
     if ((a.actX.mode & 2) && !(a.actX.mean && a.actX.scale && a.actX.beta && a.actX.cmod == Ci)) return DPP_E_BADARG;
     if ((reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(partial)) & 15) return DPP_E_BADARG;
+    // (the prologue's per-channel vectors are loaded 8 or 16 bytes at a time)
+    if ((a.actX.mode & 2) && ((reinterpret_cast<uintptr_t>(a.actX.mean) | reinterpret_cast<uintptr_t>(a.actX.scale) | reinterpret_cast<uintptr_t>(a.actX.beta)) & 15)) return DPP_E_BADARG;
     const int WR = shape_wr(Co, Ci);
     const dim3 grid(nsl / WR), block(DPP_THREADS);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -487,6 +489,8 @@ extern "C" int dpp_wgrad3_stream(const float* dY, int Co, const float* X, int Ci
     if (a.actX.mode & ~3) return DPP_E_UNSUPPORTED;
     if ((a.actX.mode & 2) && !(a.actX.mean && a.actX.scale && a.actX.beta && a.actX.cmod == Ci)) return DPP_E_BADARG;
     if ((reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(partial)) & 15) return DPP_E_BADARG;
+    // (the prologue's per-channel vectors are loaded 8 or 16 bytes at a time)
+    if ((a.actX.mode & 2) && ((reinterpret_cast<uintptr_t>(a.actX.mean) | reinterpret_cast<uintptr_t>(a.actX.scale) | reinterpret_cast<uintptr_t>(a.actX.beta)) & 15)) return DPP_E_BADARG;
     int WR, TG;
     shape3(Co, Ci, WR, TG);
     const dim3 grid(nsl / WR, 9 / TG), block(DPP_THREADS);
@@ -519,6 +523,7 @@ extern "C" int dpp_fc_wgrad_stream(const float* X, const float* dY, float* dW, i
     if (a.actX.mode & ~3) return DPP_E_UNSUPPORTED;
     if ((a.actX.mode & 2) && !(a.actX.mean && a.actX.scale && a.actX.beta && a.actX.cmod >= 4 && (a.actX.cmod & 3) == 0)) return DPP_E_BADARG;
     if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(dW)) & 15) return DPP_E_BADARG;
+    if ((a.actX.mode & 2) && ((reinterpret_cast<uintptr_t>(a.actX.mean) | reinterpret_cast<uintptr_t>(a.actX.scale) | reinterpret_cast<uintptr_t>(a.actX.beta)) & 15)) return DPP_E_BADARG;
     if (store & DPP_ST_B) DPP_LAUNCH((fc_wgrad_stream_kernel<8, dpp_bf16>), dim3(K / 128, N / 128), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), a);
     else DPP_LAUNCH((fc_wgrad_stream_kernel<8>), dim3(K / 128, N / 128), dim3(DPP_THREADS), 0, static_cast<hipStream_t>(stream), a);
     return dpp_launch_status();

@@ -15,7 +15,8 @@ from . import lib as _lib
 
 class Buffer(object):
     """A typed view of device memory: `ptr` (int), `shape`, `dtype`; `owner` (the allocation's tensor) keeps the allocation alive,
-    `keep` whatever else has to outlive the kernels queued on it (the inputs of an asynchronous producer)."""
+    `keep` whatever else has to outlive the kernels queued on it (the inputs of an asynchronous producer).  view() and reshape() hand
+    `keep` on; tests/guards.py relies on that: a guarded view keeps the Buffer of its whole allocation there and finds it again through it."""
     __slots__ = ('ptr', 'shape', 'dtype', 'owner', 'rt', 'keep')
 
     def __init__(self, rt, ptr, shape, dtype, owner):

@@ -146,6 +146,10 @@ typedef struct {
                          v_mfma_f32_16x16x32_bf16 -- BASELINE config 5.  Variant 4 with K = 32 / 64 only (dpp_gemm_variant_rows says
                          0 otherwise); dpp_fc_gemm takes its precision as an argument and ignores this field. */
 } dpp_gemm_desc;
+/* Alignment.  A, B (and actA.x2 / actA.out of a mode-4 operand) off a 16-byte boundary: variant 0 loads that operand one float at a time,
+ * variants 2-4 answer DPP_E_UNSUPPORTED.  C, residual, bias, epi.bn_x and the four epi.bn_* vectors off it: the one-float-per-store epilogue.
+ * The prologue vectors (mean, scale, beta, aux) must be 16-byte aligned: DPP_E_BADARG.  partial, epi.stats and epi.bn_partial are accessed
+ * one float at a time by every variant: 4-byte alignment is enough. */
 int dpp_gemm(const dpp_gemm_desc* d, dpp_stream_t stream);
 /* Would dpp_gemm run `d` on the kernel d->variant asks for (2, 3 or 4)?  Returns that kernel's rows per workgroup (the row-block count of
  * the fused-epilogue partials is M / rows), or 0: alignment, prologue mode or the epilogue rule it out and the caller should describe
@@ -167,6 +171,8 @@ int dpp_gemm_walk_grid(const dpp_gemm_desc* d, int* gx, int* gy);
  * ReLU prologue of the layer's input (NULL = none; modes 0-3).  rows_per_wave (a multiple of 4) pixel rows go to one wave; the
  * number of slices written is dpp_wgrad_stream_slices(Co, Ci, M, rows_per_wave) -- 0 when (Co, Ci) is not one of the shapes of the
  * ResNet's 1x1 layers (16x64, 64x16, 16x32, 64x32, 32x64, 32x128, 128x32, 128x64, 64x128, 64x256, 256x64, 256x128), for which
+ * (dY, X, partial and, with a mode 2 / 3 prologue, its mean / scale / beta must be 16-byte aligned -- here, in dpp_wgrad3_stream and in
+ * dpp_fc_wgrad_stream (dW for partial): they are only accessed 8 or 16 bytes at a time; DPP_E_BADARG otherwise, nothing launched)
  * dpp_gemm's generic filter-gradient layout (a_kc = b_kc = 0, splitk) remains.  Sum the slices with dpp_reduce_multi /
  * dpp_reduce_partials (fixed order).  T.grad of convlayer.py:230-240 (poseregnettrainer.py:110-111). */
 int dpp_wgrad_stream_slices(int Co, int Ci, int M, int rows_per_wave);
@@ -200,10 +206,13 @@ int dpp_wgrad3_stream(const float* dY, int Co, const float* X, int Ci, int N, in
  * precision 0: exact f32 (v_mfma_f32_16x16x4_f32; equals dpp_gemm up to summation order).
  * precision 1: operands rounded to bf16 (RNE, after the prologue), f32 accumulation (v_mfma_f32_16x16x32_bf16) -- BASELINE
  *              config 5; not for the 1e-3 mm parity path.
- * kchunk: 32 | 64 (0 = 64).  d->bm / bn / wm / variant are ignored; no fused statistics / BatchNorm-backward epilogue. */
+ * kchunk: 32 | 64 (0 = 64).  d->bm / bn / wm / variant are ignored; no fused statistics / BatchNorm-backward epilogue.
+ * Alignment: A or B off a 16-byte boundary is loaded one float at a time (and keeps the call off the three-stage kernel); C / partial,
+ * residual and bias off it: DPP_E_UNSUPPORTED; the mean / scale / beta of a mode 2 / 3 prologue off it: DPP_E_BADARG. */
 int dpp_fc_gemm(const dpp_gemm_desc* d, int precision, int kchunk, dpp_stream_t stream);
 
-/* out[i] = sum_z partial[z*n + i] (+ bias[i % nbias] if bias) -- fixed summation order (deterministic). */
+/* out[i] = sum_z partial[z*n + i] (+ bias[i % nbias] if bias) -- fixed summation order (deterministic).  One float per access:
+ * 4-byte alignment is enough (dpp_reduce_multi takes 16-byte accesses per job when n % 4 == 0 and the job's pointers allow them). */
 int dpp_reduce_partials(const float* partial, int nz, int n, const float* bias, int nbias, float* out,
                         dpp_stream_t stream);
 
@@ -219,7 +228,11 @@ int dpp_reduce_multi(const void* jobs_dev, int njobs, int total_blocks, dpp_stre
  * Y[n,y,x,o] = sum_{tap,c} act(X)[n, y+dy, x+dx, c] * Wk[o][tap][c] + bias[o] + residual[n,y,x,o], zero padding applied
  * after `act`.  conv2d 3x3 of res_block, /root/reference/src/net/resnet.py:365-368,394-397 via
  * /root/reference/src/net/convlayer.py:230-240.  The data gradient is the same call on dY with the weights from
- * dpp_conv3x3_wtrans.  bm = 64 | 128 rows per workgroup (0 = choose).  Ci, Co multiples of 16. */
+ * dpp_conv3x3_wtrans.  bm = 64 | 128 rows per workgroup (0 = choose).  Ci, Co multiples of 16.
+ * Alignment: X (8 bytes when bf16-stored, else 16), Wk and the prologue's mean / scale / beta must lie on 16-byte boundaries --
+ * DPP_E_BADARG otherwise, nothing is launched (they are only ever read 16 bytes at a time).  Y, residual, bias, epi->bn_x and the
+ * four epi->bn_* vectors may be 4-byte aligned: the call then takes the one-float-per-store epilogue (float32 tensors only; with a
+ * bf16-stored Y or bn_x DPP_E_UNSUPPORTED).  epi->stats and epi->bn_partial are accessed one float at a time. */
 int dpp_conv3x3(const float* X, int N, int H, int W, int Ci, const dpp_act* act, const float* Wk, int Co,
                 const float* bias, const float* residual, float* Y, int bm, const dpp_epilogue* epi,
                 int store /* DPP_ST_A: X, DPP_ST_C: Y + residual, DPP_ST_BNX: epi->bn_x hold bf16 */, dpp_stream_t stream);
@@ -231,7 +244,9 @@ int dpp_conv3x3_bf16(const float* X, int N, int H, int W, int Ci, const dpp_act*
  * wave-autonomous stream: a wave owns 16-pixel pieces of image rows, keeps the 9 x C x C filter in registers and loads every tap
  * straight from global memory -- no halo tile, no barrier before the column reductions.  dpp_conv3x3_stream_rows = pixels per
  * workgroup (= per block of epi->stats / epi->bn_partial), or 0 when the shape is not taken (then dpp_conv3x3_stream returns
- * DPP_E_UNSUPPORTED and dpp_conv3x3 remains).  Same arithmetic per output element as dpp_conv3x3 up to the summation order. */
+ * DPP_E_UNSUPPORTED and dpp_conv3x3 remains).  Same arithmetic per output element as dpp_conv3x3 up to the summation order.
+ * Alignment: X, Wk and the prologue vectors 16 bytes (DPP_E_UNSUPPORTED otherwise); Y, bias and everything in epi are accessed one
+ * float at a time: 4-byte alignment is enough. */
 int dpp_conv3x3_stream_rows(int N, int H, int W, int C);
 int dpp_conv3x3_stream(const float* X, int N, int H, int W, int C, const dpp_act* act, const float* Wk, const float* bias, float* Y,
                        const dpp_epilogue* epi, dpp_stream_t stream);
@@ -244,7 +259,9 @@ int dpp_conv3x3_wtrans(const float* Wk, int Co, int Ci, float* Wd, dpp_stream_t 
 size_t dpp_wtrans_job_bytes(void);
 int dpp_conv3x3_wtrans_multi(const void* jobs_dev, int njobs, int total_blocks, dpp_stream_t stream);
 /* Filter gradient partials: partial[blk][o][tap][c] = sum over the workgroup's pixels of dY[.,o] * act(X)[.+tap, c];
- * blk < dpp_conv3x3_wgrad_blocks(N,H,W,Ci,Co,bm); sum over blk with dpp_reduce_partials.  (T.grad, poseregnettrainer.py:110-111) */
+ * blk < dpp_conv3x3_wgrad_blocks(N,H,W,Ci,Co,bm); sum over blk with dpp_reduce_partials.  (T.grad, poseregnettrainer.py:110-111)
+ * Alignment: X, dY (8 bytes when bf16-stored, else 16) and the prologue vectors (16): DPP_E_BADARG otherwise, nothing launched; the
+ * partials are stored one float at a time: 4-byte alignment is enough. */
 int dpp_conv3x3_wgrad_blocks(int N, int H, int W, int Ci, int Co, int bm);
 int dpp_conv3x3_wgrad(const float* X, int N, int H, int W, int Ci, const dpp_act* act, const float* dY, int Co,
                       float* partial, int bm, int store /* DPP_ST_A: X, DPP_ST_B: dY hold bf16 */, dpp_stream_t stream);
@@ -263,7 +280,9 @@ int dpp_conv3x3_wgrad_bf16(const float* X, int N, int H, int W, int Ci, const dp
  * MaxPoolGrad gives the gradient to every element equal to the maximum, and the constant background of a depth crop
  * makes whole windows tie.
  * stats (may be NULL; needs H % 16 == W % 16 == 0): [2][Co][N * H/16 * W/16] per-tile (mean, M2) of the 64 pooled outputs a
- * workgroup writes -- the BatchNorm statistics partial of Y, combined by dpp_bn_finalize(rows_per_block = 64). */
+ * workgroup writes -- the BatchNorm statistics partial of Y, combined by dpp_bn_finalize(rows_per_block = 64).
+ * Alignment: dpp_stem_fwd stores the tie masks one byte at a time (any argmax pointer); dpp_stem_wgrad loads four channels of dY and
+ * of the tie mask at once when Co % 4 == 0, dY is 16-byte and argmax 4-byte aligned, and element by element otherwise. */
 int dpp_stem_fwd(const float* X, int N, int H, int W, const float* Wk, const float* bias, int Co, float* Y, uint8_t* argmax,
                  float* stats, int store /* DPP_ST_C: Y holds bf16 */, dpp_stream_t stream);
 int dpp_stem_wgrad_blocks(int N, int H, int W, int tiles_per_block);
@@ -278,7 +297,8 @@ int dpp_stem_wgrad(const float* X, int N, int H, int W, const float* dY, const u
  * (bit j = window element j, row-major, equals the maximum; NULL allowed when pool == 1 or in inference).
  * wgrad: partial[blk][Co][kh*kw][Ci], blk < dpp_convpool_wgrad_blocks(N, Hp, Wp); sum with dpp_reduce_multi.
  * dgrad: dX[N][H][W][Ci] = gradient w.r.t. the (activated) input operand.  Limits: Co <= 32, Ci <= 32, pool <= 4, k <= 7.
- * These layers are 12.8 MFLOP / sample in total: VALU kernels, one thread per output pixel. */
+ * These layers are 12.8 MFLOP / sample in total: VALU kernels, one thread per output pixel.  Every access to global memory is one
+ * element wide: no pointer needs more than its element's alignment. */
 int dpp_convpool_fwd(const float* X, int N, int H, int W, int Ci, const dpp_act* act, const float* Wk, int kh, int kw, int pad,
                      int Co, int pool, const float* bias, float* Y, uint16_t* ties, dpp_stream_t stream);
 int dpp_convpool_wgrad_blocks(int N, int Hp, int Wp);
@@ -297,7 +317,11 @@ int dpp_convpool_dgrad(const float* dY, const uint16_t* ties, int N, int H, int 
  * bwd_reduce:    G = dA * [ (x-mean)*scale+beta >= 0 ] (relu != 0) or dA; partial[2][C][nb] = sum G, sum G*xhat
  * bwd_finalize:  dbeta, dgamma and c1 = dbeta/M, c2 = dgamma/M; if q != NULL also q = scale*c1 and p = scale*inv_std*c2, the
  *                per-channel constants of the mode-4 operand prologue (dpp_act)
- * bwd_apply:     dX = scale * (G - c1 - xhat*c2) + add      (gradient through the batch statistics) */
+ * bwd_apply:     dX = scale * (G - c1 - xhat*c2) + add      (gradient through the batch statistics)
+ * Alignment: the [M][C] tensors (X, dA, G, add, dX: 16 bytes, 8 when bf16-stored) and the per-channel vectors that stats_partial,
+ * bwd_reduce, bwd_apply and bwd_finalize_apply READ (mean, inv_std, scale, beta, c1, c2) are accessed four channels at a time:
+ * DPP_E_BADARG otherwise, nothing launched; bwd_finalize_apply also reads `partial` 16 bytes at a time when nb % 4 == 0.  Partials,
+ * column sums, and everything finalize / bwd_finalize / eval_coeffs touch go one float at a time: 4-byte alignment is enough. */
 int dpp_bn_stats_partial(const float* X, int M, int C, int rows_per_block, float* partial, int store /* DPP_ST_A: X holds bf16 */,
                          dpp_stream_t stream);
 int dpp_bn_finalize(const float* partial, int nb, int nseg, int M, int rows_per_block, int C, const float* gamma, float eps,
